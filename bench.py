@@ -8,12 +8,16 @@ the reference's RLAlgo.train loop body does between evaluations
 (torchrl/algo/rl_algo.py:111-118), inputs resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full     (+ device-noise mode, probed kernel launches, peaks,
+                                                              secondary workloads, CPU baseline)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     (+ the last step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...          (no launcher: the script spawns its N ranks itself, one per GPU)
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -26,6 +30,7 @@ sys.path.insert(0, REPO)
 
 N_PER_GPU, T, BATCH_PER_GPU, OPT_EPOCHS = 2048, 128, 65536, 10
 D, H, A = 17, 64, 6
+UPDATES_PER_ITERATION = OPT_EPOCHS * N_PER_GPU * T // BATCH_PER_GPU
 # algorithmic FLOPs per sample of the fused minibatch-gradient kernel (2*MACs):
 # pf fwd 11136 + vf fwd 10496 + backward 2x(fwd) for both nets; log pi_old is cached
 # by the collector, so target_pf is not re-run (76032 - 11136)
@@ -41,10 +46,12 @@ class CountingLogger:
 
     def __init__(self):
         self.updates, self._later = 0, []
+        self.last = collections.deque(maxlen=UPDATES_PER_ITERATION)   # the latest info dicts (--dump-outputs)
 
     def add_update_info(self, d):
         self.drain()
         self.updates += 1
+        self.last.append(d)
 
     def add_update_infos_later(self, resolve):
         self._later.append(resolve)
@@ -54,7 +61,9 @@ class CountingLogger:
         cut = max(len(self._later) - leave, 0)
         later, self._later = self._later[:cut], self._later[cut:]
         for resolve in later:
-            self.updates += len(resolve())
+            infos = resolve()
+            self.updates += len(infos)
+            self.last.extend(infos)
 
     def add_epoch_info(self, *a, **k): pass
     def log(self, *a): pass
@@ -100,6 +109,40 @@ def iteration(agent, col, epoch):
     agent.update_per_epoch()                      # launched; its statistics are read in the next iteration (or at the end)
     agent.logger.drain(leave=1)                   # the PREVIOUS update's statistics, assembled while this rollout runs
     return len(collected["train_rewards"]), collected["train_epoch_reward"]   # consumed where RLAlgo.train consumes it
+
+
+DUMP_ENVS = 512                                   # rollout-buffer columns kept by --dump-outputs (a fixed, seeded sample)
+
+
+def snapshot_outputs(agent, col):
+    """What the last iteration handed its caller, as host arrays: both networks' parameters after the update, the rollout
+    buffer it was computed on (GAE's advantages and returns included) for a fixed seeded sample of DUMP_ENVS envs over all
+    T steps, the epoch reward with the number of episodes that finished, and the statistics of the iteration's updates.  Every
+    array has a fixed, non-empty shape (the finished episodes' returns are a list of varying length, possibly empty)."""
+    import torch
+    torch.cuda.synchronize()
+    out = {}
+    for net in ("pf", "vf"):
+        for i, p in enumerate(getattr(agent, net)._mlp2_param_list()):
+            out["%s_param%d" % (net, i)] = p.detach().float().cpu().numpy()
+    out["pf_logstd"] = agent.pf.logstd.detach().float().cpu().numpy()
+    buf = agent.replay_buffer
+    envs = torch.from_numpy(np.sort(np.random.RandomState(0).choice(buf.env_nums, DUMP_ENVS, replace=False)))
+    for key in buf._keys:
+        out["buffer_" + key] = getattr(buf, "_" + key).detach()[:, envs.to(buf.device)].float().cpu().numpy()
+    out["train_epoch_reward"] = np.array([col.train_epoch_reward], dtype=np.float64)
+    out["train_episodes_finished"] = np.array([len(col.train_rews)], dtype=np.float64)
+    infos = list(agent.logger.last)
+    for key in (infos[0] if infos else ()):
+        out["update_" + key.replace("/", "_")] = np.array([d[key] for d in infos], dtype=np.float64)
+    return out
+
+
+def dump_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log("wrote %d arrays (%.1f MB) to %s" % (len(outputs), sum(a.nbytes for a in outputs.values()) / 1e6, path))
 
 
 def log(msg):
@@ -602,8 +645,16 @@ def main():
                     help="multi-rank exchange of the 44 KB gradient / statistics: peer = xGMI-mapped buffers inside the "
                          "fold launch (fail if the self-check does not pass), rccl = all-reduce calls, auto = peer when its "
                          "self-check passes on every rank, else rccl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cfg 3 / cfg 5 epochs and the peak calibration")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the device-noise mode timed like it (the headline is then the "
+                         "reference-noise mode only while it costs at most PARITY_SLACK x that), the event-probed pass of "
+                         "the gradient kernel (roofline.achieved), stand-alone collective timings and, at one rank, peak "
+                         "calibration, secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the cfg 3 / cfg 5 epochs and the peak calibration")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="BASELINE.md section 3 literally: 3 warm-up + 20 timed whole CPU iterations (median / min / max); "
@@ -612,6 +663,8 @@ def main():
                     help="with --cpu-baseline-only: which workload's CPU baseline to time (tools/bench_{sac,dqn}.py)")
     ap.add_argument("--probe-graph-collectives", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("TRL_BENCH_DUMP_AFTER_S") and ("RANK" in os.environ or args.gpus == 1):   # diagnosing a wedged rank: every thread's stack, then exit
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["TRL_BENCH_DUMP_AFTER_S"]), exit=True)
@@ -792,26 +845,18 @@ def main():
             torch.distributed.barrier()
         return time.perf_counter() - t0, marks, read
 
-    # HIP events around every launch of the dominant kernel, on the stream it is launched on.  One process: the
+    # HIP events around every launch of the dominant kernel (--full), on the stream it is launched on.  One process: the
     # minibatch loop of the timed region replays a captured HIP graph, whose nodes cannot be bracketed by
     # events, so the same kernel on the same data is timed in a follow-up pass right after the timed region.
     graph_mode = (not dist.collectives_active() or dist.peer_ready() or os.environ.get("TRL_GRAPH_COLLECTIVES") == "1") \
         and os.environ.get("TRL_NO_GRAPH") != "1"
     probes = []
-    eng.probe = None if graph_mode else probes
-    elapsed, marks, infos_read = timed_region()
-    log("device-noise mode: timed %d iterations in %.3f s" % (args.steps, elapsed))
-    log("per-iteration ms: " + " ".join("%.2f" % (1e3 * (b - a)) for a, b in zip(marks[:-1], marks[1:])))
-    if graph_mode:
-        eng.probe = probes
-        run_iterations(PROBE_STEPS)
-        torch.cuda.synchronize()
-    eng.probe = None
     # The reference's exploration-noise stream (CPU torch generator, distribution.py:60-76 -- what the parity tests run)
     # at one rank: the same iteration with the NEXT rollout's block drawn by a host thread while the device works
     # (collector/on_policy.py::_NoisePrefetcher; bit-identical buffers and parameters to the in-place draws,
-    # tests/test_noise_prefetch_gpu.py).  Timed with the same protocol; it is the headline when it costs <= PARITY_SLACK.
-    device_elapsed, parity_elapsed = elapsed, None
+    # tests/test_noise_prefetch_gpu.py).  Timed with the same protocol; it is the headline when it costs <= PARITY_SLACK
+    # x the device-noise mode.  A plain run times it alone (it has been the headline of every recorded run); --full times
+    # the device-noise mode first and applies that rule.  Where it cannot run, the device-noise mode is the headline.
     col.noise_mode, col.prefetch_noise = "host", True
     can_parity = col._can_prefetch(T)                                   # this rank's rows of every step's draw, from derived states
     col.noise_mode, col.prefetch_noise = "device", False
@@ -819,6 +864,21 @@ def main():
         flag = torch.tensor([1.0 if can_parity else 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce_max_(flag.neg_())
         can_parity = float(flag.item()) == -1.0
+    device_elapsed, parity_elapsed = None, None
+    dump = args.dump_outputs and rank == 0
+    outputs = {}                                                        # noise mode -> its last timed step's outputs
+    if args.full or not can_parity:
+        eng.probe = probes if args.full and not graph_mode else None
+        device_elapsed, marks, infos_read = timed_region()
+        log("device-noise mode: timed %d iterations in %.3f s" % (args.steps, device_elapsed))
+        log("per-iteration ms: " + " ".join("%.2f" % (1e3 * (b - a)) for a, b in zip(marks[:-1], marks[1:])))
+        if dump:
+            outputs["device"] = snapshot_outputs(agent, col)
+        if args.full and graph_mode:
+            eng.probe = probes
+            run_iterations(PROBE_STEPS)
+            torch.cuda.synchronize()
+        eng.probe = None
     if can_parity:
         col.noise_mode, col.prefetch_noise = "host", True
         run_iterations(5, True)                                            # (first block drawn in place, pipeline primed)
@@ -834,18 +894,22 @@ def main():
                                              jump_ahead_passes=_noise.STATS["jump_passes"],
                                              native_helper=_noise.native_helper() is not None)
         log("per-iteration ms: " + " ".join("%.2f" % (1e3 * (b - a)) for a, b in zip(pmarks[:-1], pmarks[1:])))
+        if dump:
+            outputs["parity"] = snapshot_outputs(agent, col)
         col.stop_noise_prefetch()
         col.noise_mode, col.prefetch_noise = "device", False
     if dist.initialized():                                              # MAX over ranks of both timings, then ONE decision
-        tmax = torch.tensor([device_elapsed, parity_elapsed if parity_elapsed is not None else 0.0], dtype=torch.float64, device=dev)
+        tmax = torch.tensor([0.0 if t is None else t for t in (device_elapsed, parity_elapsed)], dtype=torch.float64, device=dev)
         dist.all_reduce_max_(tmax)
-        device_elapsed = float(tmax[0].item())
+        device_elapsed = float(tmax[0].item()) if device_elapsed is not None else None
         parity_elapsed = float(tmax[1].item()) if parity_elapsed is not None else None
-    elapsed = device_elapsed
-    headline_parity = parity_elapsed is not None and parity_elapsed <= PARITY_SLACK * device_elapsed
+    headline_parity = parity_elapsed is not None and (device_elapsed is None or parity_elapsed <= PARITY_SLACK * device_elapsed)
+    elapsed = parity_elapsed if headline_parity else device_elapsed
     if headline_parity:
-        elapsed, infos_read = parity_elapsed, pread
-    coll_us = time_collectives(dist, dev) if (dist.initialized() and dist.collectives_active()) else None
+        infos_read = pread
+    if dump:
+        dump_outputs(outputs["parity" if headline_parity else "device"], args.dump_outputs)
+    coll_us = time_collectives(dist, dev) if (args.full and dist.initialized() and dist.collectives_active()) else None
 
     if rank != 0:
         _shutdown_dist()
@@ -886,23 +950,25 @@ def main():
                    "parallelism": "env-sharded dp%d, gradient SUM %s" % (
                        world, "inside the fold/clip/Adam launch over peer-mapped xGMI buffers" if dist.peer_ready()
                        else ("by all-reduce calls (%s)" % transport if dist.collectives_active() else "not needed (one rank)"))},
-        "roofline": {"bound": "mfma", "kernel": "ppo_grad_wave_kernel<17,64,6,tanh>", "achieved": achieved,
-                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFLOPS,
+        "roofline": {"bound": "mfma", "kernel": "ppo_grad_wave_kernel<17,64,6,tanh>",
+                     "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "traffic": pmc_traffic()[0], "traffic_stamp": pmc_traffic()[1],
                      # traffic / mfma_busy are rocprofv3 --pmc figures of committed passes over THIS tree's kernel (the
                      # digest stamp says so), not values of this process: counters cannot be collected inside the timed run
                      "traffic_measured_in_this_run": False, "mfma_busy_measured_in_this_run": False,
-                     "flop_per_launch": flops, "avg_launch_us": avg_s * 1e6,
+                     "flop_per_launch": flops,
                      "whole_iteration_frac": FLOP_PER_ENV_STEP * env_steps / elapsed / world / 1e12 / MFMA_F32_PEAK_TFLOPS,
                      # the HBM side of the same iteration (north_star: fraction of the HBM roofline): SURVEY.md 8(d)'s 1 240
                      # algorithmic bytes per env-step against the nominal 8 TB/s -- the path is MFMA-bound, this says by how much
                      "hbm_whole_iteration_frac": BYTES_PER_ENV_STEP * env_steps / elapsed / world / 8e12,
                      "hbm_whole_iteration_GBps": BYTES_PER_ENV_STEP * env_steps / elapsed / world / 1e9,
-                     "mfma_busy": pmc_traffic()[2],
-                     "launches_timed": len(grad_ms),
-                     "timed_in": ("follow-up pass of %d iterations (the timed region replays a HIP graph)" % PROBE_STEPS)
-                     if graph_mode else "the timed region"},
+                     "mfma_busy": pmc_traffic()[2]},
     }
+    if args.full:                                                       # the event-probed launches of the dominant kernel
+        out["roofline"].update({"achieved": achieved, "frac": achieved / MFMA_F32_PEAK_TFLOPS, "avg_launch_us": avg_s * 1e6,
+                                "launches_timed": len(grad_ms),
+                                "timed_in": ("follow-up pass of %d iterations (the timed region replays a HIP graph)" % PROBE_STEPS)
+                                if graph_mode else "the timed region"})
     if backend is None and comm_info:
         out["config"].update(comm_info)                                    # (one rank: how the noise blocks travelled)
     if backend is not None:
@@ -917,13 +983,14 @@ def main():
         if os.environ.get("TRL_BENCH_SPAWNED") == "1":
             out["config"]["launcher"] = "bench.py spawned its own ranks"
     if parity_elapsed is not None:
-        out["device_noise_ms_per_step"] = 1e3 * device_elapsed / args.steps
+        if device_elapsed is not None:
+            out["device_noise_ms_per_step"] = 1e3 * device_elapsed / args.steps
         out["parity_mode_ms_per_step"] = 1e3 * parity_elapsed / args.steps
         out["config"]["headline_mode"] = "parity" if headline_parity else \
             "device (the reference-noise mode cost more than %.2fx on this host)" % PARITY_SLACK
         out["config"]["parity_mode"] = ("exploration noise from the CPU torch generator (reference stream, prefetched one rollout "
                                         "ahead), %d iterations timed like the headline" % args.steps)
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         out["peaks_measured"] = measure_peaks(dev)
         mf = out["peaks_measured"].get("f32_mfma_TFLOPs")
         if mf:
@@ -931,7 +998,7 @@ def main():
         if out["peaks_measured"].get("hbm_kernels"):
             out["roofline"]["hbm"] = out["peaks_measured"]["hbm_kernels"]
         out["secondary"] = secondary_workloads()
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_subprocess()
     print(json.dumps(out))
     _shutdown_dist()

@@ -18,7 +18,7 @@ def _bench(extra_env, gpus=2, extra_args=()):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(TRL_BENCH_DEVICE_MAP=",".join(["0"] * gpus), **extra_env)
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "3",
-                          "--no-cpu-baseline", "--no-secondary", *extra_args], env=env, stdout=subprocess.PIPE,
+                          "--full", "--no-cpu-baseline", "--no-secondary", *extra_args], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -105,7 +105,7 @@ def test_full_size_one_rank_with_the_collectives_forced_on(transport, want):
                TRL_FORCE_COLLECTIVES="1")
     env.pop("TRL_BENCH_DEVICE_MAP", None)
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "3",
-                          "--no-cpu-baseline", "--no-secondary", "--transport", transport], env=env, stdout=subprocess.PIPE,
+                          "--full", "--no-cpu-baseline", "--no-secondary", "--transport", transport], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -114,3 +114,32 @@ def test_full_size_one_rank_with_the_collectives_forced_on(transport, want):
     assert cfg["process_group_backend"] == "nccl" and cfg["transport_requested"] == transport
     assert out["n_gpus"] == 1 and out["value"] > 2e7                     # (a wedged or host-bound route would be far below)
     assert all(v > 0 for v in cfg["collective_us"].values())
+
+
+def test_plain_one_rank_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full times the headline alone (the CPU baseline, secondary workloads, peaks,
+    the probed launches and the device-noise comparison are --full's), and `--dump-outputs DIR` writes what the last timed
+    step computed as float32 / float64 arrays, 64 MB at most."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env.pop("TRL_BENCH_DEVICE_MAP", None)
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "3",
+                          "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["metric"] == "env_steps_per_sec_ppo_2048env_halfcheetah_shape" and out["unit"] == "env-steps/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3
+    assert abs(out["value"] - 2048 * 128 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+    assert out["config"]["headline_mode"] == "parity" and out["config"]["update_infos_read_in_timed_region"] == 3 * 40
+    assert not {"cpu_baseline", "secondary", "peaks_measured", "device_noise_ms_per_step"} & set(out)
+    assert "avg_launch_us" not in out["roofline"]
+    got = {p.name[:-len(".npy")]: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and a.size and np.isfinite(a).all() for a in got.values())
+    assert got["pf_param0"].shape == (64, 17) and got["vf_param5"].shape == (1,) and got["pf_logstd"].shape == (6,)
+    assert got["buffer_obs"].shape == (128, 512, 17) and got["buffer_advs"].shape == (128, 512, 1)
+    assert got["update_Training_policy_loss"].shape == (40,) and got["train_epoch_reward"].shape == (1,)
+    assert got["train_episodes_finished"].shape == (1,)

@@ -6,10 +6,10 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 T=${T:-r06z}
-# 1. the default bench line (cpu baseline, secondary workloads, peaks)
-python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.log; tail -1 $O/${T}_bench.json | cut -c1-400
+# 1. the full bench line (cpu baseline, secondary workloads, peaks)
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.log; tail -1 $O/${T}_bench.json | cut -c1-400
 # 2. kernel trace of the same command (short: no cpu baseline / secondary)
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary"
 rm -rf $O/prof_b; rocprofv3 --kernel-trace --stats -d $O/prof_b -- $B > $O/${T}_prof_bench.json 2>/dev/null
 python tools/kstats.py $(find $O/prof_b -name "*.db" | head -1) > $O/${T}_bench_kernel_stats.csv
 head -12 $O/${T}_bench_kernel_stats.csv | cut -c1-150
@@ -20,7 +20,7 @@ head -4 $O/${T}_bench_kernel_stats_joint.csv | cut -c1-150
 # 3. HBM traffic counters, separate passes; then the SQ counters of the same command (MFMA-busy of the headline kernel)
 #    -- joint launches: the counters of the 256-workgroup launch the roofline entry refers to
 export TRL_PPO_CHAINS=joint
-B3="python bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-secondary"
+B3="python bench.py --steps 3 --warmup 3 --full --no-cpu-baseline --no-secondary"
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/pmc_$c; rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- $B3 > /dev/null 2>&1
 done
@@ -46,12 +46,12 @@ for w in sac dqn qrdqn; do
 done
 rm -rf $O/prof_* $O/pmc_*
 # 5. two ranks on one GPU (peer transport), then BASELINE cfg 4's layout: eight ranks x 2048 envs on one GPU (all-reduce route)
-TRL_BENCH_DEVICE_MAP=0,0 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/${T}_bench_2ranks_one_gpu.json 2> $O/${T}_bench_2ranks.log
+TRL_BENCH_DEVICE_MAP=0,0 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $O/${T}_bench_2ranks_one_gpu.json 2> $O/${T}_bench_2ranks.log
 tail -1 $O/${T}_bench_2ranks_one_gpu.json | cut -c1-300
-TRL_BENCH_DEVICE_MAP=0,0,0,0,0,0,0,0 timeout 400 python bench.py --gpus 8 --steps 5 --warmup 3 --no-cpu-baseline --no-secondary > $O/${T}_bench_8ranks_one_gpu.json 2> $O/${T}_bench_8ranks.log
+TRL_BENCH_DEVICE_MAP=0,0,0,0,0,0,0,0 timeout 400 python bench.py --gpus 8 --steps 5 --warmup 3 --full --no-cpu-baseline --no-secondary > $O/${T}_bench_8ranks_one_gpu.json 2> $O/${T}_bench_8ranks.log
 tail -1 $O/${T}_bench_8ranks_one_gpu.json | cut -c1-300
 # 6. PPO iteration timeline (reference noise)
-rm -rf $O/prof_t; rocprofv3 --kernel-trace -d $O/prof_t -- python bench.py --steps 4 --warmup 3 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+rm -rf $O/prof_t; rocprofv3 --kernel-trace -d $O/prof_t -- python bench.py --steps 4 --warmup 3 --full --no-cpu-baseline --no-secondary > /dev/null 2>&1
 python tools/ktimeline.py $(find $O/prof_t -name "*.db" | head -1) 100 > $O/${T}_ppo_iteration_timeline_reference_noise.csv
 rm -rf $O/prof_t
 # 7. the host side of the reference noise stream (jump-ahead pass at 8 ranks), the conv input-gradient A/B

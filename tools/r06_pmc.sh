@@ -1,12 +1,12 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 T=r06z
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary"
 rm -rf $O/prof_b; TRL_PPO_CHAINS=joint rocprofv3 --kernel-trace --stats -d $O/prof_b -- $B > /dev/null 2>&1
 python tools/kstats.py $(find $O/prof_b -name "*.db" | head -1) > $O/${T}_bench_kernel_stats_joint.csv
 head -4 $O/${T}_bench_kernel_stats_joint.csv | cut -c1-150
 export TRL_PPO_CHAINS=joint
-B3="python bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-secondary"
+B3="python bench.py --steps 3 --warmup 3 --full --no-cpu-baseline --no-secondary"
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/pmc_$c; rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- $B3 > /dev/null 2>&1
 done
