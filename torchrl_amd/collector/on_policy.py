@@ -545,8 +545,14 @@ class VecOnPolicyCollector(VecCollector):
         """`n_steps` vector steps as per-step launch sequences.  On a device env with device noise and a ring that the
         rollout fills exactly, the whole sequence (~17 launches x n_steps) is captured into a HIP graph on its second
         visit and replayed afterwards -- the eager sequence is host-launch-bound (~190 us per step); the rollout's
-        exploration noise is then drawn up front in one Philox launch."""
+        exploration noise is then drawn up front in one Philox launch.
+        PPO's value chain (algo/on_policy/ppo.py::_FusedPPO._run_chains) may still be stepping the value function and
+        reading the ring's rows: this route waits for it on the current stream before its first copy, launch, capture or
+        replay -- it gives up running beside the value chain, which only the fused rollout (`_launch`) does."""
         env, buf = self.env, self.replay_buffer
+        from ..networks import nets as _nets
+        _nets.settle(self.pf, env.device)
+        _nets.settle(self.vf, env.device)
         D, A = self._dims
         graphable = (self.noise_mode == "device" and not getattr(env, "is_host_env", False)
                      and buf._top == 0 and n_steps == buf._max_replay_buffer_size)

@@ -41,9 +41,11 @@ def pending_event(net):
 
 
 def settle(net, device=None):
-    """Make the current stream wait for whatever is still writing `net`'s parameters on another stream."""
+    """Make the current stream wait for whatever is still writing `net`'s parameters on another stream.  Inside a stream
+    capture this does nothing: the event was recorded outside the capture, and every capture site waits on the current
+    stream before it captures or replays (`_FusedPPO._run_chains` / `run`, `VecOnPolicyCollector._rollout_per_step`)."""
     ev = _PENDING.get(net)
-    if ev is not None:
+    if ev is not None and not torch.cuda.is_current_stream_capturing():
         torch.cuda.current_stream(device).wait_event(ev)
 
 
