@@ -267,7 +267,7 @@ int trl_ppo_minibatch_grad_f32(const trl_ppo_batch_t* args, void* stream);
  *  8..11 mean / unbiased std / max / min of the clamped logstd (ppo.py:82-85)
  *  12..15 sum / sum of squares / max / -min of the value prediction (a2c.py:89-92)
  *  16..19 mean / unbiased std over the A dims / max / min of std = exp(clamped logstd) (a2c.py:95-100)
- *  20..23 unused
+ *  20 categorical heads: entropy sum (trl_cat_losses_f32)   21..23 unused
  * pf_params may be NULL (then 8..11 are left untouched). */
 int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
                        int D, int H, int A, const float* pf_params, float* grads, double* info,
@@ -290,6 +290,17 @@ int trl_ppo_generic_losses_f32(const float* mean, const float* logstd, const flo
                                float entropy_coeff, int clipped_value_loss, int tanh_action, int loss_mode,
                                float* d_mean, float* d_v, float* d_logstd, double* info, double* workspace,
                                void* stream);
+/* The same for a categorical head (CategoricalDisPolicy): logits (B, A), 2 <= A <= 64, acts (B) integer values as floats.
+ * p = softmax(l), log pi = log p_a, H = -sum_k p_k log p_k; advantage normalisation, ratio, clip, tie convention and value
+ * loss exactly as trl_ppo_generic_losses_f32 (shared helpers);
+ *   d_logits_j = g_lp (1[j = a] - p_j) + (entropy_coeff / n_global) p_j (log p_j + H).
+ * info: the same 24 slots; 8..11 and 16..19 (log_std / std statistics) are zero and slot 20 holds the entropy SUM over the
+ * local samples.  workspace: trl_cat_losses_workspace(B, A) doubles. */
+int trl_cat_losses_workspace(int B, int A);
+int trl_cat_losses_f32(const float* logits, const float* acts, const float* advs, const float* old_logp, const float* v,
+                       const float* rets, const float* v_old, const double* adv_raw, double n_global, int B, int A,
+                       float clip_para, float entropy_coeff, int clipped_value_loss, int loss_mode, float* d_logits,
+                       float* d_v, double* info, double* workspace, void* stream);
 
 /* --- V-MPO: the loss half of VMPO.update (torchrl/algo/on_policy/v_mpo.py:57-181) ----------------------
  * trl_adv_normalize_f32: out = (adv - mean) / (std_unbiased + eps) from trl_adv_stats_f64's {sum, sumsq, ..} (:175-177;
@@ -685,6 +696,10 @@ int trl_synth_collect_step_f32(float* cur_obs, const float* head, const float* e
                                int ep_cap, int step, int N, int D, int A, int tanh_action, void* stream);
 /* N(0,1) fill from the Philox4x32-10 stream (device exploration / rsample noise) */
 int trl_philox_normal_f32(float* out, int64_t n, int64_t seed, int64_t counter, void* stream);
+/* U(0,1) fill from the Philox4x32-10 stream of the categorical action draw (trl_cat_act_f32): out (T, N),
+ * out[t][n] = the uniform of (seed, counter0 + t, global env index env_offset + n) -- element g & 3 of Philox block g >> 2,
+ * counter words (lo32(counter), hi32(counter)), its own stream tag, mapped by (x >> 8) * 2^-24 + 2^-25. */
+int trl_philox_uniform_f32(float* out, int T, int N, int64_t seed, int64_t counter0, int64_t env_offset, void* stream);
 /* K1 stand-alone: one VecEnv.step of the synthetic env (torchrl/env/vecenv.py:53-61); cur_obs is
  * advanced in place and copied to next_obs; rewards / dones are (N) floats */
 int trl_synth_env_step_f32(float* cur_obs, const float* act, const float* env_A, const float* env_B,
@@ -878,6 +893,20 @@ int trl_frame_stream_gather_u8(const uint8_t* stream, const int32_t* pos, const 
  *                      (torchrl/collector/base.py:220-224), straight from the reset mask */
 int trl_gauss_explore_f32(const float* mean, const float* logstd, const float* eps, float* act, float* logp,
                           int N, int A, int tanh_action, void* stream);
+/* The categorical counterpart of trl_gauss_explore_f32 (CategoricalDisPolicy.explore, discrete_policies.py:136-150):
+ * logits (N, A), 2 <= A <= 64 -> act (N, 1) holding the integer action as a float, logp (N, nullable) = log pi(a),
+ * onehot (N, A, nullable).  m = max_k l_k, e_k = exp(l_k - m), S = sum e_k and the prefix sums in ascending k (fp32); the
+ * action is the smallest k whose prefix sum is >= u * S, else A - 1; log pi = (l_a - m) - log S.  u (N, nullable): the
+ * caller's draws; NULL: trl_philox_uniform_f32's value for (seed, counter, env_offset + n), drawn in place -- a function
+ * of the GLOBAL env index, so env shards on several ranks reproduce the single-process draw.  deterministic: arg-max,
+ * lowest index on ties (eval_act, :152-154). */
+int trl_cat_act_f32(const float* logits, const float* u, int64_t seed, int64_t counter, int64_t env_offset,
+                    int deterministic, float* act, float* logp, float* onehot, int N, int A, void* stream);
+/* log pi(a) (B), the entropy (B) and the probabilities p = softmax(logits) (B, A) of (logits (B, A), acts (B)) pairs --
+ * every output nullable, acts only needed for logp: CategoricalDisPolicy.forward / .update (discrete_policies.py:132-134,
+ * 156-168) with trl_cat_act_f32's arithmetic, so log pi and log pi_old of the same (s, a, parameters) are bit-identical. */
+int trl_cat_logp_f32(const float* logits, const float* acts, float* logp, float* ent, float* probs, int B, int A,
+                     void* stream);
 int trl_onpolicy_bookkeep_f32(float* rewards, const float* dones, const float* v_next, float discount,
                               float* terminals, int32_t* cur_step, float* ep_return, int max_episode_frames,
                               uint8_t* reset_mask, int32_t* any_flag, double* epoch_reward, int32_t* ep_count,

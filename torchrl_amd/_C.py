@@ -275,6 +275,13 @@ SIGNATURES = {
     "trl_ppo_generic_losses_workspace": (C.c_int, [C.c_int] * 2),
     "trl_ppo_generic_losses_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_float,
                                                                  C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "trl_cat_losses_workspace": (C.c_int, [C.c_int] * 2),
+    "trl_cat_losses_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
+                           + [C.c_void_p] * 5),
+    "trl_cat_act_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "trl_cat_logp_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
+    "trl_philox_uniform_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "trl_linear_fwd_workspace": (C.c_int, [C.c_int] * 3),
     "trl_linear_fwd_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
     "trl_linear_bwd_input_group_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -676,6 +683,81 @@ def ppo_generic_losses(mean, logstd, acts, advs, old_logp, v, rets, v_old, adv_r
         dev_ptr(info, torch.float64, "info"), dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(mean.device)),
         "trl_ppo_generic_losses_f32")
     return d_mean, d_v
+
+
+def cat_losses(logits, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, clip_para, entropy_coeff,
+               clipped_value_loss, loss_mode, info, workspace=None):
+    """The loss half of a PPO / A2C minibatch for a categorical head; returns (d_logits (B, A), d_v (B, 1))."""
+    B, A = int(logits.shape[0]), int(logits.shape[1])
+    need = lib().trl_cat_losses_workspace(B, A)
+    if need < 0:
+        raise TrlError("cat_losses: unsupported sizes B=%d A=%d (2 <= A <= 64)" % (B, A))
+    if int(acts.numel()) != B:
+        raise TrlError("cat_losses: acts must hold one action index per sample, got %s for B=%d" % (tuple(acts.shape), B))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.float64, device=logits.device)
+    d_logits = torch.empty((B, A), dtype=torch.float32, device=logits.device)
+    d_v = torch.empty((B, 1), dtype=torch.float32, device=logits.device)
+    check(lib().trl_cat_losses_f32(
+        dev_ptr(logits, name="logits"), dev_ptr(acts, name="acts"), dev_ptr(advs, name="advs"),
+        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v"), dev_ptr(rets, name="rets"),
+        dev_ptr(v_old, name="v_old", allow_none=True), dev_ptr(adv_raw, torch.float64, "adv_raw"), float(n_global), B, A,
+        float(clip_para), float(entropy_coeff), int(bool(clipped_value_loss)), int(loss_mode),
+        dev_ptr(d_logits, name="d_logits"), dev_ptr(d_v, name="d_v"), dev_ptr(info, torch.float64, "info"),
+        dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(logits.device)), "trl_cat_losses_f32")
+    return d_logits, d_v
+
+
+def cat_act(logits, seed=0, counter=0, env_offset=0, u=None, deterministic=False, act=None, logp=None, onehot=None):
+    """One vector step's action half for a categorical policy: (act (N, 1) float, logp (N,)); `onehot` (N, A) is filled
+    when given.  u None: the Philox uniform of (seed, counter, env_offset + n) is drawn in the launch."""
+    N, A = int(logits.shape[0]), int(logits.shape[1])
+    if act is None:
+        act = torch.empty((N, 1), dtype=torch.float32, device=logits.device)
+    if logp is None:
+        logp = torch.empty((N,), dtype=torch.float32, device=logits.device)
+    if int(act.numel()) != N or int(logp.numel()) != N or (u is not None and int(u.numel()) != N) \
+            or (onehot is not None and tuple(onehot.shape) != (N, A)):
+        raise TrlError("cat_act: act / logp / u hold one value per row and onehot is (N, A) for logits %s" % ((N, A),))
+    check(lib().trl_cat_act_f32(dev_ptr(logits, name="logits"), dev_ptr(u, name="u", allow_none=True), int(seed),
+                                int(counter), int(env_offset), int(bool(deterministic)), dev_ptr(act, name="act"),
+                                dev_ptr(logp, name="logp"), dev_ptr(onehot, name="onehot", allow_none=True), N, A,
+                                stream_ptr(logits.device)), "trl_cat_act_f32")
+    return act, logp
+
+
+def cat_logp(logits, acts, out=None, ent=None, want_ent=False):
+    """(log pi(a) (B,), entropy (B,) or None) of stored (logits, action index) pairs."""
+    B, A = int(logits.shape[0]), int(logits.shape[1])
+    if int(acts.numel()) != B:
+        raise TrlError("cat_logp: acts must hold one action index per sample, got %s for B=%d" % (tuple(acts.shape), B))
+    if out is None:
+        out = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    if ent is None and want_ent:
+        ent = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    if int(out.numel()) != B or (ent is not None and int(ent.numel()) != B):
+        raise TrlError("cat_logp: outputs hold one value per sample")
+    check(lib().trl_cat_logp_f32(dev_ptr(logits, name="logits"), dev_ptr(acts, name="acts"), dev_ptr(out, name="out"),
+                                 dev_ptr(ent, name="ent", allow_none=True), None, B, A, stream_ptr(logits.device)),
+          "trl_cat_logp_f32")
+    return out, ent
+
+
+def cat_probs(logits):
+    """softmax(logits) (B, A) with the categorical kernels' arithmetic."""
+    B, A = int(logits.shape[0]), int(logits.shape[1])
+    probs = torch.empty((B, A), dtype=torch.float32, device=logits.device)
+    check(lib().trl_cat_logp_f32(dev_ptr(logits, name="logits"), None, None, None, dev_ptr(probs, name="probs"), B, A,
+                                 stream_ptr(logits.device)), "trl_cat_logp_f32")
+    return probs
+
+
+def philox_uniform(out, seed, counter0, env_offset=0):
+    """out (T, N): the uniforms `cat_act` draws for steps counter0 .. counter0 + T - 1 and envs env_offset .. + N - 1."""
+    T, N = int(out.shape[0]), int(out.shape[1])
+    check(lib().trl_philox_uniform_f32(dev_ptr(out, name="out"), T, N, int(seed), int(counter0), int(env_offset),
+                                       stream_ptr(out.device)), "trl_philox_uniform_f32")
+    return out
 
 
 def adv_normalize(advs, adv_raw, n_global, eps=1e-5):

@@ -1,5 +1,6 @@
 """Names the reference's example scripts import (the old single-env scripts) whose algorithms have no
-kernel path in this build.  Importing works; constructing one fails loudly instead of silently
+kernel path in this build (the categorical policy of the discrete on-policy examples is NOT among
+them any more: policies.CategoricalDisPolicy runs PPO / A2C on k_categorical.hip).  Importing works; constructing one fails loudly instead of silently
 running somewhere else -- there is no CPU / autograd fallback in this package."""
 from ... import _C
 

@@ -63,6 +63,11 @@ class PPO(A2C):
         buf = self.replay_buffer
         rows, n = buf._max_replay_buffer_size, buf.env_nums
         tgt = self.target_pf
+        if getattr(tgt, "continuous", True) is False:                  # categorical head: MLP forward + trl_cat_logp_f32
+            with torch.no_grad():
+                _C.cat_logp(tgt.logits(buf._obs.reshape(rows * n, -1)).contiguous(), buf._acts.reshape(rows * n),
+                            out=buf._ensure_key("old_logp", (n, 1)).view(rows * n))
+            return
         with torch.no_grad():                                          # kernels only: MLP forward + trl_gauss_logp_f32
             mean, _, log_std = tgt.forward(buf._obs.reshape(rows * n, -1))
             _C.gauss_logp(mean.contiguous(), buf._acts.reshape(rows * n, -1), log_std.float().contiguous(),
@@ -656,6 +661,14 @@ class _FusedPPO:
         A = self.A
         for r, i, g in zip(raw, info, norms):
             v_var = max((i[13] - i[12] * i[12] / n) / (n - 1), 0.0)
+            if getattr(self, "categorical", False):                     # no `std` in the policy's dict: a2c.py:62-63, 96-101
+                ent = i[20] / n
+                out.append({
+                    'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
+                    'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15],
+                    'ent': ent, 'log_prob': i[1] / n,
+                })
+                continue
             ent = A * _HALF_LOG_2PI_PLUS_HALF + A * i[8]
             std_ss = (i[17] ** 2) * (A - 1) if A > 1 else 0.0            # sum over dims of (std - mean)^2
             out.append({
@@ -672,7 +685,8 @@ class _FusedPPO:
         r, i = raw, info
         adv_var = np.maximum((r[:, 1] - r[:, 0] * r[:, 0] / n) / (n - 1), 0.0)
         lp_var = np.maximum((i[:, 2] - i[:, 1] * i[:, 1] / n) / (n - 1), 0.0)
-        ent = self.A * _HALF_LOG_2PI_PLUS_HALF + self.A * i[:, 8]
+        categorical = getattr(self, "categorical", False)              # entropy: the kernel's sum; no log_std/* keys
+        ent = i[:, 20] / n if categorical else self.A * _HALF_LOG_2PI_PLUS_HALF + self.A * i[:, 8]
         cols = (('advs/mean', r[:, 0] / n), ('advs/std', np.sqrt(adv_var)), ('advs/max', r[:, 2]), ('advs/min', -r[:, 3]),
                 ('Training/vf_loss', i[:, 7] / n), ('grad_norm/vf', norms[:, 1].astype(np.float64)),
                 ('Training/policy_loss', i[:, 0] / n - c_ent * ent),
@@ -680,6 +694,8 @@ class _FusedPPO:
                 ('logprob/min', -i[:, 4]), ('log_std/mean', i[:, 8]), ('log_std/std', i[:, 9]), ('log_std/max', i[:, 10]),
                 ('log_std/min', i[:, 11]), ('ratio/max', i[:, 5]), ('ratio/min', -i[:, 6]),
                 ('grad_norm/pf', norms[:, 0].astype(np.float64)))
+        if categorical:
+            cols = tuple(c for c in cols if not c[0].startswith('log_std/'))
         keys = [k for k, _ in cols]
         table = np.stack([v for _, v in cols], axis=1).tolist()
         return [dict(zip(keys, row)) for row in table]
@@ -714,6 +730,8 @@ def make_engine(algo):
     pf, vf = algo.pf, algo.vf
     ps = pf.mlp2_spec() if hasattr(pf, "mlp2_spec") else None
     vs = vf.mlp2_spec() if hasattr(vf, "mlp2_spec") else None
+    if getattr(pf, "continuous", True) is False:                        # categorical head: never the fused 64-wide kernels
+        return _GenericPPO(algo)
     if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
             and os.environ.get("TRL_GENERIC_PPO") != "1":
         return _FusedPPO(algo)
@@ -735,8 +753,11 @@ class _GenericPPO(_FusedPPO):
         from ... import ops
         self.algo, self.ops = algo, ops
         pf, vf = algo.pf, algo.vf
-        if not hasattr(pf, "logstd"):
-            raise _C.TrlError("PPO / A2C kernels need a state-independent-std policy (GuassianContPolicyBasicBias)")
+        # a categorical head (policies.CategoricalDisPolicy): no logstd in the flat vector, trl_cat_losses_f32 for the loss half
+        self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
+        if not self.categorical and not hasattr(pf, "logstd"):
+            raise _C.TrlError("PPO / A2C kernels need a state-independent-std policy (GuassianContPolicyBasicBias) or a "
+                              "CategoricalDisPolicy")
         self.dev = next(pf.parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
@@ -744,11 +765,12 @@ class _GenericPPO(_FusedPPO):
         if ops.act_code(vf) != self.act:
             raise _C.TrlError("policy and value network must use the same activation")
         self.pf_layers, self.vf_layers = ops.linear_layers(pf), ops.linear_layers(vf)
-        pf_list = [t for wb in self.pf_layers for t in wb] + [pf.logstd]
+        tail = (lambda net: []) if self.categorical else (lambda net: [net.logstd])
+        pf_list = [t for wb in self.pf_layers for t in wb] + tail(pf)
         vf_list = [t for wb in self.vf_layers for t in wb]
         self.P_pf = sum(p.numel() for p in pf_list)
         self.P_vf = sum(p.numel() for p in vf_list)
-        self.D, self.A = int(self.pf_layers[0][0].shape[1]), int(pf.logstd.numel())
+        self.D, self.A = int(self.pf_layers[0][0].shape[1]), int(self.pf_layers[-1][0].shape[0])
         self.flat = flatten_into(pf_list + vf_list)                   # [pf | vf], parameters become views
         # nets that are MLP2 blocks hand their own flat view to the fused inference kernel (Net.flat_params): it must
         # be THIS storage, or the first forward after the engine exists would re-home the parameters away from it
@@ -760,7 +782,9 @@ class _GenericPPO(_FusedPPO):
         tgt = getattr(algo, "target_pf", None)
         self.target_flat = None
         if tgt is not None:
-            self.target_flat = flatten_into([t for wb in ops.linear_layers(tgt) for t in wb] + [tgt.logstd])
+            self.target_flat = flatten_into([t for wb in ops.linear_layers(tgt) for t in wb] + tail(tgt))
+            if getattr(tgt, "mlp2_spec", lambda: None)() is not None:  # (same storage for its fused forward, as for pf / vf)
+                tgt._flat = self.target_flat
         self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
         self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
         self.gviews, off = [], 0
@@ -771,7 +795,7 @@ class _GenericPPO(_FusedPPO):
                 gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
                 views.append((gw, gb))
             self.gviews.append(views)
-            if layers is self.pf_layers:
+            if layers is self.pf_layers and not self.categorical:
                 self.g_logstd = self.grads[off:off + self.A]; off += self.A
         self.step_state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
         self.lr_dev = torch.zeros(2, device=self.dev)
@@ -820,10 +844,16 @@ class _GenericPPO(_FusedPPO):
                 v_old, old_lp = gather("old_values", k), gather("old_logp", k)
                 mean, tape_pf = ops.mlp_forward(self.pf_layers, obs, self.act)
                 v, tape_vf = ops.mlp_forward(self.vf_layers, obs, self.act)
-                d_mean, d_v = _C.ppo_generic_losses(
-                    mean, algo.pf.logstd.detach(), acts, advs.view(-1), None if old_lp is None else old_lp.view(-1),
-                    v.view(-1), rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, *hyper,
-                    self.g_logstd, info[k])
+                if self.categorical:                                   # `mean` holds the logits, acts (n_local, 1) the indices
+                    d_mean, d_v = _C.cat_losses(
+                        mean, acts.view(-1), advs.view(-1), None if old_lp is None else old_lp.view(-1), v.view(-1),
+                        rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, hyper[0], hyper[1],
+                        hyper[2], loss_mode, info[k])
+                else:
+                    d_mean, d_v = _C.ppo_generic_losses(
+                        mean, algo.pf.logstd.detach(), acts, advs.view(-1), None if old_lp is None else old_lp.view(-1),
+                        v.view(-1), rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, *hyper,
+                        self.g_logstd, info[k])
                 ops.mlp_backward(tape_pf, d_mean, grads=self.gviews[0], workspace=ws)
                 ops.mlp_backward(tape_vf, d_v, grads=self.gviews[1], workspace=ws)
                 dist.all_reduce_sum_(self.grads)                       # C1: gradient SUM over ranks
@@ -855,7 +885,13 @@ class _GenericPPO(_FusedPPO):
         self.step_count += K
         for s in self._opt_steps:
             s.fill_(float(self.step_count))
+        ent_sum = None
+        if self.categorical and dist.collectives_active():             # slot 20 (entropy SUM) is not among the columns
+            ent_sum = info[:, 20].contiguous()                         # reduce_info_ sums: its own all-reduce, put back below
+            dist.all_reduce_sum_(ent_sum)
         dist.reduce_info_(info)
+        if ent_sum is not None:
+            info[:, 20] = ent_sum
         host = stats.cpu()                                             # the only host sync of the update
         make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
         return make(host[:4 * K].view(K, 4).numpy(), host[4 * K:28 * K].view(K, 24).numpy(),

@@ -25,6 +25,9 @@ from .ppo import _GenericPPO
 
 class TRPO(A2C):
     def __init__(self, max_kl, cg_damping, v_opt_times, cg_iters, residual_tol, **kwargs):
+        if getattr(kwargs.get("pf"), "continuous", True) is False:
+            raise _C.TrlError("TRPO with a categorical policy is not built: its Fisher-vector product and line search are "
+                              "kernels for the diagonal-Gaussian head; discrete actions run on PPO / A2C")
         super().__init__(**kwargs)
         self.max_kl, self.cg_damping, self.cg_iters, self.residual_tol = max_kl, cg_damping, cg_iters, residual_tol
         self.v_opt_times = v_opt_times

@@ -22,6 +22,9 @@ from .ppo import _GenericPPO
 
 class VMPO(A2C):
     def __init__(self, pf, opt_epochs=10, eta_eps=0.02, alpha_eps=0.1, clipped_value_loss=False, **kwargs):
+        if getattr(pf, "continuous", True) is False:
+            raise _C.TrlError("VMPO with a categorical policy is not built: its KL terms are kernels for the "
+                              "diagonal-Gaussian head; discrete actions run on PPO / A2C")
         self.target_pf = copy.deepcopy(pf)
         super().__init__(pf=pf, **kwargs)
         self.eta_eps, self.alpha_eps = eta_eps, alpha_eps

@@ -290,13 +290,24 @@ class VecOnPolicyCollector(VecCollector):
         otherwise -- any other MLP shape is collected by the per-step launch sequence on the generic dense-layer
         kernels."""
         from .. import ops
-        if not hasattr(self.pf, "logstd"):
-            raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias policies")
+        # a categorical policy (policies.CategoricalDisPolicy) over Discrete(A): the per-step route with trl_cat_act_f32 in
+        # place of trl_gauss_explore_f32; `_dims[1]` = A is the head's width, the ring's `acts` are (N, 1) indices
+        self._cat = getattr(self.pf, "continuous", True) is False and hasattr(self.pf, "logits")
+        if not self._cat and not hasattr(self.pf, "logstd"):
+            raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias and CategoricalDisPolicy policies")
+        if self._cat and self.noise_mode != "device":
+            raise _C.TrlError("a categorical policy draws its actions from the device Philox stream only "
+                              "(noise_mode=\"device\"): the reference samples through torch.multinomial, whose host stream "
+                              "is not reproduced -- noise_mode=%r is not built" % (self.noise_mode,))
         ps = self.pf.mlp2_spec() if hasattr(self.pf, "mlp2_spec") else None
         vs = self.vf.mlp2_spec() if hasattr(self.vf, "mlp2_spec") else None
         self._act = ops.act_code(self.pf)
-        self._dims = (int(ops.linear_layers(self.pf)[0][0].shape[1]), int(self.pf.logstd.numel()))
-        if self._dims != (self.env.obs_dim, self.env.act_dim) or int(ops.linear_layers(self.vf)[0][0].shape[1]) != self.env.obs_dim:
+        layers = ops.linear_layers(self.pf)
+        self._dims = (int(layers[0][0].shape[1]), int(layers[-1][0].shape[0]) if self._cat else int(self.pf.logstd.numel()))
+        env_acts = int(getattr(self.env, "action_num", 0) or 0) if self._cat else self.env.act_dim
+        if self._cat and not env_acts:
+            raise _C.TrlError("a categorical policy needs an env with a Discrete action space")
+        if self._dims != (self.env.obs_dim, env_acts) or int(ops.linear_layers(self.vf)[0][0].shape[1]) != self.env.obs_dim:
             raise _C.TrlError("policy / value input and output sizes %s do not match the env (%d obs, %d act)"
                               % (self._dims, self.env.obs_dim, self.env.act_dim))
         # the fused 2-layer forward (and the cooperative, normalised rollout) are instantiated for the benchmark shape
@@ -314,6 +325,8 @@ class VecOnPolicyCollector(VecCollector):
         roll = pair and bool(lib.trl_rollout_supported(ps[0], ps[1], ps[2], ps[3])) and \
             (bool(mlp2) or os.environ.get("TRL_NO_RT_ROLLOUT") != "1")
         self._spec = ps if (roll and not getattr(self.env, "is_host_env", False)) else None   # ... and the rollout kernel
+        if self._cat:                                                       # (the persistent rollout samples Gaussians)
+            self._spec = None
 
     def _forward(self, net, x, out_dim, out=None):
         """mean / value of an MLP on the device: the fused 2-layer kernel when instantiated, the dense-layer family
@@ -487,10 +500,11 @@ class VecOnPolicyCollector(VecCollector):
             D, A = self._dims
             N, dev = env.env_nums, env.device
             f = lambda *shape: torch.empty(*shape, device=dev)
+            W = 1 if self._cat else A                                       # stored action width
             sb = self._sb = {"N": N, "mean": f(N, A), "eps": f(N, A), "nxt_raw": f(N, D), "v_next": f(N, 1),
                              "done": f(N, 1), "any": torch.zeros(1, dtype=torch.int32, device=dev),
                              # rows used when nothing is stored (evaluation)
-                             "obs": f(N, D), "next_obs": f(N, D), "acts": f(N, A), "values": f(N, 1), "rewards": f(N, 1),
+                             "obs": f(N, D), "next_obs": f(N, D), "acts": f(N, W), "values": f(N, 1), "rewards": f(N, 1),
                              "terminals": f(N, 1), "time_limits": f(N, 1), "old_logp": f(N, 1)}
         return sb
 
@@ -504,14 +518,24 @@ class VecOnPolicyCollector(VecCollector):
         nz = getattr(env, "_obs_normalizer", None)
         if store:
             row = buf._top
-            feats = (("obs", D), ("next_obs", D), ("acts", A), ("values", 1), ("rewards", 1), ("terminals", 1),
-                     ("time_limits", 1), ("old_logp", 1))
+            feats = (("obs", D), ("next_obs", D), ("acts", 1 if self._cat else A), ("values", 1), ("rewards", 1),
+                     ("terminals", 1), ("time_limits", 1), ("old_logp", 1))
             r = {k: buf._ensure_key(k, (N, w))[row] for k, w in feats}
         else:
             r = sb
         r["obs"].copy_(ob)
         mean = self._forward(self.pf, ob, A, out=sb["mean"])
         self._forward(self.vf, ob, 1, out=r["values"])
+        if self._cat:
+            # `mean` holds the logits.  noise_t: this step's (N,) uniforms drawn up front (captured rollout); None: the
+            # launch draws the uniform of (seed, global step, global env index) itself -- the same values.  Host envs get
+            # the (N, 1) indices, the synthetic env the one-hot rows (sb["eps"]) its step kernel takes.
+            host = getattr(env, "is_host_env", False)
+            _C.cat_act(mean, seed=self._noise_seed, counter=self.global_step, env_offset=self._noise_layout(env)[1],
+                       u=noise_t, deterministic=deterministic, act=r["acts"], logp=r["old_logp"].view(N),
+                       onehot=None if host else sb["eps"])
+            env_act = r["acts"] if host else sb["eps"]
+            return self._step_tail(env, r, sb, nz, env_act, store, step, max_frames)
         if deterministic:
             eps = None
         elif noise_t is not None:
@@ -523,8 +547,13 @@ class VecOnPolicyCollector(VecCollector):
             eps = dist.shard_rows_of_global(make, 1, N, A, env.device)
         _C.gauss_explore(mean, self.pf.logstd.detach(), eps, bool(self.pf.tanh_action), act=r["acts"],
                          logp=r["old_logp"].view(N))
+        return self._step_tail(env, r, sb, nz, r["acts"], store, step, max_frames)
+
+    def _step_tail(self, env, r, sb, nz, env_act, store, step, max_frames):
+        """What follows the action half of `_step_launches`: env step, bookkeeping, masked reset, next policy input."""
+        D, N, buf = self._dims[0], env.env_nums, self.replay_buffer
         raw_next = sb["nxt_raw"] if nz is not None else r["next_obs"]
-        self._env_advance(env, r["acts"], raw_next, r["rewards"], sb["done"], r["time_limits"])
+        self._env_advance(env, env_act, raw_next, r["rewards"], sb["done"], r["time_limits"])
         if nz is not None:
             nz.update_filt(raw_next, update=env.training, out=r["next_obs"])            # NormObs.observation
         self._forward(self.vf, r["next_obs"], 1, out=sb["v_next"])
@@ -571,10 +600,13 @@ class VecOnPolicyCollector(VecCollector):
             if st is None or st["key"] != (n_steps, env.env_nums):
                 st = self._roll_graph = {"key": (n_steps, env.env_nums), "graph": None, "seen": False, "hdr": self._hdr_i,
                                          "ob0": torch.empty(env.env_nums, D, device=env.device),
-                                         "noise": torch.empty(n_steps, env.env_nums, A, device=env.device), "out": None}
+                                         "noise": torch.empty((n_steps, env.env_nums) + (() if self._cat else (A,)),
+                                                              device=env.device), "out": None}
             self._clear_header(index=st["hdr"])                           # (a captured sequence carries its header's address)
             st["ob0"].copy_(ob)
-            if dist.world_size() == 1:
+            if self._cat:                                                 # the rollout's (T, N) uniforms, one launch
+                _C.philox_uniform(st["noise"], self._noise_seed, self.global_step, self._noise_layout(env)[1])
+            elif dist.world_size() == 1:
                 _C.philox_normal(st["noise"], self._noise_seed, self.global_step)
             else:                                                         # (T, N_total, A) drawn identically on every rank
                 make = lambda m, f: _C.philox_normal(torch.empty(m, f, device=env.device), self._noise_seed, self.global_step)

@@ -12,10 +12,7 @@
 // Two passes: every block writes partial sums, one block folds them in fixed order (deterministic).
 #include "trl_common.h"
 #include "trl_mlp.h"
-
-#define PG_THREADS 256
-#define PG_MAX_A 64
-#define PG_SCAL 12          // lp sum, lp^2, max lp, -min lp, max ratio, -min ratio, surrogate sum | vloss, v sum, v^2, max v, -min v
+#include "trl_ppo_loss.h"
 
 struct PpoGenDev {
   const float* mean; const float* logstd; const float* acts; const float* advs; const float* old_logp;
@@ -28,30 +25,14 @@ struct PpoGenDev {
   double n_global;
 };
 
-__device__ __forceinline__ double pg_block_reduce(double v, bool is_max, double* smem) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) smem[wave] = v;
-  __syncthreads();
-  double r = is_max ? -INFINITY : 0.0;
-  for (int w = 0; w < PG_THREADS / 64; ++w) r = is_max ? fmax(r, smem[w]) : r + smem[w];
-  return r;
-}
-
 __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDev a) {
   __shared__ double smem[PG_THREADS / 64];
   __shared__ float s_dls[PG_THREADS / 64][PG_MAX_A];
   const int b = blockIdx.x * PG_THREADS + threadIdx.x;
   const bool valid = b < a.B;
   const int A = a.A;
-  // advantage normalisation constants (ppo.py:141-147): mean, unbiased std
-  const double ng = a.n_global;
-  const double adv_mean = a.adv_raw[0] / ng;
-  const double adv_var = (a.adv_raw[1] - a.adv_raw[0] * a.adv_raw[0] / ng) / (ng - 1.0);
-  const float adv_mu = (float)adv_mean;
-  const float adv_rstd = 1.0f / ((float)sqrt(fmax(adv_var, 0.0)) + 1e-5f);
-  const float inv_b = (float)(1.0 / ng);
+  const PgAdvNorm nrm = pg_adv_norm(a.adv_raw, a.n_global);
+  const float adv_mu = nrm.mu, adv_rstd = nrm.rstd, inv_b = nrm.inv_b;
 
   // ---- policy: log pi, surrogate, d/d(mean), d/d(logstd) ----
   float lp = 0.0f;
@@ -63,16 +44,7 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDe
     }
   const float advn = valid ? (a.advs[b] - adv_mu) * adv_rstd : 0.0f;
   float ratio, s1, s2, g_lp;
-  if (a.loss_mode == TRL_LOSS_A2C) {                              // L = -mean(log pi * adv) (a2c.py:69-70)
-    ratio = 1.0f;
-    s1 = s2 = lp * advn;
-    g_lp = valid ? -advn * inv_b : 0.0f;
-  } else {                                                       // clipped surrogate (ppo.py:58-66)
-    ratio = valid ? __expf(lp - a.old_logp[b]) : 1.0f;
-    s1 = ratio * advn;
-    s2 = fminf(fmaxf(ratio, 1.0f - a.clip_para), 1.0f + a.clip_para) * advn;
-    g_lp = (valid && s1 <= s2) ? -advn * ratio * inv_b : 0.0f;
-  }
+  pg_surrogate(valid, lp, a.old_logp, b, advn, a.loss_mode, a.clip_para, inv_b, ratio, s1, s2, g_lp);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 0; o < A; ++o) {
     float dls = 0.0f;
@@ -95,19 +67,7 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDe
     vv = a.v[b];
     const float R = a.rets[b];
     float dv;
-    if (a.clipped_value_loss) {                                  // ppo.py:104-111
-      const float vo = a.v_old[b];
-      const float dc = vv - vo;
-      const float vc = vo + fminf(fmaxf(dc, -a.clip_para), a.clip_para);
-      const float l1 = (vv - R) * (vv - R), l2 = (vc - R) * (vc - R);
-      const float wa = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f), wb = 1.0f - wa;
-      const float pass = (dc >= -a.clip_para && dc <= a.clip_para) ? 1.0f : 0.0f;
-      l = 0.5f * fmaxf(l1, l2);
-      dv = inv_b * (wa * (vv - R) + wb * pass * (vc - R));
-    } else {                                                     // nn.MSELoss, a2c.py:43
-      l = (vv - R) * (vv - R);
-      dv = 2.0f * (vv - R) * inv_b;
-    }
+    pg_value_loss(vv, R, a.v_old, b, a.clip_para, a.clipped_value_loss, inv_b, l, dv);
     a.d_v[b] = dv;
   }
   // ---- block partials ----
@@ -118,20 +78,11 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDe
     for (int w = 0; w < PG_THREADS / 64; ++w) s += s_dls[w][threadIdx.x];
     out[threadIdx.x] = (double)s;
   }
-  const double ninf = -INFINITY;
-  const double vals[PG_SCAL] = {valid ? (double)lp : 0.0, valid ? (double)lp * lp : 0.0, valid ? (double)lp : ninf,
-                                valid ? -(double)lp : ninf, valid ? (double)ratio : ninf, valid ? -(double)ratio : ninf,
-                                valid ? -(double)fminf(s1, s2) : 0.0, (double)l, (double)vv, (double)vv * vv,
-                                valid ? (double)vv : ninf, valid ? -(double)vv : ninf};
-  const bool is_max[PG_SCAL] = {false, false, true, true, true, true, false, false, false, false, true, true};
-#pragma unroll
-  for (int k = 0; k < PG_SCAL; ++k) {
-    const double r = pg_block_reduce(vals[k], is_max[k], smem);
-    if (threadIdx.x == 0) out[A + k] = r;
-  }
+  pg_write_scalars(out + A, valid, lp, ratio, s1, s2, l, vv, smem);
 }
 
-// one block: fold the block partials in order; d_logstd (A) and the info row (trl_ppo_reduce_f32's layout)
+// one block: fold the block partials in order; d_logstd (A) and the info row (trl_ppo_reduce_f32's layout).
+// logstd NULL: a categorical head's fold (trl_ppo_loss.h::pg_launch_fold) -- A == 1 leading sum, the entropy
 __global__ __launch_bounds__(PG_THREADS) void ppo_generic_fold_kernel(const double* __restrict__ partial, int blocks, int A,
                                                                     const float* __restrict__ logstd,
                                                                     float* __restrict__ d_logstd, double* __restrict__ info) {
@@ -146,13 +97,18 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_fold_kernel(const doub
       r = is_max ? fmax(r, o) : r + o;
     }
     s_out[e] = r;
-    if (e < A) d_logstd[e] = (float)r;
+    if (e < A && d_logstd) d_logstd[e] = (float)r;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     const double* s = s_out + A;
     info[0] = s[6]; info[1] = s[0]; info[2] = s[1]; info[3] = s[2]; info[4] = s[3]; info[5] = s[4]; info[6] = s[5];
     info[7] = s[7]; info[12] = s[8]; info[13] = s[9]; info[14] = s[10]; info[15] = s[11];
+    if (!logstd) {                                               // no log_std / std statistics; 20: entropy sum
+      for (int o = 8; o < 12; ++o) info[o] = info[o + 8] = 0.0;
+      info[20] = s_out[0];
+      return;
+    }
     double sm = 0, sq = 0, mx = -INFINITY, mn = INFINITY, es = 0, eq = 0, emx = -INFINITY, emn = INFINITY;
     for (int o = 0; o < A; ++o) {                                // ppo.py:82-85 log_std/*, a2c.py:95-100 std/*
       const double x = fmin(fmax((double)logstd[o], -20.0), 2.0), ex = exp(x);
@@ -163,6 +119,14 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_fold_kernel(const doub
     info[8] = mean; info[9] = A > 1 ? sqrt(fmax((sq - sm * mean) / (A - 1), 0.0)) : NAN; info[10] = mx; info[11] = mn;
     info[16] = em; info[17] = A > 1 ? sqrt(fmax((eq - es * em) / (A - 1), 0.0)) : NAN; info[18] = emx; info[19] = emn;
   }
+}
+
+int pg_launch_fold(const double* partial, int blocks, int n_vec, const float* logstd, float* vec_out, double* info,
+                   hipStream_t stream) {
+  hipLaunchKernelGGL(ppo_generic_fold_kernel, dim3(1), dim3(PG_THREADS), 0, stream, partial, blocks, n_vec, logstd, vec_out,
+                     info);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
 }
 
 extern "C" int trl_ppo_generic_losses_workspace(int B, int A) {
@@ -190,8 +154,5 @@ extern "C" int trl_ppo_generic_losses_f32(const float* mean, const float* logstd
   const int blocks = trl_ceil_div(B, PG_THREADS);
   hipLaunchKernelGGL(ppo_generic_losses_kernel, dim3(blocks), dim3(PG_THREADS), 0, (hipStream_t)stream, a);
   TRL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ppo_generic_fold_kernel, dim3(1), dim3(PG_THREADS), 0, (hipStream_t)stream, workspace, blocks, A, logstd,
-                     d_logstd, info);
-  TRL_LAUNCH_CHECK();
-  return TRL_OK;
+  return pg_launch_fold(workspace, blocks, A, logstd, d_logstd, info, (hipStream_t)stream);
 }

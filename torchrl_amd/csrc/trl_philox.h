@@ -7,6 +7,7 @@
 
 #define TRL_TAG_RESET 0x52535421u
 #define TRL_TAG_NOISE 0x4E4F4953u
+#define TRL_TAG_CATEGORICAL 0x43415447u   // one uniform per (seed, step counter, global env index): k_categorical.hip
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t out[4]) {

@@ -15,6 +15,9 @@ HalfCheetah-shaped dynamics (17-d obs, 6-d act):
     reset obs ~ N(0,1), Philox stream keyed (seed*N_total + global_index, episode_idx)
 `index_offset` / `total_env_nums` place a shard of a larger logical vector env
 on this GPU (multi-GPU: envs are sharded by index).
+
+`discrete=True` (`SynthCheetahDiscrete-v0`): `action_space = Discrete(act_dim)`; an action index k is applied as the
+one-hot row e_k of the same dynamics (same step kernel), actions travel as (N, 1).
 """
 import numpy as np
 import torch
@@ -22,7 +25,9 @@ from gym import spaces
 
 from .. import _C
 
-SYNTH_IDS = {"SynthHalfCheetah-v0": dict(obs_dim=17, act_dim=6, horizon=1000)}
+SYNTH_IDS = {"SynthHalfCheetah-v0": dict(obs_dim=17, act_dim=6, horizon=1000),
+             # the same dynamics driven by ONE of act_dim discrete actions: action k applies the one-hot row e_k
+             "SynthCheetahDiscrete-v0": dict(obs_dim=17, act_dim=6, horizon=1000, discrete=True)}
 SYNTH_FRAME_IDS = {"SynthAtari-v0": dict(frame_shape=(4, 84, 84), action_num=6, horizon=1000)}
 
 
@@ -37,16 +42,18 @@ class SynthVecEnv:
     is_device_env = True
 
     def __init__(self, env_nums, obs_dim=17, act_dim=6, horizon=1000, reward_scale=1.0,
-                 device=None, index_offset=0, total_env_nums=None):
+                 device=None, index_offset=0, total_env_nums=None, discrete=False):
         self.env_nums = int(env_nums)
         self.obs_dim, self.act_dim, self.horizon = obs_dim, act_dim, int(horizon)
+        self.discrete = bool(discrete)
+        self.action_num = int(act_dim) if self.discrete else 0
         self._reward_scale = reward_scale
         self.training = True
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.index_offset = int(index_offset)
         self.total_env_nums = int(total_env_nums) if total_env_nums is not None else self.env_nums
         self.observation_space = spaces.Box(-np.inf, np.inf, (obs_dim,))
-        self.action_space = spaces.Box(-1.0, 1.0, (act_dim,))
+        self.action_space = spaces.Discrete(act_dim) if self.discrete else spaces.Box(-1.0, 1.0, (act_dim,))
         a, b = dynamics_matrices(obs_dim, act_dim)
         self.env_A = torch.from_numpy(a).to(self.device)
         self.env_B = torch.from_numpy(b).to(self.device)
@@ -95,7 +102,13 @@ class SynthVecEnv:
         """One vector step as a stand-alone kernel (torchrl/env/vecenv.py:53-61 protocol, device tensors):
         returns (obs (N, D), rewards (N, 1), dones (N, 1) bool, {'time_limit': (N,) bool})."""
         n = self.env_nums
-        acts = torch.as_tensor(actions).to(device=self.device, dtype=torch.float32).reshape(n, self.act_dim).contiguous()
+        if self.discrete:                                               # (N, 1) indices -> the one-hot rows the kernel takes
+            idx = torch.as_tensor(actions).to(device=self.device).reshape(n, 1).to(torch.int64)
+            if int(idx.min()) < 0 or int(idx.max()) >= self.act_dim:
+                raise _C.TrlError("SynthVecEnv.step: action indices must lie in [0, %d)" % self.act_dim)
+            acts = torch.zeros(n, self.act_dim, device=self.device).scatter_(1, idx, 1.0)
+        else:
+            acts = torch.as_tensor(actions).to(device=self.device, dtype=torch.float32).reshape(n, self.act_dim).contiguous()
         nxt = torch.empty(n, self.obs_dim, device=self.device)
         rew = torch.empty(n, 1, device=self.device)
         done = torch.empty(n, 1, device=self.device)

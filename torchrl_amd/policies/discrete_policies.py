@@ -1,4 +1,5 @@
-"""Epsilon-greedy wrappers over a Q network (torchrl/policies/discrete_policies.py:23-89).
+"""Discrete-action policies: epsilon-greedy wrappers over a Q network (torchrl/policies/discrete_policies.py:23-89)
+and the categorical policy of the on-policy algorithms (:124-168, `CategoricalDisPolicy` below).
 
 `explore` keeps the reference's host-side protocol -- linear epsilon decay per call, then
 `np.random.rand(*shape)` and `np.random.randint(0, A, shape)` from the global numpy stream (so
@@ -10,7 +11,7 @@ envs; actions are returned as (N, 1) int64.
 import numpy as np
 import torch
 
-from .. import _C, ops
+from .. import _C, networks, ops
 
 
 class EpsilonGreedyDQNDiscretePolicy:
@@ -95,13 +96,90 @@ class EpsilonGreedyQRDQNDiscretePolicy(EpsilonGreedyDQNDiscretePolicy):
         self.quantile_num = quantile_num
 
 
-class CategoricalDisPolicy:
-    """Imported by the reference's discrete on-policy examples (ppo / a2c _discrete_atari_vec.py).  There is nothing to
-    be faithful to on that path: the reference's PPO.update_actor reads out['log_std'] (ppo.py:52), which this policy's
-    `update` does not return (discrete_policies.py:156-168), and the vector collector stores (N, 1) actions that
-    `Categorical.log_prob` broadcasts against the (B,) batch shape -- the scripts fail at the first update.  No kernel
-    path is built for it; constructing one fails loudly."""
+class CategoricalDisPolicy(networks.Net):
+    """Categorical policy over a discrete action set (torchrl/policies/discrete_policies.py:124-168): an MLP whose head
+    emits A logits.  Same constructor signature and protocol as the reference -- `forward` returns the softmax
+    probabilities, `explore` / `eval_act` / `update` their dicts -- with the reference's initialisation (it is `Net`'s).
+    On the GPU the trunk runs on the dense-layer kernels and everything behind the logits on k_categorical.hip:
+    `trl_cat_act_f32` samples (Philox uniforms, not torch.multinomial's stream), `trl_cat_logp_f32` gives
+    log pi / entropy / probabilities; PPO / A2C read `logits()` and use `trl_cat_losses_f32` (algo/on_policy/ppo.py).
 
-    def __init__(self, *args, **kwargs):
-        raise _C.TrlError("CategoricalDisPolicy is not built in torchrl_amd: on-policy algorithms here take "
-                          "GuassianContPolicyBasicBias (continuous actions); discrete actions are covered by DQN / QRDQN")
+    MLP trunks of any shape; a conv trunk (the reference's Atari-shaped examples) is not built.  The reference's
+    `explore` returns `action` of shape (N,); here it is (N, 1) float holding the integer value, the layout the
+    on-policy ring stores.  `update` takes actions of shape (B,) or (B, 1)."""
+
+    def __init__(self, **kwargs):
+        missing = [k for k in ("output_shape", "base_type") if k not in kwargs]
+        if missing:
+            raise _C.TrlError("a CategoricalDisPolicy without a network (`output_shape`, `base_type`) is not built: "
+                              "missing %s" % ", ".join(missing))
+        base_type = kwargs["base_type"]
+        if not (isinstance(base_type, type) and issubclass(base_type, networks.MLPBase)):
+            raise _C.TrlError("CategoricalDisPolicy over a %s trunk is not built: on-policy algorithms here run MLP trunks "
+                              "(networks.MLPBase) only, CNN trunks are outside the categorical HIP path"
+                              % getattr(base_type, "__name__", base_type))
+        if not 2 <= int(kwargs["output_shape"]) <= 64:
+            raise _C.TrlError("CategoricalDisPolicy: the categorical kernels carry 2..64 actions, got %s"
+                              % (kwargs["output_shape"],))
+        super().__init__(**kwargs)
+        self.continuous = False
+        self._explore_calls = 0
+
+    tanh_action = False                                                # (the engines' launch descriptors ask every policy)
+    explore_seed = 0xCA7
+
+    def logits(self, x):
+        return networks.Net.forward(self, x)
+
+    @staticmethod
+    def _rows(t):
+        return t.reshape(-1, t.shape[-1]).float().contiguous()
+
+    def forward(self, x):
+        l = self.logits(x)
+        if l.is_cuda and not l.requires_grad:
+            return _C.cat_probs(self._rows(l)).reshape(l.shape)
+        if l.is_cuda:
+            _C.note_eager(type(self).__name__ + ".forward", "autograd is on")
+        return torch.softmax(l, dim=-1)
+
+    def explore(self, x, return_log_probs=False):
+        """One draw per row.  On the GPU: trl_cat_act_f32 with the Philox uniform of (explore_seed, number of calls so
+        far, row) -- the collectors do not come through here (they key the draw by their own global step)."""
+        with torch.no_grad():
+            l = self.logits(x)
+        if l.is_cuda:
+            rows = self._rows(l)
+            act, lp = _C.cat_act(rows, seed=self.explore_seed, counter=self._explore_calls)
+            self._explore_calls += 1
+            out = {"dis": _C.cat_probs(rows).reshape(l.shape), "action": act.reshape(l.shape[:-1] + (1,))}
+            if return_log_probs:
+                out["log_prob"] = lp.reshape(l.shape[:-1])
+            return out
+        probs = torch.softmax(l, dim=-1)
+        dis = torch.distributions.Categorical(probs)
+        action = dis.sample()
+        out = {"dis": probs, "action": action.unsqueeze(-1).float()}
+        if return_log_probs:
+            out["log_prob"] = dis.log_prob(action)
+        return out
+
+    def eval_act(self, x):
+        with torch.no_grad():
+            l = self.logits(x)
+        if l.is_cuda:
+            act, _ = _C.cat_act(self._rows(l), deterministic=True)
+            return act.reshape(l.shape[:-1]).to(torch.int64).cpu().numpy()
+        return l.max(dim=-1)[1].cpu().numpy()
+
+    def update(self, obs, actions):
+        l = self.logits(obs)
+        if l.is_cuda and not l.requires_grad:
+            rows = self._rows(l)
+            lp, ent = _C.cat_logp(rows, actions.reshape(-1).float().contiguous(), want_ent=True)
+            return {"dis": _C.cat_probs(rows).reshape(l.shape), "log_prob": lp.reshape(l.shape[:-1] + (1,)),
+                    "ent": ent.reshape(l.shape[:-1])}
+        if l.is_cuda:
+            _C.note_eager(type(self).__name__ + ".update", "autograd is on")
+        dis = torch.distributions.Categorical(torch.softmax(l, dim=-1))
+        return {"dis": dis, "log_prob": dis.log_prob(actions.reshape(l.shape[:-1]).long()).unsqueeze(-1), "ent": dis.entropy()}
