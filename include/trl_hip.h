@@ -202,6 +202,17 @@ int trl_rollout_synth_f32(const trl_rollout_t* args, void* stream);
  * 2..32 inputs and 1..8 actions through the runtime-dims instantiations (17- and 32-feature tiles, missing features
  * and actions masked) -- torchrl/networks/base.py:8-44 and torchrl/collector/on_policy.py:90-155 are shape-generic. */
 int trl_rollout_supported(int D, int H, int A, int act);
+/* The same rollout for a categorical policy (CategoricalDisPolicy, discrete_policies.py:124-168) on the synthetic env with
+ * one-hot actions: args->A (2..8) is the number of actions, pf_params the MLP2 block D -> H -> H -> A WITHOUT a logstd
+ * tail (its outputs are the logits), args->acts rows are (N, 1) -- the drawn index as a float -- and args->old_logp gets
+ * log pi of it.  Per step and env the action is trl_cat_act_f32's: the uniform of (noise_seed, args->noise_step0 + step,
+ * env_offset + env index) against the prefix sums of exp(l - max); args->deterministic: arg-max, lowest index on ties.
+ * The env steps with the one-hot row of the index.  Everything else (value pass, bootstrap, resets, ring rows, header,
+ * episode log) is trl_rollout_synth_f32's.  args->noise / noise_flag / stage_n / norm_state must be unset (TRL_EINVAL);
+ * args->tanh_action is ignored.  Shapes: trl_rollout_cat_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32,
+ * 2 <= A <= 8, Tanh or ReLU. */
+int trl_rollout_synth_cat_f32(const trl_rollout_t* args, int64_t noise_seed, int64_t env_offset, void* stream);
+int trl_rollout_cat_supported(int D, int H, int A, int act);
 /* Page-locked host block -> device buffer by a KERNEL (the device reads host memory in place), meant for a stream of
  * its own next to the one that computes: n floats (n % 4 == 0, 16-byte aligned pointers); when every workgroup's part is
  * in device memory, state[0] = stamp is stored with device scope -- what a consumer launched on another stream polls

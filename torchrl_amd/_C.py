@@ -129,6 +129,8 @@ SIGNATURES = {
     "trl_mlp2_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_rollout_synth_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_void_p]),
     "trl_rollout_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_rollout_synth_cat_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_rollout_cat_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_stage_h2d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trl_ppo_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_mlp2_forward_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -541,6 +543,13 @@ def mlp2_forward(params, x, D, H, O, act, out=None):
 
 def rollout(args, device):
     check(lib().trl_rollout_synth_f32(C.byref(args), stream_ptr(device)), "trl_rollout_synth_f32")
+
+
+def rollout_cat(args, noise_seed, env_offset, device):
+    """The persistent rollout with a categorical head: actions keyed by (noise_seed, args.noise_step0 + step,
+    env_offset + env index), as trl_cat_act_f32 keys them."""
+    check(lib().trl_rollout_synth_cat_f32(C.byref(args), int(noise_seed), int(env_offset), stream_ptr(device)),
+          "trl_rollout_synth_cat_f32")
 
 
 def ppo_partial_stride(D, H, A):

@@ -290,8 +290,9 @@ class VecOnPolicyCollector(VecCollector):
         otherwise -- any other MLP shape is collected by the per-step launch sequence on the generic dense-layer
         kernels."""
         from .. import ops
-        # a categorical policy (policies.CategoricalDisPolicy) over Discrete(A): the per-step route with trl_cat_act_f32 in
-        # place of trl_gauss_explore_f32; `_dims[1]` = A is the head's width, the ring's `acts` are (N, 1) indices
+        # a categorical policy (policies.CategoricalDisPolicy) over Discrete(A): `_dims[1]` = A is the head's width, the
+        # ring's `acts` are (N, 1) indices.  The per-step route uses trl_cat_act_f32 in place of trl_gauss_explore_f32; the
+        # persistent rollout has a categorical head for the shapes of trl_rollout_cat_supported (see the end of this method)
         self._cat = getattr(self.pf, "continuous", True) is False and hasattr(self.pf, "logits")
         if not self._cat and not hasattr(self.pf, "logstd"):
             raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias and CategoricalDisPolicy policies")
@@ -325,8 +326,19 @@ class VecOnPolicyCollector(VecCollector):
         roll = pair and bool(lib.trl_rollout_supported(ps[0], ps[1], ps[2], ps[3])) and \
             (bool(mlp2) or os.environ.get("TRL_NO_RT_ROLLOUT") != "1")
         self._spec = ps if (roll and not getattr(self.env, "is_host_env", False)) else None   # ... and the rollout kernel
-        if self._cat:                                                       # (the persistent rollout samples Gaussians)
-            self._spec = None
+        if self._cat:
+            # the persistent rollout's categorical head (trl_rollout_synth_cat_f32): 64-wide pairs with 2..8 actions on a
+            # device env that takes one-hot actions, one rank, no observation normaliser (its kernel is the Gaussian
+            # benchmark shape's); everything else keeps the per-step route.  The route is opt-in, TRL_CAT_FUSED_ROLLOUT=1,
+            # until its rollout has been timed against the per-step replayed graph at 2048 envs x 128 steps
+            # (profiles/NOTES_categorical_rollout.md); TRL_NO_RT_ROLLOUT=1 switches it off like the other runtime-dims
+            # instantiations.
+            fused = pair and bool(lib.trl_rollout_cat_supported(ps[0], ps[1], ps[2], ps[3])) and \
+                os.environ.get("TRL_CAT_FUSED_ROLLOUT") == "1" and \
+                os.environ.get("TRL_NO_RT_ROLLOUT") != "1" and dist.world_size() == 1 and \
+                all(getattr(e, "discrete", False) and hasattr(e, "env_B") and not getattr(e, "is_host_env", False)
+                    and not hasattr(e, "_obs_normalizer") for e in (self.env, self.eval_env) if e is not None)
+            self._spec = ps if fused else None
 
     def _forward(self, net, x, out_dim, out=None):
         """mean / value of an MLP on the device: the fused 2-layer kernel when instantiated, the dense-layer family
@@ -409,7 +421,7 @@ class VecOnPolicyCollector(VecCollector):
         a.deterministic = int(deterministic)
         N = env.env_nums
         if store:
-            feats = (("obs", D), ("next_obs", D), ("acts", A), ("values", 1), ("rewards", 1),
+            feats = (("obs", D), ("next_obs", D), ("acts", 1 if self._cat else A), ("values", 1), ("rewards", 1),
                      ("terminals", 1), ("time_limits", 1), ("old_logp", 1))
             for key, f in feats:
                 setattr(a, key, buf._ensure_key(key, (N, f)).data_ptr())
@@ -438,7 +450,10 @@ class VecOnPolicyCollector(VecCollector):
             words = 8 + 3 * self.SPECULATIVE_ROWS
             a.publish_dst, a.publish_src, a.publish_words = self._blob_host.data_ptr(), self._blob.data_ptr(), words
             self._published = True
-        _C.rollout(a, env.device)
+        if self._cat:                                                   # the draw trl_cat_act_f32 makes at these steps
+            _C.rollout_cat(a, self._noise_seed, self._noise_layout(env)[1], env.device)
+        else:
+            _C.rollout(a, env.device)
         self._idle_hdr_clean = True
         if store:
             buf._advance(n_steps)

@@ -18,15 +18,6 @@
 
 #define CAT_THREADS 256
 
-// the uniform of (seed, counter, global env index g): element g & 3 of Philox block g >> 2 under the CATEGORICAL tag
-__device__ __forceinline__ float cat_uniform(int64_t seed, int64_t ctr, int64_t g) {
-  uint32_t x[4];
-  philox4x32_10((uint32_t)(ctr & 0xFFFFFFFFll), (uint32_t)((ctr >> 32) & 0xFFFFFFFFll), (uint32_t)((g >> 2) & 0xFFFFFFFFll),
-                TRL_TAG_CATEGORICAL, (uint32_t)(seed & 0xFFFFFFFFll), (uint32_t)((seed >> 32) & 0xFFFFFFFFll), x);
-  const int c = (int)(g & 3);
-  return trl_u01(c == 0 ? x[0] : c == 1 ? x[1] : c == 2 ? x[2] : x[3]);
-}
-
 __device__ __forceinline__ float cat_row_max(const float* __restrict__ l, int A, int& arg) {
   float m = l[0];
   arg = 0;
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(CAT_THREADS) void cat_act_kernel(const float* __res
   float S = 0.0f;
   for (int k = 0; k < A; ++k) S += expf(l[k] - m);
   if (!deterministic) {
-    const float u = u_in ? u_in[n] : cat_uniform(seed, ctr, env_offset + n);
+    const float u = u_in ? u_in[n] : trl_cat_uniform(seed, ctr, env_offset + n);
     const float thr = u * S;
     float c = 0.0f;
     a = A - 1;
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(CAT_THREADS) void philox_uniform_kernel(float* __re
                                                                      int64_t ctr0, int64_t env_offset) {
   const int64_t e = (int64_t)blockIdx.x * CAT_THREADS + threadIdx.x;
   if (e >= total) return;
-  out[e] = cat_uniform(seed, ctr0 + e / N, env_offset + e % N);
+  out[e] = trl_cat_uniform(seed, ctr0 + e / N, env_offset + e % N);
 }
 
 extern "C" int trl_philox_uniform_f32(float* out, int T, int N, int64_t seed, int64_t counter0, int64_t env_offset,

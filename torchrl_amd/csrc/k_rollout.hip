@@ -65,6 +65,7 @@ struct RolloutDev {
   int D, A;                   // runtime dims of the RT instantiations (template D / A are then capacities)
   int n_ro_wg; const f32x4* stg_src; unsigned long long* stg_dst; int64_t stg_n4;
   const uint32_t* stg_ready; uint32_t stg_job; uint32_t* stg_state; uint32_t* stg_ack;
+  int64_t cat_seed, cat_env0; // CAT instantiations: key and first global env index of the action draw (trl_cat_uniform)
 };
 #define RO_STAGERS 16
 
@@ -128,10 +129,18 @@ __device__ __forceinline__ void stage_block(const f32x4* __restrict__ src, unsig
 // (torchrl/collector/on_policy.py:90-155 and torchrl/networks/base.py:8-44 are shape-generic).  D = 32 (WIDE, a.D in
 // [18, 32] -- Ant's 27 observations): features 16..31 are a second k group of the first layer and a second row block of
 // the env GEMM instead of the single 17th feature that rides on the VALU.
-template <int D, int H, int A, int ACT, bool NORM, bool RT = false>
+// CAT = true: a categorical head (policies.CategoricalDisPolicy) over Ar = 2..8 actions.  The head's A outputs are the
+// logits; after the head exchange every lane holds all of its env's logits (they are 8 LDS words away), so the softmax is
+// the per-thread ascending-k loop of cat_act_kernel (k_categorical.hip) -- same max, same prefix sums, no cross-lane
+// step -- against the uniform of (cat_seed, global step, global env index), drawn 16 steps at a time like the Gaussian
+// noise (one (step, env) per thread).  The env takes the one-hot row of the drawn index: lane group g feeds action
+// dims g and 4 + g to the env GEMM as before, now 1.0 where the index matches -- a row selection of env_B, no one-hot row
+// in memory.  The ring's `acts` is (N, 1): the index as a float.  The parameter block has no logstd tail.
+template <int D, int H, int A, int ACT, bool NORM, bool RT = false, bool CAT = false>
 __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
   using S = RoShape<D, H, A>;
   constexpr bool WIDE = D > 17;
+  static_assert(!CAT || RT, "the categorical head exists as a runtime-dims instantiation only");
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!(RT && NORM), "the cooperative (normalised) rollout is instantiated for the benchmark shape");
   const int Dr = RT ? a.D : D, Ar = RT ? a.A : A;   // actual dims (row strides of obs / acts, parameter offsets)
@@ -188,7 +197,7 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
   for (int e = tid; e < H; e += RO_THREADS) { lds[S::O_B1 + e] = gp[F_B1 + e]; lds[S::O_B2 + e] = gp[F_B2 + e]; }
   if (tid < 8) {
     lds[S::O_B3 + tid] = tid < Ar ? gp[F_B3 + (tid < Ar ? tid : 0)] : 0.0f;
-    lds[S::O_LS + tid] = tid < Ar ? gp[F_LS + (tid < Ar ? tid : 0)] : 0.0f;
+    lds[S::O_LS + tid] = (!CAT && tid < Ar) ? gp[F_LS + (tid < Ar ? tid : 0)] : 0.0f;
   }
   // which of the tile's input features exist: feature 4g + q of the lane's x operand, feature 16 + g (narrow tile) or
   // 16 + 4g + q (wide tile); a missing feature is loaded from an in-range address and replaced by zero
@@ -293,7 +302,17 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
     const size_t cell = (size_t)row * a.N + n;
 
     // ---- exploration noise: host stream (reference parity, distribution.py:67-70) or device Philox ----
-    if (dev_noise && (t % RO_NB) == 0) {
+    float cat_u = 0.0f;
+    if constexpr (CAT) {
+      if (dev_noise && (t % RO_NB) == 0) {
+        // thread (wave mo, env j, g) draws the uniform of step t + 4 mo + g: what trl_cat_act_f32 draws at that step
+        const int ts = 4 * mo + g;
+        S_EPS[ts * 16 + j] = trl_cat_uniform(a.cat_seed, a.noise_step0 + t + ts, a.cat_env0 + n);
+        __syncthreads();   // (as below: the previous batch was read before the barriers of the step that ended it)
+      }
+      if (dev_noise) cat_u = S_EPS[(t % RO_NB) * 16 + j];
+    }
+    if (!CAT && dev_noise && (t % RO_NB) == 0) {
       // lane (env j, g) of wave mo draws both Philox blocks (8 normals) of step t + 4 mo + g
       const int ts = 4 * mo + g;
       const int64_t gs = a.noise_step0 + t + ts;
@@ -309,10 +328,10 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
       __syncthreads();   // readers of the previous batch finished before the barriers of the step that ended it
     }
     float eps_lo = 0.0f, eps_hi = 0.0f;
-    if (dev_noise) {
+    if (!CAT && dev_noise) {
       eps_lo = S_EPS[((t % RO_NB) * 8 + o_lo) * 16 + j];
       eps_hi = S_EPS[((t % RO_NB) * 8 + o_hi) * 16 + j];
-    } else if (a.noise) {
+    } else if (!CAT && a.noise) {
       eps_lo = valid ? a.noise[((size_t)t * a.N + n) * Ar + o_lo] : 0.0f;
       eps_hi = valid ? a.noise[((size_t)t * a.N + n) * Ar + o_hi] : 0.0f;
     }
@@ -360,10 +379,45 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
 #pragma unroll
     for (int w = 0; w < 4; ++w) { mean_lo += headp[(w * 8 + o_lo) * 16 + j]; mean_hi += headp[(w * 8 + o_hi) * 16 + j]; }
 
+    // categorical head (discrete_policies.py:136-150): cat_act_kernel's rule on the env's Ar logits
+    int cat_k = 0;
+    float cat_lsel = 0.0f, cat_m = 0.0f, cat_S = 1.0f;
+    if constexpr (CAT) {
+      float lg[8], ex[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float l = lds[S::O_B3 + k];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) l += headp[(w * 8 + k) * 16 + j];
+        lg[k] = l;
+      }
+      cat_m = lg[0];
+#pragma unroll
+      for (int k = 1; k < 8; ++k)
+        if (k < Ar && lg[k] > cat_m) { cat_m = lg[k]; cat_k = k; }    // strict: the lowest index wins a tie
+      cat_S = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (k < Ar) { ex[k] = expf(lg[k] - cat_m); cat_S += ex[k]; }
+      if (dev_noise) {
+        const float thr = cat_u * cat_S;
+        float c = 0.0f;
+        bool hit = false;
+        cat_k = Ar - 1;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (k < Ar) {
+            c += ex[k];
+            if (!hit && c >= thr) { cat_k = k; hit = true; }
+          }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cat_lsel = k == cat_k ? lg[k] : cat_lsel;
+    }
     // action + log-prob under the collecting policy (continuous_policy.py:123-129, distribution.py:33-45)
     const float z_lo = fmaf(std_lo, eps_lo, mean_lo), z_hi = fmaf(std_hi, eps_hi, mean_hi);
-    const float act_lo = has_lo ? (a.tanh_action ? trl_tanh(z_lo) : z_lo) : 0.0f;
-    const float act_hi = has_hi ? (a.tanh_action ? trl_tanh(z_hi) : z_hi) : 0.0f;
+    const float act_lo = CAT ? (g == cat_k ? 1.0f : 0.0f) : has_lo ? (a.tanh_action ? trl_tanh(z_lo) : z_lo) : 0.0f;
+    const float act_hi = CAT ? (4 + g == cat_k ? 1.0f : 0.0f) : has_hi ? (a.tanh_action ? trl_tanh(z_hi) : z_hi) : 0.0f;
     // ---- env step: next^T[f][env] = sum_k M[f][k] [obs; act]^T[k][env] (action part) ----
     e0 = mfma16(we0[XK], act_lo, e0);
     e0 = mfma16(we0[XK + 1], act_hi, e0);
@@ -380,10 +434,14 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
     const float act_sq = mfma16(1.0f, fmaf(act_lo, act_lo, act_hi * act_hi), zero4)[0];   // all action dims
     float logp = 0.0f;
     if (mo == 3) {                                          // only the wave that stores old_logp needs it
-      float zc, lp = 0.0f;
-      if (has_lo) lp += gauss_logp_term(act_lo, mean_lo, iv_lo, ls_lo, a.tanh_action, zc);
-      if (has_hi) lp += gauss_logp_term(act_hi, mean_hi, iv_hi, ls_hi, a.tanh_action, zc);
-      logp = mfma16(1.0f, lp, zero4)[0];
+      if constexpr (CAT) {
+        logp = (cat_lsel - cat_m) - logf(cat_S);
+      } else {
+        float zc, lp = 0.0f;
+        if (has_lo) lp += gauss_logp_term(act_lo, mean_lo, iv_lo, ls_lo, a.tanh_action, zc);
+        if (has_hi) lp += gauss_logp_term(act_hi, mean_hi, iv_hi, ls_hi, a.tanh_action, zc);
+        logp = mfma16(1.0f, lp, zero4)[0];
+      }
     }
     CLK(5)
     float nx[XK];
@@ -522,8 +580,12 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
           if (g == 0 && (!RT || Dr > 16)) dst[16] = src[4];
         }
       } else if (mo == 2) {
-        if (has_lo) a.acts[cell * Ar + g] = act_lo;
-        if (has_hi) a.acts[cell * Ar + 4 + g] = act_hi;
+        if constexpr (CAT) {
+          if (g == 0) a.acts[cell] = (float)cat_k;          // (N, 1): the index
+        } else {
+          if (has_lo) a.acts[cell * Ar + g] = act_lo;
+          if (has_hi) a.acts[cell * Ar + 4 + g] = act_hi;
+        }
       } else {
         // one store instruction for the four per-cell scalars: lane group g writes key g.  values[cell]
         // carries the over-length marker to the value pass, which overwrites it with V(obs)
@@ -750,14 +812,14 @@ static int rollout_norm_capacity() {
   return cus * per_cu * RO_ENVS;
 }
 
-template <int D, int H, int A, int ACT, bool RT = false>
+template <int D, int H, int A, int ACT, bool RT = false, bool CAT = false>
 static int launch_rollout(const RolloutDev& d, hipStream_t s, hipEvent_t value_wait = nullptr) {
   const int n_wg = trl_ceil_div(d.N, RO_ENVS);
   if constexpr (RT) {
     if (d.norm_state) { trl_set_error("rollout: the normalised rollout is instantiated for the benchmark shape only"); return TRL_EUNSUPPORTED; }
     RolloutDev e = d;
     e.n_ro_wg = n_wg;
-    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
+    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true, CAT>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
   } else if (d.norm_state) {
     const int cap = rollout_norm_capacity<D, H, A, ACT>();
     if (d.norm_update && d.N > cap) {
@@ -812,7 +874,14 @@ extern "C" int trl_rollout_supported(int D, int H, int A, int act) {
   return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
 }
 
-extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) {
+// Categorical heads on the persistent rollout: the 64-wide two-layer pairs of the runtime-dims instantiations with 2..8
+// actions (the head's outputs are the logits; no running observation normaliser).
+extern "C" int trl_rollout_cat_supported(int D, int H, int A, int act) {
+  return H == 64 && D >= 2 && D <= 32 && A >= 2 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
+}
+
+// cat: the categorical entry point (trl_rollout_synth_cat_f32) with its draw's key and first global env index
+static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t cat_seed, int64_t cat_env0) {
   if (!p) { trl_set_error("rollout: null descriptor"); return TRL_EINVAL; }
   TRL_REQUIRE(p->pf_params && p->vf_params && p->env_A && p->env_B, "null network / env pointer");
   TRL_REQUIRE(p->cur_obs && p->t_env && p->cur_step && p->episode_idx && p->ep_return, "null env state pointer");
@@ -824,6 +893,16 @@ extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) {
   TRL_REQUIRE(p->top >= 0 && p->top < p->rows, "top outside ring");
   TRL_REQUIRE(no_ring || p->n_steps <= p->rows, "n_steps exceeds ring rows");
   TRL_REQUIRE(p->horizon > 0 && p->max_episode_frames > 0, "horizon / max_episode_frames must be positive");
+  if (cat) {
+    TRL_REQUIRE(cat_env0 >= 0, "categorical: negative env offset");
+    TRL_REQUIRE(!p->noise && !p->noise_flag && !p->stage_n,
+                "categorical: actions are drawn from the device Philox stream only (no host noise block, nothing staged)");
+    TRL_REQUIRE(!p->norm_state, "categorical: no running observation normaliser in the persistent rollout");
+    if (!trl_rollout_cat_supported(p->D, p->H, p->A, p->act)) {
+      trl_set_error("rollout: categorical shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
+      return TRL_EUNSUPPORTED;
+    }
+  }
   if (p->n_steps == 0) return TRL_OK;
   RolloutDev d;
   d.pf_params = p->pf_params; d.vf_params = p->vf_params; d.env_A = p->env_A; d.env_B = p->env_B;
@@ -845,6 +924,7 @@ extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) {
   d.pub_dst = (uint32_t*)p->publish_dst; d.pub_src = (const uint32_t*)p->publish_src; d.pub_words = p->publish_words;
   d.noise_flag = p->noise ? p->noise_flag : nullptr; d.noise_stamp = p->noise_stamp;
   d.n_ro_wg = 0; d.stg_n4 = 0;
+  d.cat_seed = cat_seed; d.cat_env0 = cat_env0;
   if (p->stage_n) {
     TRL_REQUIRE(p->stage_n > 0 && (p->stage_n & 3) == 0 && p->stage_src && p->stage_dst && p->stage_ready && p->stage_state &&
                 p->stage_ack && !p->norm_state, "stage: n % 4 == 0, non-null pointers, no observation normaliser");
@@ -860,6 +940,14 @@ extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t vw = (hipEvent_t)p->value_wait_event;
   d.D = p->D; d.A = p->A;
+  if (cat) {
+    if (p->D <= 17) {
+      if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 8, TRL_ACT_TANH, true, true>(d, s, vw);
+      return launch_rollout<17, 64, 8, TRL_ACT_RELU, true, true>(d, s, vw);
+    }
+    if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true, true>(d, s, vw);
+    return launch_rollout<32, 64, 8, TRL_ACT_RELU, true, true>(d, s, vw);
+  }
   if (p->D == 17 && p->H == 64 && p->A == 6) {
     if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 6, TRL_ACT_TANH>(d, s, vw);
     if (p->act == TRL_ACT_RELU) return launch_rollout<17, 64, 6, TRL_ACT_RELU>(d, s, vw);
@@ -874,6 +962,12 @@ extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) {
   }
   trl_set_error("rollout: shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
   return TRL_EUNSUPPORTED;
+}
+
+extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) { return rollout_synth(p, stream, false, 0, 0); }
+
+extern "C" int trl_rollout_synth_cat_f32(const trl_rollout_t* p, int64_t noise_seed, int64_t env_offset, void* stream) {
+  return rollout_synth(p, stream, true, noise_seed, env_offset);
 }
 
 extern "C" int trl_rollout_norm_workspace(int N) {

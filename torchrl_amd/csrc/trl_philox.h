@@ -7,7 +7,7 @@
 
 #define TRL_TAG_RESET 0x52535421u
 #define TRL_TAG_NOISE 0x4E4F4953u
-#define TRL_TAG_CATEGORICAL 0x43415447u   // one uniform per (seed, step counter, global env index): k_categorical.hip
+#define TRL_TAG_CATEGORICAL 0x43415447u   // one uniform per (seed, step counter, global env index): trl_cat_uniform
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t out[4]) {
@@ -40,4 +40,14 @@ __device__ __forceinline__ void philox_normals4(uint32_t c0, uint32_t c1, uint32
     z[p] = r * c;
     z[p + 1] = r * s;
   }
+}
+
+// the uniform of (seed, counter, global env index g) of the categorical action draw: element g & 3 of Philox block g >> 2
+// under the CATEGORICAL tag -- shared by the per-step launch (k_categorical.hip) and the persistent rollout (k_rollout.hip)
+__device__ __forceinline__ float trl_cat_uniform(int64_t seed, int64_t ctr, int64_t g) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)(ctr & 0xFFFFFFFFll), (uint32_t)((ctr >> 32) & 0xFFFFFFFFll), (uint32_t)((g >> 2) & 0xFFFFFFFFll),
+                TRL_TAG_CATEGORICAL, (uint32_t)(seed & 0xFFFFFFFFll), (uint32_t)((seed >> 32) & 0xFFFFFFFFll), x);
+  const int c = (int)(g & 3);
+  return trl_u01(c == 0 ? x[0] : c == 1 ? x[1] : c == 2 ? x[2] : x[3]);
 }
