@@ -4,6 +4,9 @@ GPU kernels) or the on-GPU synthetic id:
 
     python examples/ppo_discrete_vec.py --config config/ppo_cartpole_host.json --vec_env_nums 16 --seed 0 --overwrite
     python examples/ppo_discrete_vec.py --config config/ppo_synth_discrete.json --vec_env_nums 2048 --seed 0 --overwrite
+
+With TRL_CAT_FUSED_ROLLOUT=1 TRL_CAT_FUSED_UPDATE=1 (both opt-in) the synthetic config's 64 x 64 nets are collected by the
+one-launch rollout and updated by the fused two-launch sequence instead of the per-step collector and the generic engine.
 """
 import os.path as osp
 import random

@@ -435,6 +435,32 @@ int trl_ppo_reduce_adam_net_f32(const float* partial, const double* scal_partial
                                 int D, int H, int A, float* grads, double* info,
                                 const trl_adam_t* adam, float* workspace, void* stream);
 
+/* --- the fused minibatch update for a CATEGORICAL policy (CategoricalDisPolicy, 2 <= A <= 8 actions) ----------
+ * The entry points above with a categorical head on the policy network (the gradient kernel's CAT instantiations): the A head
+ * outputs are logits, args->acts is (rows, N, 1) -- the action index as a float --, args->pf_params is [W1 b1 W2 b2 W3 b3]
+ * (no logstd: P_pf = H D + H + H H + H + A H + A), args->tanh_action is ignored.  Softmax, log pi and entropy follow
+ * trl_cat_losses_f32's fixed arithmetic; d(loss)/d(logit k) = g_lp (1[k = a] - p_k) + (entropy_coeff / n_global) p_k (log p_k + H).
+ * Shapes: trl_ppo_cat_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU.  All n_wg_pf
+ * modes of trl_ppo_batch_t work.  partial rows are trl_ppo_cat_partial_stride(D, H, A) floats.  The folds take the same
+ * arguments as their Gaussian counterparts (pf_params of trl_ppo_cat_reduce_f32 is not read); the optimiser groups are
+ * [policy without logstd | value]; info[20] receives the entropy sum of the local samples and info[8..11] / [16..19] are
+ * written as zero.  Same row fold order, norm rendezvous and Adam arithmetic: a single-network launch folded by
+ * trl_ppo_cat_reduce_adam_net_f32 gives the bits of the joint launch + trl_ppo_cat_reduce_adam_f32.  There is no cross-rank
+ * variant and no one-launch step for this head. */
+int trl_ppo_cat_supported(int D, int H, int A, int act);
+int trl_ppo_cat_partial_stride(int D, int H, int A);
+int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* args, void* stream);
+int trl_ppo_cat_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                           int D, int H, int A, const float* pf_params, float* grads, double* info,
+                           void* stream);
+int trl_ppo_cat_reduce_adam_workspace(int D, int H, int A);
+int trl_ppo_cat_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                                int D, int H, int A, float* grads, double* info,
+                                const trl_adam_t* adam, float* workspace, void* stream);
+int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,
+                                    int D, int H, int A, float* grads, double* info,
+                                    const trl_adam_t* adam, float* workspace, void* stream);
+
 typedef struct trl_comm trl_comm_t;   /* opaque communicator, see the collectives section below */
 /* --- C1 / C2 / C3: collectives of the multi-GPU path ---------------
  * The reference has no distributed backend; with envs sharded by index over one process per GPU

@@ -1,0 +1,462 @@
+"""The fused two-launch PPO / A2C update for categorical policies (ppo_grad_wave_kernel<..., CAT>, trl_ppo_cat_*):
+the reference fixture through the fused engine, gradients against fp64 autograd, the single-network launches against the
+joint one, the fused against the generic engine, the engine's launch modes, and whole iterations on the fused rollout.
+Tolerances are the project's: scalars rel 1e-4 / abs 1e-5, post-step parameters abs 1e-6, gradients
+1e-4 of the network's largest entry.  The fixture test fails on a build without the categorical update."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import _categorical_ref as ref                                                # noqa: E402
+import _categorical_update_cases as cu                                        # noqa: E402
+
+pytestmark = pytest.mark.gpu
+SWITCH = "TRL_CAT_FUSED_UPDATE"                                               # the fused update is opt-in
+DEV = torch.device("cuda:0")
+H = cu.H
+
+
+class _Stub:
+    epoch_frames = 0
+
+
+class _Log:
+    def __init__(self): self.infos = []
+    def add_update_info(self, d): self.infos.append(dict(d))
+    def add_epoch_info(self, *a, **k): pass
+    def log(self, *a): pass
+    def finish(self): pass
+
+
+@pytest.fixture(scope="module")
+def g():
+    return np.load(os.path.join(HERE, "golden", "categorical_update.npz"))
+
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    for k in ("TRL_GENERIC_PPO", "TRL_PPO_CHAINS", "TRL_PPO_STEP", "TRL_NO_GRAPH", "TRL_NO_RT_ROLLOUT", SWITCH,
+              "TRL_CAT_FUSED_ROLLOUT"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def dev(x, dtype=None):
+    t = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x)
+    return (t if dtype is None else t.to(dtype)).to(DEV).contiguous()
+
+
+def make_agent(algo_cls, pf, vf, D, A, B, **kw):
+    from torchrl_amd.env.synth import SynthVecEnv
+    return algo_cls(pf=pf, vf=vf, tau=0.95, shuffle=True, discount=0.99, num_epochs=10, batch_size=B, gae=True,
+                    env=SynthVecEnv(4, obs_dim=D, act_dim=A, device=DEV, discrete=True), replay_buffer=None,
+                    collector=_Stub(), logger=_Log(), device=DEV, save_dir=None, **kw)
+
+
+def fixture_agent(g, tag, algo_cls, **kw):
+    D, A, Hh, B = (int(x) for x in g[f"{tag}_args"])
+    pf, vf = cu.nets_of(D, A, 5 + D, hidden=(Hh, Hh))
+    return pf, vf, make_agent(algo_cls, pf, vf, D, A, B, **kw)
+
+
+def batch_of(g, tag):
+    return {k: g[f"{tag}_batch_{k}"] for k in ("obs", "acts", "advs", "values", "estimate_returns")}
+
+
+def param_error(mod, g, prefix):
+    return max((a.detach().cpu() - b).abs().max().item() for a, b in zip(cu.linear_params(mod), ref.params_from(g, prefix)))
+
+
+def assert_info(info, g, prefix, absent, errlog, label):
+    keys = [str(k) for k in g[prefix + "_keys"]]
+    want = dict(zip(keys, g[prefix + "_vals"]))
+    kept = [k for k in keys if not k.startswith(absent)]
+    assert sorted(info) == sorted(kept)
+    assert not any(k.startswith(("log_std/", "std/")) for k in info)
+    worst = 0.0
+    for k in kept:
+        worst = max(worst, abs(info[k] - want[k]) / (1e-5 + 1e-4 * abs(want[k])))
+    errlog(label + "_info_worst_over_bound", worst, 1.0)
+    for k in kept:
+        assert info[k] == pytest.approx(want[k], rel=1e-4, abs=1e-5), k
+
+
+def is_fused(eng):
+    return type(eng).__name__ == "_FusedPPO" and eng.categorical
+
+
+# ---------------------------------------------------------------- 1. the reference fixture through the fused engine
+def test_fixture_a2c_and_ppo_on_the_fused_engine(g, monkeypatch, errlog):
+    from torchrl_amd.algo import A2C, PPO
+    monkeypatch.setenv(SWITCH, "1")
+    tag = "s17"
+    pf, vf, agent = fixture_agent(g, tag, A2C, plr=3e-4, vlr=1e-3, entropy_coeff=0.01)
+    info = agent.update(batch_of(g, tag))
+    eng = agent.engine()
+    assert is_fused(eng) and not hasattr(pf, "logstd")
+    assert eng.P_pf == sum(p.numel() for p in cu.linear_params(pf)) == 64 * 17 + 64 + 4096 + 64 + 64 * 6 + 6
+    assert_info(info, g, f"{tag}_a2c_info", ("std/",), errlog, "a2c")
+    for name, mod in (("pf", pf), ("vf", vf)):
+        err = param_error(mod, g, f"{tag}_a2c_{name}1_")
+        errlog("a2c_%s_%s" % (tag, name), err, 1e-6)
+        assert err <= 1e-6, (name, err)
+
+    pf, vf, agent = fixture_agent(g, tag, PPO, plr=3e-4, vlr=3e-4, clip_para=0.2, opt_epochs=2, entropy_coeff=0.005)
+    tgt = {k[len(f"{tag}_ppo_tpf0_"):].replace("__", "."): torch.from_numpy(g[k].copy())
+           for k in g.files if k.startswith(f"{tag}_ppo_tpf0_")}
+    agent.target_pf.load_state_dict(tgt)
+    for s, clipv in enumerate(g[f"{tag}_ppo_clipv"]):
+        agent.clipped_value_loss = bool(clipv)
+        info = agent.update(batch_of(g, tag))
+        assert_info(info, g, f"{tag}_ppo_info{s}", ("log_std/",), errlog, "ppo_update%d" % s)
+        for name, mod in (("pf", pf), ("vf", vf)):
+            err = param_error(mod, g, f"{tag}_ppo_{name}{s + 1}_")
+            errlog("ppo_%s_update%d_%s" % (tag, s, name), err, 1e-6)
+            assert err <= 1e-6, (s, name, err)
+    assert is_fused(agent.engine())
+    # H = 32: not a shape the fused kernels carry -- the generic engine, switch or not
+    _, _, small = fixture_agent(g, "s4", A2C, plr=3e-4, vlr=1e-3, entropy_coeff=0.01)
+    assert type(small.engine()).__name__ == "_GenericPPO" and small.engine().categorical
+
+
+def test_engine_choice(monkeypatch):
+    """Without the switch nothing changes; with it, only Adam on 64-wide matching nets takes the fused engine."""
+    from torchrl_amd.algo import A2C
+    def mk(hidden=(64, 64), **kw):
+        pf, vf = cu.nets_of(17, 6, 1, hidden=hidden)
+        return make_agent(A2C, pf, vf, 17, 6, 64, **kw)
+    assert type(mk().engine()).__name__ == "_GenericPPO"
+    monkeypatch.setenv(SWITCH, "1")
+    assert is_fused(mk().engine())
+    assert type(mk(hidden=(64, 32)).engine()).__name__ == "_GenericPPO"
+    assert type(mk(optimizer_class=torch.optim.RMSprop).engine()).__name__ == "_GenericPPO"
+    pf9, vf9 = cu.nets_of(17, 9, 1)
+    assert type(make_agent(A2C, pf9, vf9, 17, 9, 64).engine()).__name__ == "_GenericPPO"
+    monkeypatch.setenv("TRL_GENERIC_PPO", "1")
+    assert type(mk().engine()).__name__ == "_GenericPPO"
+
+
+# ---------------------------------------------------------------- direct kernel calls
+def flat_of(x):
+    flat = torch.cat([p.reshape(-1) for p in x["pf"] + x["vf"]])
+    return flat, sum(p.numel() for p in x["pf"]), sum(p.numel() for p in x["vf"])
+
+
+def adv_raw_of(advs):
+    a = advs.double().reshape(-1)
+    return torch.tensor([a.sum(), (a * a).sum(), a.max(), -a.min()], dtype=torch.float64)
+
+
+class Launch:
+    """Device copies of an input set and the descriptor of trl_ppo_cat_minibatch_grad_f32 on them."""
+
+    def __init__(self, x):
+        from torchrl_amd import _C
+        self.x = x
+        self.t = {k: dev(x[k]) for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp")}
+        self.row_idx = dev(x["row_idx"])
+        self.raw = dev(adv_raw_of(cu.minibatch(x)["advs"]))
+        flat, self.P_pf, self.P_vf = flat_of(x)
+        self.flat0 = dev(flat)
+        self.ps = _C.ppo_cat_partial_stride(x["D"], H, x["A"])
+        self.act = _C.ACT_TANH if x["act"] == "tanh" else _C.ACT_RELU
+
+    def args(self, flat, loss_mode, clipv, n_wg, n_wg_pf, partial, scal):
+        from torchrl_amd import _C
+        x, g = self.x, _C.PpoBatchArgs()
+        for k, v in self.t.items():
+            setattr(g, k, v.data_ptr())
+        if loss_mode == ref.LOSS_A2C:
+            g.old_logp = None                                                # A2C never reads log pi_old
+        if not clipv:
+            g.old_values = None
+        g.row_idx, g.rows_mb, g.N = self.row_idx.data_ptr(), x["rows"], x["N"]
+        g.adv_raw, g.n_global = self.raw.data_ptr(), float(x["rows"] * x["N"])
+        g.pf_params, g.vf_params = flat.data_ptr(), flat.data_ptr() + 4 * self.P_pf
+        g.D, g.H, g.A, g.act = x["D"], H, x["A"], self.act
+        g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = cu.CLIP, cu.C_ENT, int(clipv), 1   # (ignored)
+        g.loss_mode = loss_mode
+        g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = partial.data_ptr(), scal.data_ptr(), n_wg, n_wg_pf
+        return g
+
+    def rows(self, n):
+        # (filled with NaN: every slot the fold reads has to be written by the launch)
+        return (torch.full((n, self.ps), float("nan"), device=DEV), torch.full((n, 8), float("nan"), dtype=torch.float64, device=DEV))
+
+
+def autograd_fp64(x, loss_mode, clipv):
+    mb = cu.minibatch(x)
+    pf = [p.double().requires_grad_(True) for p in x["pf"]]
+    vf = [p.double().requires_grad_(True) for p in x["vf"]]
+    obs = mb["obs"].double()
+    ref.objective(cu.forward(pf, obs, x["act"]), cu.forward(vf, obs, x["act"]), mb["acts"].reshape(-1), mb["advs"].double().reshape(-1),
+                  mb["rets"].double(), mb["old_values"].double(), mb["old_logp"].double(), cu.CLIP, cu.C_ENT, clipv,
+                  loss_mode).backward()
+    return torch.cat([p.grad.reshape(-1) for p in pf]), torch.cat([p.grad.reshape(-1) for p in vf])
+
+
+# ---------------------------------------------------------------- 2. gradients against fp64 autograd
+@pytest.mark.parametrize("c", cu.GRAD_CASES, ids=cu.case_id)
+def test_gradients_vs_fp64_autograd(c, errlog):
+    from torchrl_amd import _C
+    x = cu.grad_inputs(c)
+    L = Launch(x)
+    n_wg = x["n_wg"]
+    mb = cu.minibatch(x)
+    with torch.no_grad():
+        logits32 = cu.forward(x["pf"], mb["obs"], x["act"])
+        v32 = cu.forward(x["vf"], mb["obs"], x["act"])
+    for loss_mode, clipv in cu.LOSSES:
+        label = "mode%d_clipv%d" % (loss_mode, int(clipv))
+        partial, scal = L.rows(n_wg)
+        grads = torch.full((L.P_pf + L.P_vf,), float("nan"), device=DEV)
+        info = torch.zeros(24, dtype=torch.float64, device=DEV)
+        info[8:12] = 7.0                                                     # the fold writes these as zero
+        info[16:20] = 7.0
+        _C.ppo_cat_minibatch_grad(L.args(L.flat0, loss_mode, clipv, n_wg, 0, partial, scal), DEV)
+        _C.ppo_cat_reduce(partial, scal, n_wg, x["D"], H, x["A"], grads, info)
+        got = grads.cpu().double()
+        assert torch.isfinite(got).all()
+        want_pf, want_vf = autograd_fp64(x, loss_mode, clipv)
+        for name, gg, ww in (("pf", got[:L.P_pf], want_pf), ("vf", got[L.P_pf:], want_vf)):
+            err, top = (gg - ww).abs().max().item(), ww.abs().max().item()
+            errlog("%s_%s_grad_over_max" % (label, name), err / top, 1e-4)
+            print("%s %s %s: max abs err %.3e, max |grad| %.3e" % (cu.case_id(c), label, name, err, top))
+            assert err <= 1e-4 * top, (label, name, err, top)
+        r = ref.losses(logits32, v32, mb["acts"].reshape(-1), mb["advs"].reshape(-1), mb["rets"].reshape(-1),
+                       mb["old_values"].reshape(-1), mb["old_logp"].reshape(-1), cu.CLIP, cu.C_ENT, clipv, loss_mode)
+        i = info.cpu()
+        errlog(label + "_entropy_sum_rel", abs(i[20].item() / r["ent"].double().sum().item() - 1.0), 1e-5)
+        errlog(label + "_logp_sum_rel", abs(i[1].item() / r["lp"].double().sum().item() - 1.0), 1e-5)
+        assert i[20].item() == pytest.approx(r["ent"].double().sum().item(), rel=1e-5)
+        assert i[1].item() == pytest.approx(r["lp"].double().sum().item(), rel=1e-5)
+        assert i[0].item() == pytest.approx(r["surr"].double().sum().item(), rel=1e-4, abs=1e-3)   # bound of test_categorical_gpu.py
+        assert i[7].item() == pytest.approx(r["vloss"].double().sum().item(), rel=1e-4, abs=1e-3)
+        assert all(i[k].item() == 0.0 for k in (8, 9, 10, 11, 16, 17, 18, 19))
+
+
+# ---------------------------------------------------------------- 3. single-network launches
+def adam_args(flat, grads, m, v, P_pf, P_vf, norms, step):
+    from torchrl_amd import _C
+    a = _C.AdamArgs()
+    a.params, a.grads, a.exp_avg, a.exp_avg_sq = flat.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr()
+    a.n_groups = 2
+    a.group_sizes[0], a.group_sizes[1] = P_pf, P_vf
+    a.group_lr[0], a.group_lr[1] = 3e-4, 1e-3
+    a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
+    a.step_count, a.norms_out, a.device_state = step, norms.data_ptr(), 0
+    return a
+
+
+@pytest.mark.parametrize("c", cu.NET_CASES, ids=cu.case_id)
+def test_single_network_launches_match_the_joint_launch_bitwise(c):
+    from torchrl_amd import _C
+    lib = _C.lib()
+    x = cu.grad_inputs(c)
+    L = Launch(x)
+    per_net = x["n_wg"] // 2
+    n_ws = lib.trl_ppo_cat_reduce_adam_workspace(x["D"], H, x["A"])
+    rs = np.random.RandomState(5)
+    P = L.P_pf + L.P_vf
+    m0, v0 = dev(rs.randn(P).astype(np.float32) * 1e-3), dev((rs.rand(P).astype(np.float32) + 0.1) * 1e-5)
+    stream = _C.stream_ptr(DEV)
+
+    def state():
+        return dict(flat=L.flat0.clone(), m=m0.clone(), v=v0.clone(), grads=torch.zeros(P, device=DEV),
+                    info=torch.zeros(2, 24, dtype=torch.float64, device=DEV), norms=torch.zeros(2, 2, device=DEV))
+
+    for loss_mode, clipv in cu.LOSSES:
+        joint, split = state(), state()
+        ws = [torch.zeros(n_ws, device=DEV) for _ in range(3)]
+        for step in (0, 1):                                                   # two steps: the second reads stepped parameters and moments
+            s = joint
+            partial, scal = L.rows(2 * per_net)
+            _C.ppo_cat_minibatch_grad(L.args(s["flat"], loss_mode, clipv, 2 * per_net, per_net, partial, scal), DEV)
+            a = adam_args(s["flat"], s["grads"], s["m"], s["v"], L.P_pf, L.P_vf, s["norms"][step], 3 + step)
+            _C.check(lib.trl_ppo_cat_reduce_adam_f32(partial.data_ptr(), scal.data_ptr(), 2 * per_net, per_net, x["D"], H, x["A"],
+                                                     s["grads"].data_ptr(), s["info"][step].data_ptr(), C.byref(a),
+                                                     ws[0].data_ptr(), stream), "trl_ppo_cat_reduce_adam_f32")
+            s = split
+            for net, n_wg_pf in ((0, per_net), (1, -1)):
+                partial, scal = L.rows(per_net)
+                _C.ppo_cat_minibatch_grad(L.args(s["flat"], loss_mode, clipv, per_net, n_wg_pf, partial, scal), DEV)
+                a = adam_args(s["flat"], s["grads"], s["m"], s["v"], L.P_pf, L.P_vf, s["norms"][step], 3 + step)
+                _C.check(lib.trl_ppo_cat_reduce_adam_net_f32(partial.data_ptr(), scal.data_ptr(), per_net, net, x["D"], H, x["A"],
+                                                             s["grads"].data_ptr(), s["info"][step].data_ptr(), C.byref(a),
+                                                             ws[1 + net].data_ptr(), stream), "trl_ppo_cat_reduce_adam_net_f32")
+        torch.cuda.synchronize()
+        assert all(int(w[0].item()) == 0 for w in ws)                         # no norm rendezvous timed out
+        for k in ("flat", "m", "v", "grads", "norms", "info"):
+            assert torch.equal(joint[k], split[k]), (loss_mode, clipv, k)
+        assert not torch.equal(joint["flat"], L.flat0) and torch.isfinite(joint["flat"]).all()
+        assert (joint["info"][:, 20] > 0).all() and (joint["norms"] > 0).all()
+
+
+# ---------------------------------------------------------------- 4. fused against generic engine
+def engine_tensors(x, old_logp):
+    t = {k: dev(x[k]) for k in ("obs", "acts", "advs", "rets", "old_values")}
+    t["old_logp"] = dev(old_logp)
+    return t
+
+
+def all_params(pf, vf):
+    return torch.cat([p.detach().reshape(-1) for p in cu.linear_params(pf) + cu.linear_params(vf)]).clone()
+
+
+@pytest.mark.parametrize("c", cu.ENGINE_CASES, ids=lambda c: "D%d_A%d" % c[:2])
+def test_fused_engine_vs_generic_engine(c, monkeypatch, errlog):
+    from torchrl_amd import _C
+    from torchrl_amd.algo import PPO
+    x = cu.engine_inputs(c)
+    D, A, seed = c
+    _, old_logp = cu.engine_old_logp(x)
+    B = cu.ENGINE_ROWS_MB * cu.ENGINE_N
+    kw = dict(plr=3e-4, vlr=1e-3, clip_para=cu.CLIP, opt_epochs=1, entropy_coeff=cu.C_ENT, clipped_value_loss=True)
+    agents = []
+    for switch in ("0", "1"):
+        monkeypatch.setenv(SWITCH, switch)
+        pf, vf = cu.nets_of(D, A, seed)
+        agent = make_agent(PPO, pf, vf, D, A, B, **kw)
+        agents.append((pf, vf, agent, agent.engine(), engine_tensors(x, old_logp)))
+    (gpf, gvf, _, geng, gt), (fpf, fvf, _, feng, ft) = agents
+    assert type(geng).__name__ == "_GenericPPO" and is_fused(feng)
+    start = all_params(fpf, fvf)
+    assert torch.equal(all_params(gpf, gvf), start)
+    for e, row_idx in enumerate(x["epochs"]):
+        gi, fi = geng.run(gt, row_idx, cu.ENGINE_N), feng.run(ft, row_idx, cu.ENGINE_N)
+        err = (all_params(gpf, gvf) - all_params(fpf, fvf)).abs().max().item()
+        errlog("epoch%d_params" % e, err, 1e-6)
+        assert err <= 1e-6, (e, err)
+        assert len(gi) == len(fi) == len(row_idx)
+        worst = 0.0
+        for a, b in zip(gi, fi):
+            assert sorted(a) == sorted(b) and not any(k.startswith("log_std/") for k in b)
+            for k in a:
+                worst = max(worst, abs(a[k] - b[k]) / (1e-5 + 1e-4 * abs(a[k])))
+        errlog("epoch%d_info_worst_over_bound" % e, worst, 1.0)
+        for a, b in zip(gi, fi):
+            for k in a:
+                assert b[k] == pytest.approx(a[k], rel=1e-4, abs=1e-5), (e, k)
+    assert not torch.equal(all_params(fpf, fvf), start)
+    # an un-stepped policy against its own log pi (the per-step kernels' trl_cat_logp_f32): ratio 1 within 1e-4
+    monkeypatch.setenv(SWITCH, "1")
+    pf, vf = cu.nets_of(D, A, seed)
+    agent = make_agent(PPO, pf, vf, D, A, B, **kw)
+    eng = agent.engine()
+    T, N = x["obs"].shape[:2]
+    with torch.no_grad():
+        own = _C.cat_logp(pf.logits(dev(x["obs"]).reshape(T * N, -1)).contiguous(), dev(x["acts"]).reshape(T * N))
+    own = own[0]
+    first = eng.run(engine_tensors(x, own.reshape(T, N, 1).cpu()), x["epochs"][0][:1], N)[0]
+    errlog("unstepped_ratio_max", abs(first["ratio/max"] - 1.0), 1e-4)
+    errlog("unstepped_ratio_min", abs(first["ratio/min"] - 1.0), 1e-4)
+    assert abs(first["ratio/max"] - 1.0) <= 1e-4 and abs(first["ratio/min"] - 1.0) <= 1e-4
+
+
+# ---------------------------------------------------------------- 5. engine modes
+def run_mode(x, old_logp, chains, monkeypatch, step="split"):
+    from torchrl_amd.algo import PPO
+    monkeypatch.setenv(SWITCH, "1")
+    monkeypatch.setenv("TRL_PPO_CHAINS", chains)
+    monkeypatch.setenv("TRL_PPO_STEP", step)
+    pf, vf = cu.nets_of(x["D"], x["A"], x["seed"])
+    agent = make_agent(PPO, pf, vf, x["D"], x["A"], cu.ENGINE_ROWS_MB * cu.ENGINE_N, plr=3e-4, vlr=1e-3, clip_para=cu.CLIP,
+                       opt_epochs=1, entropy_coeff=cu.C_ENT)
+    eng = agent.engine()
+    assert is_fused(eng) and eng.two_chains == (chains == "two") and not eng.one_launch
+    t = engine_tensors(x, old_logp)
+    out = []
+    for e in range(3):                                                        # eager, captured, replayed
+        infos = eng.run(t, x["epochs"][e], cu.ENGINE_N)
+        torch.cuda.synchronize()
+        out.append((all_params(pf, vf), eng.m.clone(), eng.v.clone(), infos))
+    replayed = bool(eng._chain_graphs) if chains == "two" else eng._graph is not None
+    assert replayed                                                           # the third epoch came from captured graphs
+    return out
+
+
+def test_engine_modes_are_bit_identical_and_deterministic(monkeypatch):
+    from torchrl_amd import _C
+    x = cu.engine_inputs(cu.ENGINE_CASES[1])
+    _, old_logp = cu.engine_old_logp(x)
+    before = _C.eager_fallback_count()
+    two = run_mode(x, old_logp, "two", monkeypatch)
+    assert _C.eager_fallback_count() == before                                # kernels only, whole epochs
+    joint = run_mode(x, old_logp, "joint", monkeypatch)
+    again = run_mode(x, old_logp, "two", monkeypatch)
+    fused_switch = run_mode(x, old_logp, "joint", monkeypatch, step="fused")  # no one-launch step for this head: the split sequence
+    assert _C.eager_fallback_count() == before
+    for other in (joint, again, fused_switch):
+        for e, ((p0, m0, v0, i0), (p1, m1, v1, i1)) in enumerate(zip(two, other)):
+            assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(v0, v1), e
+            assert len(i0) == len(i1) and all(a == b for a, b in zip(i0, i1)), e
+    assert not torch.equal(two[0][0], two[2][0])
+    assert all(np.isfinite(list(i.values())).all() for ep in two for i in ep[3])
+
+
+# ---------------------------------------------------------------- 6. end to end with the fused rollout
+def test_iterations_on_the_fused_rollout_and_the_fused_update(monkeypatch):
+    """N = 32 envs, T = 16, 64 x 64 nets on SynthCheetahDiscrete-v0 (17 / 6), both switches, deferred statistics: one
+    rollout launch, a value pass and two launches per minibatch, the next rollout beside the value chain (held back by a
+    device spin so that they really overlap).  Three iterations; the parameters equal those of the joint sequence."""
+    from torchrl_amd.algo import PPO
+    from torchrl_amd.collector.on_policy import VecOnPolicyCollector
+    from torchrl_amd.env import get_vec_env
+    from torchrl_amd.replay_buffers.on_policy import OnPolicyReplayBuffer
+    monkeypatch.setenv(SWITCH, "1")
+    monkeypatch.setenv("TRL_CAT_FUSED_ROLLOUT", "1")
+    N, T = 32, 16
+    finals = []
+    for chains in ("two", "joint"):
+        monkeypatch.setenv("TRL_PPO_CHAINS", chains)
+        np.random.seed(4)
+        pf, vf = cu.nets_of(17, 6, 0)
+        with torch.no_grad():
+            pf.seq_append_fcs[-1].weight.mul_(30.0)                          # leave the near-uniform initial policy
+        env, eval_env = (get_vec_env("SynthCheetahDiscrete-v0", {"reward_scale": 1, "obs_norm": False}, N, device=DEV)
+                         for _ in range(2))
+        for e_ in (env, eval_env):
+            e_.horizon = 9
+        env.seed(2)
+        buf = OnPolicyReplayBuffer(N * T, env_nums=N, time_limit_filter=True)
+        col = VecOnPolicyCollector(vf, env=env, eval_env=eval_env, pf=pf, replay_buffer=buf, device=DEV, train_render=False,
+                                   epoch_frames=N * T, max_episode_frames=999, eval_episodes=1, noise_mode="device")
+        assert col._spec is not None and col._cat                            # the one-launch rollout
+        logger = _Log()
+        later = []
+        logger.add_update_infos_later = later.append
+        agent = PPO(pf=pf, vf=vf, plr=3e-4, vlr=3e-4, clip_para=0.2, opt_epochs=2, tau=0.95, shuffle=True,
+                    entropy_coeff=0.005, discount=0.99, num_epochs=10, batch_size=N * 4, gae=True, env=env, replay_buffer=buf,
+                    collector=col, logger=logger, device=DEV, save_dir=None)
+        eng = agent.engine()
+        assert is_fused(eng)
+        eng._test_value_chain_delay = 5_000_000
+        for epoch in range(3):
+            res = col.train_one_epoch()
+            agent.current_epoch = epoch
+            agent.update_per_epoch()
+            assert buf._acts.shape == (T, N, 1)
+            assert np.isfinite(float(res["train_epoch_reward"]))
+        for resolve in later:
+            logger.infos.extend(dict(d) for d in resolve())
+        saved = {k: v.cpu() for k, v in vf.state_dict().items()}              # a reader of the value function settles first
+        torch.cuda.synchronize()
+        assert all(torch.equal(saved[k], v.cpu()) for k, v in vf.state_dict().items())
+        assert len(logger.infos) == 3 * 2 * (T // 4) == eng.step_count
+        assert all(np.isfinite(list(i.values())).all() for i in logger.infos)
+        assert not any(k.startswith("log_std/") for k in logger.infos[0])
+        acts = buf._acts.cpu()
+        assert acts.min() >= 0 and acts.max() <= 5 and len(set(acts.view(-1).tolist())) > 1
+        flat = eng.flat.clone()
+        assert torch.isfinite(flat).all()
+        finals.append((flat, eng.m.clone(), eng.v.clone(), logger.infos))
+    (f0, m0, v0, i0), (f1, m1, v1, i1) = finals
+    assert torch.equal(f0, f1) and torch.equal(m0, m1) and torch.equal(v0, v1)
+    assert len(i0) == len(i1) and all(a == b for a, b in zip(i0, i1))

@@ -184,6 +184,15 @@ SIGNATURES = {
                                               C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
     "trl_ppo_reduce_adam_xrank_net_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trl_ppo_cat_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_cat_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_cat_minibatch_grad_f32": (C.c_int, [C.POINTER(PpoBatchArgs), C.c_void_p]),
+    "trl_ppo_cat_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trl_ppo_cat_reduce_adam_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_cat_reduce_adam_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
+    "trl_ppo_cat_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
     "trl_ppo_step_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_ppo_step_max_workgroups": (C.c_int, []),
     "trl_ppo_minibatch_step_f32": (C.c_int, [C.POINTER(PpoBatchArgs), C.c_void_p, C.c_void_p, C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
@@ -557,6 +566,25 @@ def ppo_partial_stride(D, H, A):
     if ps < 0:
         check(ps, "trl_ppo_partial_stride")
     return ps
+
+
+def ppo_cat_partial_stride(D, H, A):
+    ps = lib().trl_ppo_cat_partial_stride(D, H, A)
+    if ps < 0:
+        check(ps, "trl_ppo_cat_partial_stride")
+    return ps
+
+
+def ppo_cat_minibatch_grad(args, device):
+    """The fused minibatch gradient for a categorical policy: args.acts is (rows, N, 1), args.pf_params has no logstd."""
+    check(lib().trl_ppo_cat_minibatch_grad_f32(C.byref(args), stream_ptr(device)), "trl_ppo_cat_minibatch_grad_f32")
+
+
+def ppo_cat_reduce(partial, scal_partial, n_wg, D, H, A, grads, info, n_wg_pf=0):
+    check(lib().trl_ppo_cat_reduce_f32(dev_ptr(partial, name="partial"),
+                                       dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A,
+                                       None, dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
+                                       stream_ptr(partial.device)), "trl_ppo_cat_reduce_f32")
 
 
 def ppo_minibatch_grad(args, device):

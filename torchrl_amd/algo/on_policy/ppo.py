@@ -124,15 +124,23 @@ class _FusedPPO:
         self.algo = algo
         pf, vf = algo.pf, algo.vf
         ps, vs = pf.mlp2_spec(), vf.mlp2_spec()
-        if ps is None or vs is None or not hasattr(pf, "logstd"):
-            raise _C.TrlError("fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias policy")
+        # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's CAT instantiations and their folds
+        # (trl_ppo_cat_*); no logstd in the flat vector, the entropy arrives through info slot 20
+        self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
+        if ps is None or vs is None or not (self.categorical or hasattr(pf, "logstd")):
+            raise _C.TrlError("fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias or CategoricalDisPolicy policy")
+        if self.categorical and not _C.lib().trl_ppo_cat_supported(*ps):
+            raise _C.TrlError("the fused categorical update carries H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU; got %s" % (ps,))
+        if self.categorical and dist.collectives_active():
+            raise _C.TrlError("the fused categorical update runs on one rank (no cross-rank fold exists for this head)")
         if vs[0] != ps[0] or vs[1] != ps[1] or vs[2] != 1 or vs[3] != ps[3]:
             raise _C.TrlError("policy %s and value %s must share input, width and activation" % (ps, vs))
         self.D, self.H, self.A, self.act = ps
         self.dev = next(pf.parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the fused path needs a GPU (no CPU path exists)" % self.dev)
-        pf_list = pf._mlp2_param_list() + [pf.logstd]
+        tail = (lambda net: []) if self.categorical else (lambda net: [net.logstd])
+        pf_list = pf._mlp2_param_list() + tail(pf)
         vf_list = vf._mlp2_param_list()
         self.P_pf = sum(p.numel() for p in pf_list)
         self.P_vf = sum(p.numel() for p in vf_list)
@@ -146,22 +154,31 @@ class _FusedPPO:
         tgt = getattr(algo, "target_pf", None)
         self.target_flat = None
         if tgt is not None:
-            self.target_flat = flatten_into(tgt._mlp2_param_list() + [tgt.logstd])
+            self.target_flat = flatten_into(tgt._mlp2_param_list() + tail(tgt))
+            if self.categorical:                                       # (its logits() forward must find THIS storage, see _GenericPPO)
+                tgt._flat = self.target_flat
         self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
         self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
-        self.p_stride = _C.ppo_partial_stride(self.D, self.H, self.A)
+        lib = _C.lib()
+        sfx = "cat_" if self.categorical else ""
+        self._k_grad = (getattr(lib, "trl_ppo_%sminibatch_grad_f32" % sfx), "trl_ppo_%sminibatch_grad_f32" % sfx)
+        self._k_fold = (getattr(lib, "trl_ppo_%sreduce_adam_f32" % sfx), "trl_ppo_%sreduce_adam_f32" % sfx)
+        self._k_fold_net = (getattr(lib, "trl_ppo_%sreduce_adam_net_f32" % sfx), "trl_ppo_%sreduce_adam_net_f32" % sfx)
+        self.p_stride = (_C.ppo_cat_partial_stride if self.categorical else _C.ppo_partial_stride)(self.D, self.H, self.A)
         self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         self.max_wg = 2 * max(1, self.n_cu // 2)
         self.partial = torch.zeros(self.max_wg, self.p_stride, device=self.dev)
         self.scal = torch.zeros(self.max_wg, 8, dtype=torch.float64, device=self.dev)
-        n_ws = _C.lib().trl_ppo_step_workspace(self.D, self.H, self.A)   # (begins with trl_ppo_reduce_adam_f32's workspace)
+        n_ws = lib.trl_ppo_cat_reduce_adam_workspace(self.D, self.H, self.A) if self.categorical else \
+            lib.trl_ppo_step_workspace(self.D, self.H, self.A)         # (begins with trl_ppo_reduce_adam_f32's workspace)
         self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + flags / norm granules of the fused step
         # TRL_PPO_STEP=fused (opt-in): the whole minibatch step as ONE launch (trl_ppo_minibatch_step_f32 -- its workgroups
         # meet inside the launch, so the grid must be resident at once; one process per device).  Same bits as the default
         # two-launch sequence (gradient, then fold / clip / Adam), and on MI355X 4 us per step SLOWER: rows that cross XCDs
         # inside a launch must be written through to the coherence point and every dependent hop costs 2.2-2.6 us, which is
         # what a graph-captured launch boundary costs too (profiles/NOTES_r06.md).
-        self.one_launch = os.environ.get("TRL_PPO_STEP", "split") == "fused"
+        # (a categorical policy has no one-launch instantiation: it takes the split sequence whatever the switch says)
+        self.one_launch = os.environ.get("TRL_PPO_STEP", "split") == "fused" and not self.categorical
         self.step_max_wg = _C.lib().trl_ppo_step_max_workgroups()
         # One process: the critic's and the actor's updates of an epoch (ppo.py:93-122 / 41-91: separate networks, optimisers,
         # clips and statistics) run as TWO launch sequences on two streams (`_run_chains`); TRL_PPO_CHAINS=joint keeps the
@@ -268,6 +285,8 @@ class _FusedPPO:
         loss_mode = int(getattr(algo, "loss_mode", _C.LOSS_PPO_CLIP))
         probe = getattr(self, "probe", None)                           # bench.py: HIP events around the grad kernel
         fused = not dist.collectives_active()
+        if self.categorical and not fused:
+            raise _C.TrlError("the fused categorical update runs on one rank (no cross-rank fold exists for this head)")
         one_launch = fused and self.one_launch and n_wg <= self.step_max_wg
         # (env shards on several ranks: the two chains need the in-launch gradient exchange of the peer transport, whose
         # granules and exchange counts are per network; over all-reduce CALLS the joint sequence stays)
@@ -370,15 +389,14 @@ class _FusedPPO:
                         ev[1].record()
                         probe.append(ev)
                     continue
-                _C.check(lib.trl_ppo_minibatch_grad_f32(C.byref(g), stream), "trl_ppo_minibatch_grad_f32")
+                _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
                 if probe is not None:
                     ev[1].record()
                     probe.append(ev)
                 if fused:                                              # one process: reduce + clip + Adam in one launch
-                    _C.check(lib.trl_ppo_reduce_adam_f32(self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf,
-                                                         self.D, self.H, self.A, self.grads.data_ptr(), info_base + 192 * k,
-                                                         C.byref(a), self.red_ws.data_ptr(), stream),
-                             "trl_ppo_reduce_adam_f32")
+                    _C.check(self._k_fold[0](self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf,
+                                             self.D, self.H, self.A, self.grads.data_ptr(), info_base + 192 * k,
+                                             C.byref(a), self.red_ws.data_ptr(), stream), self._k_fold[1])
                     continue
                 if xrank:                                              # the same launch with the cross-rank SUM inside
                     _C.check(lib.trl_ppo_reduce_adam_xrank_f32(self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf,
@@ -562,16 +580,16 @@ class _FusedPPO:
                 g.row_idx = idx_dev.data_ptr() + 8 * rows_mb * k
                 g.adv_raw = raw.data_ptr() + 32 * k
                 a.step_count, a.norms_out = self.step_count + k + 1, norm_base + 8 * k
-                _C.check(lib.trl_ppo_minibatch_grad_f32(C.byref(g), stream), "trl_ppo_minibatch_grad_f32")
+                _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
                 if xrank:                                              # the network's gradient SUM over ranks inside the launch
                     _C.check(lib.trl_ppo_reduce_adam_xrank_net_f32(part.data_ptr(), scal.data_ptr(), g.n_wg, net, self.D, self.H,
                                                                    self.A, self.grads.data_ptr(), info_base + 192 * k, C.byref(a),
                                                                    ws.data_ptr(), dist.comm_handle(), stream),
                              "trl_ppo_reduce_adam_xrank_net_f32")
                     continue
-                _C.check(lib.trl_ppo_reduce_adam_net_f32(part.data_ptr(), scal.data_ptr(), g.n_wg, net, self.D, self.H, self.A,
-                                                         self.grads.data_ptr(), info_base + 192 * k, C.byref(a), ws.data_ptr(), stream),
-                         "trl_ppo_reduce_adam_net_f32")
+                _C.check(self._k_fold_net[0](part.data_ptr(), scal.data_ptr(), g.n_wg, net, self.D, self.H, self.A,
+                                             self.grads.data_ptr(), info_base + 192 * k, C.byref(a), ws.data_ptr(), stream),
+                         self._k_fold_net[1])
 
         # (graphs by key, a few of them: the stored observations alternate between the ring's tensor and its shadow, see
         # collector/on_policy.py::_launch, so a steady run replays TWO captured sets in turn)
@@ -730,7 +748,15 @@ def make_engine(algo):
     pf, vf = algo.pf, algo.vf
     ps = pf.mlp2_spec() if hasattr(pf, "mlp2_spec") else None
     vs = vf.mlp2_spec() if hasattr(vf, "mlp2_spec") else None
-    if getattr(pf, "continuous", True) is False:                        # categorical head: never the fused 64-wide kernels
+    if getattr(pf, "continuous", True) is False:
+        # categorical head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1, opt-in) AND
+        # both nets have a shape its CAT instantiations carry, the optimiser is Adam and this is the only rank
+        if os.environ.get("TRL_CAT_FUSED_UPDATE") == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
+                and hasattr(pf, "logits") and ps is not None and vs is not None \
+                and _C.lib().trl_ppo_cat_supported(*ps) and _C.lib().trl_ppo_cat_supported(vs[0], vs[1], ps[2], vs[3]) \
+                and (vs[0], vs[1], vs[2], vs[3]) == (ps[0], ps[1], 1, ps[3]) \
+                and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
+            return _FusedPPO(algo)
         return _GenericPPO(algo)
     if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
             and os.environ.get("TRL_GENERIC_PPO") != "1":

@@ -99,16 +99,23 @@ __device__ __forceinline__ float row_sum16(float v) {
 // 17th column that rides on the VALU.
 // WT: the workgroup's partial row is folded by other workgroups of THIS launch (the one-launch step): it leaves as
 // device-scope write-through stores instead of plain ones
-template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, bool WT = false>
+// CAT (policy pass, RT only): a categorical head (policies.CategoricalDisPolicy; torchrl/policies/discrete_policies.py:124-168)
+// instead of the diagonal Gaussian.  The A head outputs are logits, the stored action is ONE float per sample (the index:
+// `acts` rows are (N, 1)), the flat policy block has no logstd tail ([W1 b1 W2 b2 W3 b3]) and the per-sample entropy sum
+// leaves through the eighth column of the scalar row.  Only the block between the head MFMAs and `dout` differs: softmax,
+// log pi and entropy in k_categorical.hip's fixed arithmetic, d(loss)/d(logits) as in cat_losses_kernel.
+template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, bool WT = false, bool CAT = false>
 __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_wg_net) {
   using S = WvShape<D, H, A>;
   constexpr bool WIDE = D > 17;                      // a second 16-feature group (features 16 .. 31) on the matrix pipe
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
+  static_assert(!CAT || (IS_PF && RT && !WT), "the categorical head is a policy pass of the runtime-dims two-launch kernels");
+  constexpr int AS = CAT ? 1 : 0;                    // CAT: floats per stored action (0: the Gaussian's O)
   const int Dr = RT ? a.D : D;                       // input features = row stride of obs and of W1
   const int O = IS_PF ? (RT ? a.A : A) : 1;          // outputs
   // offsets inside the flat parameter block for the actual dims (MlpFlat, trl_mlp.h)
   const int F_W1 = 0, F_B1 = H * Dr, F_W2 = F_B1 + H, F_B2 = F_W2 + H * H, F_W3 = F_B2 + H, F_B3 = F_W3 + O * H,
-            F_LS = F_B3 + O, F_END = F_LS + O;
+            F_LS = F_B3 + O, F_END = CAT ? F_LS : F_LS + O;      // (no logstd tail behind a categorical head)
   const int PS = RT ? a.p_stride : S::P_STRIDE;      // floats of a partial row (the LDS images keep the template's stride)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, g = lane >> 4, i = j;
@@ -158,7 +165,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     oxt[q] = (unsigned)((4 * g + q) * Dr + (jv ? i : 0)) * 4u;
     oxq2[q] = (unsigned)(j * Dr + (fv2[q] ? 16 + 4 * g + q : 0)) * 4u;
     oxt2[q] = (unsigned)((4 * g + q) * Dr + (jv2 ? 16 + i : 0)) * 4u;
-    oa_[q] = (unsigned)(j * O + (4 * g + q < O ? 4 * g + q : 0)) * 4u;
+    oa_[q] = CAT ? (unsigned)j * 4u : (unsigned)(j * O + (4 * g + q < O ? 4 * g + q : 0)) * 4u;
   }
   auto ldb = [](const float* base, unsigned byte_off) -> float {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -181,9 +188,12 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       for (int q = 0; q < 4; ++q) { xq2[q] = ldb(ob, oxq2[q]); xtq2[q] = ldb(ob, oxt2[q]); }
     }
     if constexpr (IS_PF) {
-      const float* ab = a.acts + cell0 * O;
+      const float* ab = a.acts + cell0 * (CAT ? AS : O);
+      if constexpr (CAT) { lq[0] = ldb(ab, oa_[0]); lq[1] = lq[2] = lq[3] = 0.0f; }   // the action index of sample j
+      else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) lq[q] = ldb(ab, oa_[q]);
+        for (int q = 0; q < 4; ++q) lq[q] = ldb(ab, oa_[q]);
+      }
       lq[4] = ldb(a.advs + cell0, os);
       lq[5] = a.old_logp ? ldb(a.old_logp + cell0, os) : 0.0f;
     } else {
@@ -209,8 +219,11 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       }
     }
     if constexpr (IS_PF) {
+      if constexpr (CAT) { lq[0] = a.acts[p]; lq[1] = lq[2] = lq[3] = 0.0f; }
+      else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) lq[r] = a.acts[p * O + (4 * g + r < O ? 4 * g + r : 0)];
+        for (int r = 0; r < 4; ++r) lq[r] = a.acts[p * O + (4 * g + r < O ? 4 * g + r : 0)];
+      }
       lq[4] = a.advs[p]; lq[5] = a.old_logp ? a.old_logp[p] : 0.0f;
     } else {
       lq[0] = lq[1] = lq[2] = lq[3] = 0.0f;
@@ -313,7 +326,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int o = 4 * g + r;
-    const float raw = (IS_PF && o < O) ? gp[F_LS + (o < O ? o : 0)] : 0.0f;
+    const float raw = (IS_PF && !CAT && o < O) ? gp[F_LS + (o < O ? o : 0)] : 0.0f;
     lsv[r] = fminf(fmaxf(raw, -20.0f), 2.0f);                   // continuous_policy.py:8-9,185
     ivv[r] = __expf(-2.0f * lsv[r]);
     lspass[r] = (raw >= -20.0f && raw <= 2.0f) ? 1.0f : 0.0f;   // clamp passes gradient inside [-20, 2]
@@ -342,6 +355,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
   f32x4 gW1b[4];                                     // WIDE: dW1[f1 slice][16 <= k < 32]
   float gb1[4][4], gb2[4][4], gW1c[4][4];           // per-lane (own sample) partials: db1, db2, dW1[:, 16]
   float db3[4], dls[4], stv[7];
+  float ent_sum = 0.0f;                              // CAT: sum of the per-sample entropies (lanes g == 0)
 #pragma unroll
   for (int x = 0; x < 4; ++x) {
     gW1[x] = gW3[x] = gW1b[x] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -450,6 +464,40 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       WCLK(14)
       // lane (j, g < 2) owns outputs o = 4g + r of sample j
       float zc[4], lp = 0.0f;
+      float pk[4], lpk[4], ent = 0.0f;                               // CAT: p_k, log p_k of the lane's logits; the sample's entropy
+      int ai = 0;                                                    // CAT: the stored action
+      if constexpr (CAT) {
+        // The sample's (up to) 8 logits sit in lanes (j, 0) and (j, 1).  m = max_k l_k; e_k = exp(l_k - m); S = sum_k e_k in
+        // ascending k (lane g = 1 continues lane g = 0's partial sum: a missing logit adds an exact zero); p_k = e_k / S;
+        // log p_k = (l_k - m) - log S -- the arithmetic of cat_losses_kernel.  Lanes g >= 2 run on zeros.
+        float lg[4], ek[4], m = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          lg[r] = oa[r] + ob[r];
+          m = (4 * g + r < O) ? fmaxf(m, lg[r]) : m;
+        }
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = g < 2 ? m : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ek[r] = (4 * g + r < O) ? expf(lg[r] - m) : 0.0f;
+        const float c_own = ((ek[0] + ek[1]) + ek[2]) + ek[3];
+        const float c_lo = __shfl_xor(c_own, 16, 64);                // lane g = 1: e_0 + .. + e_3
+        float Ssum = g == 1 ? (((c_lo + ek[0]) + ek[1]) + ek[2]) + ek[3] : c_own;
+        const float S_hi = __shfl_xor(Ssum, 16, 64);                 // lane g = 0: the whole sum
+        Ssum = g == 0 ? S_hi : (g == 1 ? Ssum : 1.0f);
+        const float logS = logf(Ssum);
+        ai = min(max((int)lin[0], 0), O - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool has = 4 * g + r < O;
+          lpk[r] = has ? (lg[r] - m) - logS : 0.0f;
+          pk[r] = ek[r] / Ssum;
+          lp += (has && 4 * g + r == ai) ? lpk[r] : 0.0f;
+          ent -= pk[r] * lpk[r];
+        }
+        lp += __shfl_xor(lp, 16, 64);                                // the action's lane holds log pi, the other an exact zero
+        ent += __shfl_xor(ent, 16, 64);                              // H = -sum_k p_k log p_k (logits 0..3 + 4..7)
+      } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                                  // branch-free: lanes without an output compute on zeros
         const bool has = 4 * g + r < O;
@@ -460,6 +508,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       }
       WCLK(18)
       lp += __shfl_xor(lp, 16, 64);                                // outputs 0..3 (g = 0) + 4..7 (g = 1)
+      }
       WCLK(19)
       const float advn = valid ? (lin[4] - adv_mu) * adv_rstd : 0.0f;
       float ratio, s1, s2, g_lp;
@@ -475,6 +524,18 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       }
       WCLK(20)
       float dout[4];
+      if constexpr (CAT) {
+        // dout_k = g_lp (1[k = a] - p_k) + (entropy_coeff / n) p_k (log p_k + H): the entropy bonus -c H in the loss
+        const float ce = a.entropy_coeff * inv_b;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool own = valid && g < 2 && 4 * g + r < O;
+          dout[r] = own ? g_lp * ((4 * g + r == ai ? 1.0f : 0.0f) - pk[r]) + ce * pk[r] * (lpk[r] + ent) : 0.0f;
+          db3[r] += dout[r];
+          if (g < 2) DOS[(4 * g + r) * LDT + j] = dout[r];           // dout^T[o][s] for dW3
+        }
+        if (valid && g == 0) ent_sum += ent;
+      } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool own = valid && g < 2 && 4 * g + r < O;
@@ -482,6 +543,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
         db3[r] += dout[r];
         dls[r] += own ? lspass[r] * (g_lp * (zc[r] * zc[r] * ivv[r] - 1.0f) - a.entropy_coeff * inv_b) : 0.0f;
         if (g < 2) DOS[(4 * g + r) * LDT + j] = dout[r];           // dout^T[o][s] for dW3
+      }
       }
       WCLK(21)
       if (valid && g == 0) {
@@ -657,7 +719,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     const float b3 = row_sum16(db3[r]), dl = row_sum16(dls[r]);
     if (j == 0 && o < O) {
       gimg[F_B3 + o] = b3;
-      if (IS_PF) gimg[F_LS + o] = dl;
+      if (IS_PF && !CAT) gimg[F_LS + o] = dl;
     }
   }
   WCLK(7)
@@ -689,9 +751,11 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
                  v6 = wave_sum(own ? (double)stv[6] : 0.0);
     const float v2 = wave_max(own ? stv[2] : -INFINITY), v3 = wave_max(own ? stv[3] : -INFINITY),
                 v4 = wave_max(own ? stv[4] : -INFINITY), v5 = wave_max(own ? stv[5] : -INFINITY);
+    double v7 = 0.0;                                   // CAT: the entropy sum rides in the row's free eighth column
+    if constexpr (CAT) v7 = wave_sum(own ? (double)ent_sum : 0.0);
     if (lane == 0) {
       double* p = sred + wave * 8;
-      p[0] = v0; p[1] = v1; p[2] = v2; p[3] = v3; p[4] = v4; p[5] = v5; p[6] = v6; p[7] = 0.0;
+      p[0] = v0; p[1] = v1; p[2] = v2; p[3] = v3; p[4] = v4; p[5] = v5; p[6] = v6; p[7] = v7;
     }
   }
   __syncthreads();
@@ -858,8 +922,24 @@ __device__ __forceinline__ void fold_logstd_stats(const float* __restrict__ logs
   fold_logstd_stats_raw(logstd[lane < n_act ? lane : 0], n_act, lane, info);
 }
 
+// one wave, categorical head: the entropy sum of the local samples (eighth column of the policy's scalar rows, a lane adds
+// its rows lane, lane + 64, ... in that order) into info[20]; the log_std / std slots are written as zero --
+// trl_cat_losses_f32's convention (trl_ppo_loss.h)
+__device__ __noinline__ void fold_entropy_stats(const double* __restrict__ base, int nrow, int lane, double* __restrict__ info) {
+  double v = 0.0;
+  for (int w = lane; w < nrow; w += 64) v += base[(size_t)w * 8 + 7];
+  v = wave_sum(v);
+  if (lane == 0) {
+    info[20] = v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) info[8 + k] = info[16 + k] = 0.0;
+  }
+}
+
 // returns (wave 0 lanes) the reduced gradient value of chunk `bx` (64 parameters) of network `net`, 0 outside the parameter
 // range; `stats`: this call also takes the network's scalar statistics (waves 2 / 3)
+// CAT: the policy block has no logstd tail (logstd is null) and wave 3 folds the entropy column instead
+template <bool CAT = false>
 __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ partial,
                                                   const double* __restrict__ scal, int n_wg, int n_pf,
                                                   int p_stride, int p_pf, int p_vf,
@@ -886,17 +966,22 @@ __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ part
   // path of the blocks whose 64 parameters matter: wave 2 its network's statistics, wave 3 of the policy's block log_std
   // and std.
   if (stats && wave == 2) fold_scalar_stats(scal + (size_t)row0 * 8, nrow, net, lane, info);
-  if (stats && net == 0 && wave == 3 && logstd) fold_logstd_stats(logstd, n_act, lane, info);
+  if constexpr (CAT) {
+    if (stats && net == 0 && wave == 3) fold_entropy_stats(scal + (size_t)row0 * 8, nrow, lane, info);
+  } else {
+    if (stats && net == 0 && wave == 3 && logstd) fold_logstd_stats(logstd, n_act, lane, info);
+  }
   return gval;
 }
 
+template <bool CAT = false>
 __global__ __launch_bounds__(64 * RED_WAVES) void ppo_reduce_kernel(const float* __restrict__ partial,
                                                          const double* __restrict__ scal, int n_wg, int n_pf,
                                                          int p_stride, int p_pf, int p_vf,
                                                          const float* __restrict__ logstd, int n_act,
                                                          float* __restrict__ grads, double* __restrict__ info) {
-  ppo_reduce_block(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
-                   blockIdx.x == gridDim.x - 1);
+  ppo_reduce_block<CAT>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
+                        blockIdx.x == gridDim.x - 1);
 }
 
 // ---------------------------------------------------------------- K11 clip + Adam
@@ -1000,7 +1085,7 @@ __device__ __forceinline__ void adam_element(const AdamDev& a, int e, float gr) 
 // blocks -- 4 waves per SIMD -- resident beside each other.  With the statistics inlined into the job loop the kernel took
 // 156 registers: the second rank's blocks found no room next to the first's, its norm rendezvous could not complete, and
 // both ranks sat out their time-outs -- round 6, caught by tests/test_bench_multirank_gpu.py)
-template <bool LOOP>                                  // false: the grid has one block per job (no job loop: the common launch)
+template <bool LOOP, bool CAT = false>                // LOOP false: the grid has one block per job (no job loop: the common launch)
 __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(const float* __restrict__ partial,
                                                               const double* __restrict__ scal, int n_wg, int n_pf,
                                                               int p_stride, int p_pf, int p_vf,
@@ -1044,7 +1129,7 @@ __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(cons
   for (int j = blk; j < (LOOP ? n_jobs : blk + 1); j += LOOP ? grid : 1) {
     const int net = j / nb, bx = j - net * nb;
     if (j != blk) __syncthreads();                                // the fold's LDS image is read by wave 0 of the previous job
-    float gval = ppo_reduce_block(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
+    float gval = ppo_reduce_block<CAT>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
     if (wave == 0) {
       if (xrank) {
         // C1 of SURVEY.md 8(e) inside the launch: every rank pushes its 64 folded values into its slot on all ranks and
@@ -1351,8 +1436,9 @@ __device__ __forceinline__ void ppo_step_tail(const PpoDev& a, const StepDev& t,
   SCLK(7)
 }
 
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool STEP>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool STEP, bool CAT = false>
 __global__ __launch_bounds__(WV_THREADS, 1) void ppo_grad_wave_kernel(PpoDev a, StepDev t) {
+  static_assert(!CAT || (RT && !STEP), "categorical head: runtime-dims tiles, two-launch sequence");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // this launch's sequence number (the step's workspace): read by every workgroup before anything of it is published
   unsigned seq = 0u;
@@ -1366,7 +1452,7 @@ __global__ __launch_bounds__(WV_THREADS, 1) void ppo_grad_wave_kernel(PpoDev a, 
 #ifdef TRL_CHAIN_CLK                                  /* tools/time_chains.py: when did this workgroup start and end (100 MHz) */
   const unsigned long long clk0 = wall_clock64();
 #endif
-  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, STEP>(a, lds, blockIdx.x, a.n_pf);
+  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, STEP, CAT>(a, lds, blockIdx.x, a.n_pf);
   else                          ppo_wave_pass<D, H, A, ACT, false, CONTIG, RT, STEP>(a, lds, blockIdx.x - a.n_pf, a.n_wg - a.n_pf);
 #ifdef TRL_CHAIN_CLK
   __syncthreads();
@@ -1428,23 +1514,41 @@ extern "C" int trl_ppo_partial_stride(int D, int H, int A) {
   return TRL_EUNSUPPORTED;
 }
 
+// Categorical head (ppo_wave_pass<..., CAT = true>): the runtime-dims tiles only, at least two actions; the flat policy
+// block is [W1 b1 W2 b2 W3 b3] (no logstd tail).
+static bool ppo_cat_shape(int D, int H, int A) { return H == 64 && D >= 2 && D <= 32 && A >= 2 && A <= 8; }
+static int ppo_p_pf(int D, int H, int A, bool cat) { return H * D + H + H * H + H + A * H + A + (cat ? 0 : A); }
+static int ppo_p_vf(int D, int H) { return H * D + H + H * H + H + H + 1; }
+extern "C" int trl_ppo_cat_supported(int D, int H, int A, int act) {
+  return (ppo_cat_shape(D, H, A) && (act == TRL_ACT_TANH || act == TRL_ACT_RELU)) ? 1 : 0;
+}
+extern "C" int trl_ppo_cat_partial_stride(int D, int H, int A) {
+  if (ppo_cat_shape(D, H, A)) {
+    const int p_pf = ppo_p_pf(D, H, A, true), p_vf = ppo_p_vf(D, H);
+    return ((p_pf > p_vf ? p_pf : p_vf) + 63) & ~63;
+  }
+  trl_set_error("trl_ppo_cat_partial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8)", D, H, A);
+  return TRL_EUNSUPPORTED;
+}
+static int ppo_stride_for(int D, int H, int A, bool cat) { return cat ? trl_ppo_cat_partial_stride(D, H, A) : trl_ppo_partial_stride(D, H, A); }
+
 // Kernel generations that were built and measured on MI355X before this one (profiles/README.md): groups of
 // 4 waves per tile with LDS rendezvous (85 us per 65 536-sample minibatch), this wave-per-tile kernel (64 us),
 // and a PAIR of waves per tile with two waves per SIMD (75 us) -- on gfx950 the fp32 MFMA and the VALU do not
 // overlap across the two waves of a SIMD (tools/ubench/mfma_valu.hip: an MFMA-only wave and a VALU-only wave
 // on one SIMD take the SUM of their times), so a second wave only adds its duplicated loss / fetch work.
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool STEP>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool STEP, bool CAT = false>
 static int launch_ppo_v(const PpoDev& d, const StepDev& t, hipStream_t s) {
   using S = WvShape<D, H, A>;
   const size_t lds = S::LDS_FLOATS * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, STEP>,
+    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, STEP, CAT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { trl_set_error("ppo_grad: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_set = true;
   }
-  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, STEP>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d, t);
+  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, STEP, CAT>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d, t);
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
@@ -1455,6 +1559,14 @@ static int launch_ppo(const PpoDev& d, const StepDev* t, hipStream_t s) {
   static const StepDev none{};
   if (t) return (d.N % 16 == 0) ? launch_ppo_v<D, H, A, ACT, true, RT, true>(d, *t, s) : launch_ppo_v<D, H, A, ACT, false, RT, true>(d, *t, s);
   return (d.N % 16 == 0) ? launch_ppo_v<D, H, A, ACT, true, RT, false>(d, none, s) : launch_ppo_v<D, H, A, ACT, false, RT, false>(d, none, s);
+}
+
+// categorical head: the two-launch sequence only (no STEP instantiation)
+template <int D, int ACT>
+static int launch_ppo_cat(const PpoDev& d, hipStream_t s) {
+  static const StepDev none{};
+  return (d.N % 16 == 0) ? launch_ppo_v<D, 64, 8, ACT, true, true, false, true>(d, none, s)
+                         : launch_ppo_v<D, 64, 8, ACT, false, true, false, true>(d, none, s);
 }
 
 // Policy / value split of the grid.  A policy tile costs more than a value tile (head, log-prob loss,
@@ -1479,8 +1591,13 @@ extern "C" int trl_ppo_wg_split(int D, int H, int A, int n_tiles, int n_wg) {
 // as separate, concurrent launch sequences)
 static int resolve_pf_wgs(int n_wg, int n_wg_pf) { return n_wg_pf < 0 ? 0 : (n_wg_pf > 0 ? n_wg_pf : n_wg / 2); }
 
-static int ppo_grad_launch(const trl_ppo_batch_t* p, const StepDev* step, void* stream) {
+static int ppo_grad_launch(const trl_ppo_batch_t* p, const StepDev* step, void* stream, bool cat = false) {
   if (!p) { trl_set_error("ppo_grad: null descriptor"); return TRL_EINVAL; }
+  if (cat && !trl_ppo_cat_supported(p->D, p->H, p->A, p->act)) {
+    trl_set_error("ppo_cat_grad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU)",
+                  p->D, p->H, p->A, p->act);
+    return TRL_EUNSUPPORTED;
+  }
   TRL_REQUIRE(p->obs && p->acts && p->advs && p->rets, "null rollout tensor");
   TRL_REQUIRE(p->loss_mode == TRL_LOSS_PPO_CLIP || p->loss_mode == TRL_LOSS_A2C, "unknown loss_mode");
   TRL_REQUIRE(p->loss_mode == TRL_LOSS_A2C || p->old_logp, "the clipped surrogate needs old_logp");
@@ -1495,7 +1612,7 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, const StepDev* step, void* 
   const int D = p->D, H = p->H, A = p->A;
   TRL_REQUIRE(((uintptr_t)p->partial & 15) == 0 && (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 3) == 0,
               "partial rows must be 16-byte aligned, parameter blocks 4-byte aligned");
-  TRL_REQUIRE(!SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
+  TRL_REQUIRE(cat || !SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
               "parameter blocks of the benchmark shape must be 16-byte aligned");
   PpoDev d;
   d.obs = p->obs; d.acts = p->acts; d.advs = p->advs; d.rets = p->rets; d.old_values = p->old_values;
@@ -1507,6 +1624,12 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, const StepDev* step, void* 
   d.n_pf = resolve_pf_wgs(p->n_wg, p->n_wg_pf);
   d.D = D; d.A = A;
   hipStream_t s = (hipStream_t)stream;
+  if (cat) {                                          // actual dims at run time inside the 17- / 32-feature tile; acts is (rows, N, 1)
+    d.p_stride = trl_ppo_cat_partial_stride(D, H, A);
+    d.tanh_action = 0;
+    if (D <= 17) return p->act == TRL_ACT_TANH ? launch_ppo_cat<17, TRL_ACT_TANH>(d, s) : launch_ppo_cat<17, TRL_ACT_RELU>(d, s);
+    return p->act == TRL_ACT_TANH ? launch_ppo_cat<32, TRL_ACT_TANH>(d, s) : launch_ppo_cat<32, TRL_ACT_RELU>(d, s);
+  }
   if (SHAPE_IS(17, 64, 6)) {
     d.p_stride = PpoShape<17, 64, 6>::P_STRIDE;
     if (p->act == TRL_ACT_TANH) return launch_ppo<17, 64, 6, TRL_ACT_TANH, false>(d, step, s);
@@ -1525,19 +1648,38 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, const StepDev* step, void* 
 }
 
 extern "C" int trl_ppo_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, nullptr, stream); }
+// The same launch for a categorical policy (2 <= A <= 8 logits): acts is (rows, N, 1) -- the action index as a float --,
+// pf_params is [W1 b1 W2 b2 W3 b3], tanh_action is ignored, partial rows are trl_ppo_cat_partial_stride floats and the
+// policy workgroups' scalar rows carry the entropy sum in their eighth column (trl_ppo_cat_reduce_*_f32 fold it).
+extern "C" int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, nullptr, stream, true); }
 
-extern "C" int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
-                                  int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
+static int launch_reduce(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                         const float* pf_params, float* grads, double* info, void* stream, bool cat) {
   TRL_REQUIRE(partial && scal_partial && grads && info, "null pointer");
   TRL_REQUIRE(n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg, "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
-  const int ps = trl_ppo_partial_stride(D, H, A);
+  const int ps = ppo_stride_for(D, H, A, cat);
   if (ps < 0) return ps;
-  const int p_pf = H * D + H + H * H + H + A * H + A + A, p_vf = H * D + H + H * H + H + H + 1;
-  hipLaunchKernelGGL(ppo_reduce_kernel, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                     partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
-                     pf_params ? pf_params + (p_pf - A) : (const float*)nullptr, A, grads, info);
+  const int p_pf = ppo_p_pf(D, H, A, cat), p_vf = ppo_p_vf(D, H);
+  if (cat)                                            // no logstd tail: nothing of it is folded, the entropy column is
+    hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
+                       (const float*)nullptr, A, grads, info);
+  else
+    hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
+                       pf_params ? pf_params + (p_pf - A) : (const float*)nullptr, A, grads, info);
   TRL_LAUNCH_CHECK();
   return TRL_OK;
+}
+extern "C" int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
+                                  int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, false);
+}
+// categorical head: pf_params is accepted for symmetry and not read (there is no logstd); info[20] = entropy sum
+extern "C" int trl_ppo_cat_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
+                                      int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
+  (void)pf_params;
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, true);
 }
 
 static int fill_adam(const trl_adam_t* p, AdamDev& d) {
@@ -1572,15 +1714,15 @@ extern "C" int trl_ppo_reduce_adam_workspace(int D, int H, int A) {
 
 static int launch_reduce_adam(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
                               float* grads, double* info, const trl_adam_t* adam, float* workspace, const XrArgs* xr,
-                              int max_blocks, void* stream, int only_net = -1) {
+                              int max_blocks, void* stream, int only_net = -1, bool cat = false) {
   TRL_REQUIRE(partial && scal_partial && grads && info && workspace, "null pointer");
   TRL_REQUIRE(only_net >= 0 ? n_wg >= 1 : (n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg), "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
-  const int ps = trl_ppo_partial_stride(D, H, A);
+  const int ps = ppo_stride_for(D, H, A, cat);
   if (ps < 0) return ps;
   AdamDev d;
   int rc = fill_adam(adam, d);
   if (rc) return rc;
-  const int p_pf = H * D + H + H * H + H + A * H + A + A, p_vf = H * D + H + H * H + H + H + 1;
+  const int p_pf = ppo_p_pf(D, H, A, cat), p_vf = ppo_p_vf(D, H);
   TRL_REQUIRE(adam->n_groups == 2 && adam->group_sizes[0] == p_pf && adam->group_sizes[1] == p_vf,
               "optimiser groups must be [policy | value] of this shape");
   TRL_REQUIRE(adam->grads == grads, "adam->grads must be the reduce output");
@@ -1592,6 +1734,18 @@ static int launch_reduce_adam(const float* partial, const double* scal_partial, 
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
   const int n_pf = only_net == 0 ? n_wg : (only_net == 1 ? 0 : resolve_pf_wgs(n_wg, n_wg_pf));
   const int jobs = (only_net >= 0 ? 1 : 2) * trl_ceil_div(ps, RED_CHUNK);
+  if (cat) {                                          // no logstd pointer: its statistics do not exist; wave 3 folds the entropy column
+    if (grid == jobs)
+      hipLaunchKernelGGL((ppo_reduce_adam_kernel<false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
+                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
+    else
+      hipLaunchKernelGGL((ppo_reduce_adam_kernel<true, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
+                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+  }
   if (grid == jobs)
     hipLaunchKernelGGL(ppo_reduce_adam_kernel<false>, dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
                        partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf,
@@ -1622,6 +1776,25 @@ extern "C" int trl_ppo_reduce_adam_net_f32(const float* partial, const double* s
                                            float* workspace, void* stream) {
   TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
   return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net);
+}
+
+// The categorical head's folds (rows of trl_ppo_cat_minibatch_grad_f32; same row fold order, norm rendezvous and Adam
+// arithmetic; optimiser groups [policy without logstd | value]).  The cross-rank variants do not exist for this head.
+extern "C" int trl_ppo_cat_reduce_adam_workspace(int D, int H, int A) {
+  const int ps = trl_ppo_cat_partial_stride(D, H, A);
+  if (ps < 0) return ps;
+  return 16 + 4 * trl_ceil_div(ps, RED_CHUNK);
+}
+extern "C" int trl_ppo_cat_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                                           int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
+                                           float* workspace, void* stream) {
+  return launch_reduce_adam(partial, scal_partial, n_wg, n_wg_pf, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, -1, true);
+}
+extern "C" int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,
+                                               int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
+                                               float* workspace, void* stream) {
+  TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
+  return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net, true);
 }
 
 // Env shards on several ranks: the same launch with the gradient SUM over ranks between the fold and the clip
