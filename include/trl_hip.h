@@ -411,20 +411,6 @@ int trl_ppo_reduce_adam_f32(const float* partial, const double* scal_partial, in
                             int D, int H, int A, float* grads, double* info,
                             const trl_adam_t* adam, float* workspace, void* stream);
 
-/* The whole minibatch step of ONE process as ONE launch: trl_ppo_minibatch_grad_f32 followed, inside the same launch, by
- * what trl_ppo_reduce_adam_f32 does (PPO.update's backward, clip_grad_norm_ and optimizer.step of both networks,
- * torchrl/algo/on_policy/ppo.py:67-75, 113-122) -- the workgroups of the gradient grid meet through device-scope flags,
- * fold the partial rows in trl_ppo_reduce_f32's order and step their own 64 parameters; results are bit-identical to the
- * two-launch sequence.  args->n_wg must not exceed trl_ppo_step_max_workgroups() (every workgroup has to be resident at
- * once: TRL_EUNSUPPORTED otherwise -- use the two launches), adam->params / + P_pf must be args->pf_params / vf_params,
- * adam->grads == grads.  workspace: trl_ppo_step_workspace(D, H, A) floats, zeroed once; it begins with
- * trl_ppo_reduce_adam_f32's workspace (same Adam header), so both routes may be used on it in turn.  A rendezvous that does
- * not complete within ~2 s sets workspace word 0 and info[23] and leaves the parameters untouched. */
-int trl_ppo_step_workspace(int D, int H, int A);
-int trl_ppo_step_max_workgroups(void);
-int trl_ppo_minibatch_step_f32(const trl_ppo_batch_t* args, float* grads, double* info, const trl_adam_t* adam,
-                               float* workspace, void* stream);
-
 /* One network's half of trl_ppo_reduce_adam_f32: the n_wg rows of `partial` / `scal_partial` come from a single-network
  * gradient launch (trl_ppo_batch_t.n_wg_pf = n_wg: net 0, the policy; n_wg_pf = -1: net 1, the value function); folds them,
  * clips that group by its own norm and takes its Adam step (adam: the two-group descriptor; only group `net` is stepped,
@@ -446,7 +432,7 @@ int trl_ppo_reduce_adam_net_f32(const float* partial, const double* scal_partial
  * [policy without logstd | value]; info[20] receives the entropy sum of the local samples and info[8..11] / [16..19] are
  * written as zero.  Same row fold order, norm rendezvous and Adam arithmetic: a single-network launch folded by
  * trl_ppo_cat_reduce_adam_net_f32 gives the bits of the joint launch + trl_ppo_cat_reduce_adam_f32.  There is no cross-rank
- * variant and no one-launch step for this head. */
+ * variant for this head. */
 int trl_ppo_cat_supported(int D, int H, int A, int act);
 int trl_ppo_cat_partial_stride(int D, int H, int A);
 int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* args, void* stream);

@@ -43,7 +43,7 @@ def g():
 
 @pytest.fixture(autouse=True)
 def _clean_env(monkeypatch):
-    for k in ("TRL_GENERIC_PPO", "TRL_PPO_CHAINS", "TRL_PPO_STEP", "TRL_NO_GRAPH", "TRL_NO_RT_ROLLOUT", SWITCH,
+    for k in ("TRL_GENERIC_PPO", "TRL_PPO_CHAINS", "TRL_NO_GRAPH", "TRL_NO_RT_ROLLOUT", SWITCH,
               "TRL_CAT_FUSED_ROLLOUT"):
         monkeypatch.delenv(k, raising=False)
 
@@ -361,16 +361,15 @@ def test_fused_engine_vs_generic_engine(c, monkeypatch, errlog):
 
 
 # ---------------------------------------------------------------- 5. engine modes
-def run_mode(x, old_logp, chains, monkeypatch, step="split"):
+def run_mode(x, old_logp, chains, monkeypatch):
     from torchrl_amd.algo import PPO
     monkeypatch.setenv(SWITCH, "1")
     monkeypatch.setenv("TRL_PPO_CHAINS", chains)
-    monkeypatch.setenv("TRL_PPO_STEP", step)
     pf, vf = cu.nets_of(x["D"], x["A"], x["seed"])
     agent = make_agent(PPO, pf, vf, x["D"], x["A"], cu.ENGINE_ROWS_MB * cu.ENGINE_N, plr=3e-4, vlr=1e-3, clip_para=cu.CLIP,
                        opt_epochs=1, entropy_coeff=cu.C_ENT)
     eng = agent.engine()
-    assert is_fused(eng) and eng.two_chains == (chains == "two") and not eng.one_launch
+    assert is_fused(eng) and eng.two_chains == (chains == "two")
     t = engine_tensors(x, old_logp)
     out = []
     for e in range(3):                                                        # eager, captured, replayed
@@ -391,9 +390,8 @@ def test_engine_modes_are_bit_identical_and_deterministic(monkeypatch):
     assert _C.eager_fallback_count() == before                                # kernels only, whole epochs
     joint = run_mode(x, old_logp, "joint", monkeypatch)
     again = run_mode(x, old_logp, "two", monkeypatch)
-    fused_switch = run_mode(x, old_logp, "joint", monkeypatch, step="fused")  # no one-launch step for this head: the split sequence
     assert _C.eager_fallback_count() == before
-    for other in (joint, again, fused_switch):
+    for other in (joint, again):
         for e, ((p0, m0, v0, i0), (p1, m1, v1, i1)) in enumerate(zip(two, other)):
             assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(v0, v1), e
             assert len(i0) == len(i1) and all(a == b for a, b in zip(i0, i1)), e

@@ -534,7 +534,7 @@ def test_epoch_prologue_equals_adv_stats_and_does_its_side_jobs(n_mb, rows_mb, N
     torch.testing.assert_close(got[:, 1], (a64 * a64).sum((1, 2)), rtol=1e-12, atol=1e-9)
 
 
-# ------------------------------------------------------------------ the whole minibatch step as one launch
+# ------------------------------------------------------------------ the minibatch step, one network per launch
 def _step_fixture(D, A, T, N, seed):
     gen = torch.Generator().manual_seed(seed)
     pf, vf = nets.init_mlp(D, [64, 64], A, generator=gen), nets.init_mlp(D, [64, 64], 1, generator=gen)
@@ -545,115 +545,15 @@ def _step_fixture(D, A, T, N, seed):
     return pf, ls, vf, {k: dev(v) for k, v in full.items()}
 
 
-@pytest.mark.parametrize("D,A,N,n_wg,n_pf,device_state", [
-    (17, 6, 64, 2, 0, 0), (17, 6, 64, 8, 3, 1), (17, 6, 48, 64, 0, 1), (17, 6, 21, 6, 0, 0),
-    (17, 6, 256, 256, 147, 1), (11, 3, 32, 16, 0, 1), (27, 8, 32, 250, 130, 0)])
-def test_one_launch_step_is_the_two_launch_sequence_bit_for_bit(D, A, N, n_wg, n_pf, device_state):
-    """trl_ppo_minibatch_step_f32 (gradient, fold, clip, Adam: one launch, workgroups meeting inside it) against
-    trl_ppo_minibatch_grad_f32 + trl_ppo_reduce_adam_f32 (ppo.py:67-75, 113-122): parameters, Adam moments, folded
-    gradient, the 24 statistics and both norms bit for bit over three consecutive steps -- small grids (one workgroup
-    owning many fold jobs), the full 256-workgroup grid, ragged N, runtime-dims tiles, host- and device-side step count."""
-    from torchrl_amd import _C
-    lib = _C.lib()
-    T, rows_mb = 8, 4
-    pf, ls, vf, buf = _step_fixture(D, A, T, N, seed=D * 100 + n_wg)
-    if n_wg > lib.trl_ppo_step_max_workgroups():
-        pytest.skip("%d workgroups are not co-resident on this device" % n_wg)
-    P_pf, P_vf = 64 * D + 64 + 64 * 64 + 64 + A * 64 + 2 * A, 64 * D + 64 + 64 * 64 + 64 + 64 + 1
-    ps = _C.ppo_partial_stride(D, 64, A)
-    idx = torch.as_tensor(np.random.RandomState(1).permutation(T)[:rows_mb].astype(np.int64)).to(DEV)
-    raw = torch.zeros(1, 4, dtype=torch.float64, device=DEV)
-    _C.adv_stats(buf["advs"].reshape(T, N), idx.reshape(1, -1), raw)
-    stream = _C.stream_ptr(torch.device(DEV))
-    results = []
-    for one_launch in (False, True):
-        params = torch.cat([flat(pf, ls), flat(vf)]).contiguous()
-        assert params.numel() == P_pf + P_vf
-        m, v, grads = torch.zeros_like(params), torch.zeros_like(params), torch.zeros_like(params)
-        partial = torch.zeros(n_wg, ps, device=DEV)
-        scal = torch.zeros(n_wg, 8, dtype=torch.float64, device=DEV)
-        ws = torch.zeros(lib.trl_ppo_step_workspace(D, 64, A), device=DEV)
-        ws[4:8].view(torch.float64).fill_(1.0)
-        ws[2:4] = torch.tensor([3e-4, 1e-3])
-        infos, norms = torch.zeros(3, 24, dtype=torch.float64, device=DEV), torch.zeros(3, 2, device=DEV)
-        g = _C.PpoBatchArgs()
-        for k, name in (("obs", "obs"), ("acts", "acts"), ("advs", "advs"), ("rets", "estimate_returns"),
-                        ("old_values", "values"), ("old_logp", "old_logp")):
-            setattr(g, k, buf[name].data_ptr())
-        g.row_idx, g.rows_mb, g.N = idx.data_ptr(), rows_mb, N
-        g.adv_raw, g.n_global = raw.data_ptr(), float(rows_mb * N)
-        g.pf_params, g.vf_params = params.data_ptr(), params.data_ptr() + 4 * P_pf
-        g.D, g.H, g.A, g.act = D, 64, A, _C.ACT_TANH
-        g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = 0.2, 0.005, 1, 1
-        g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = partial.data_ptr(), scal.data_ptr(), n_wg, n_pf
-        a = _C.AdamArgs()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr()
-        a.n_groups = 2
-        a.group_sizes[0], a.group_sizes[1] = P_pf, P_vf
-        a.group_lr[0], a.group_lr[1] = 3e-4, 1e-3
-        a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-        a.device_state = device_state
-        for k in range(3):
-            a.step_count, a.norms_out = k + 1, norms[k].data_ptr()
-            if one_launch:
-                _C.check(lib.trl_ppo_minibatch_step_f32(C.byref(g), grads.data_ptr(), infos[k].data_ptr(), C.byref(a),
-                                                        ws.data_ptr(), stream), "trl_ppo_minibatch_step_f32")
-            else:
-                _C.check(lib.trl_ppo_minibatch_grad_f32(C.byref(g), stream), "trl_ppo_minibatch_grad_f32")
-                _C.check(lib.trl_ppo_reduce_adam_f32(partial.data_ptr(), scal.data_ptr(), n_wg, n_pf, D, 64, A, grads.data_ptr(),
-                                                     infos[k].data_ptr(), C.byref(a), ws.data_ptr(), stream),
-                         "trl_ppo_reduce_adam_f32")
-        torch.cuda.synchronize()
-        assert int(ws[:1].view(torch.int32).item()) == 0, "a rendezvous timed out"
-        if device_state:
-            assert int(ws[:2].view(torch.int32)[1].item()) == 3
-        results.append([x.cpu() for x in (params, m, v, grads, infos, norms)])
-    assert not torch.equal(results[0][0], torch.cat([flat(pf, ls), flat(vf)]).cpu()), "the steps moved nothing"
-    for name, x, y in zip(("params", "exp_avg", "exp_avg_sq", "grads", "info", "norms"), *results):
-        assert torch.equal(torch.nan_to_num(x, nan=-7.0), torch.nan_to_num(y, nan=-7.0)), name
-    assert float(results[1][4][:, 23].abs().sum()) == 0.0
-
-
-def test_one_launch_step_refuses_grids_that_cannot_be_resident():
-    from torchrl_amd import _C
-    lib = _C.lib()
-    cap = lib.trl_ppo_step_max_workgroups()
-    assert 0 < cap <= 256
-    pf, ls, vf, buf = _step_fixture(17, 6, 8, 16, seed=3)
-    params = torch.cat([flat(pf, ls), flat(vf)]).contiguous()
-    before = params.clone()
-    n_wg = cap + 2
-    g = _C.PpoBatchArgs()
-    for k, name in (("obs", "obs"), ("acts", "acts"), ("advs", "advs"), ("rets", "estimate_returns"),
-                    ("old_values", "values"), ("old_logp", "old_logp")):
-        setattr(g, k, buf[name].data_ptr())
-    raw = torch.zeros(1, 4, dtype=torch.float64, device=DEV)
-    partial = torch.zeros(n_wg, _C.ppo_partial_stride(17, 64, 6), device=DEV)
-    scal = torch.zeros(n_wg, 8, dtype=torch.float64, device=DEV)
-    g.row_idx, g.rows_mb, g.N, g.adv_raw, g.n_global = None, 8, 16, raw.data_ptr(), 128.0
-    g.pf_params, g.vf_params = params.data_ptr(), params.data_ptr() + 4 * 5708
-    g.D, g.H, g.A, g.act, g.tanh_action = 17, 64, 6, _C.ACT_TANH, 1
-    g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = partial.data_ptr(), scal.data_ptr(), n_wg, 0
-    m, v, grads = torch.zeros_like(params), torch.zeros_like(params), torch.zeros_like(params)
-    a = _C.AdamArgs()
-    a.params, a.grads, a.exp_avg, a.exp_avg_sq = params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr()
-    a.n_groups, a.step_count, a.grad_scale = 2, 1, 1.0
-    a.group_sizes[0], a.group_sizes[1] = 5708, 5377
-    ws = torch.zeros(lib.trl_ppo_step_workspace(17, 64, 6), device=DEV)
-    info = torch.zeros(24, dtype=torch.float64, device=DEV)
-    rc = lib.trl_ppo_minibatch_step_f32(C.byref(g), grads.data_ptr(), info.data_ptr(), C.byref(a), ws.data_ptr(),
-                                        _C.stream_ptr(torch.device(DEV)))
-    assert rc == -2 and b"co-resident" in lib.trl_last_error()      # TRL_EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(params, before)
-
-
-@pytest.mark.parametrize("D,A,N,n_wg,n_pf", [(17, 6, 64, 8, 3), (17, 6, 256, 256, 147), (11, 3, 21, 6, 2), (27, 8, 32, 16, 9)])
+@pytest.mark.parametrize("D,A,N,n_wg,n_pf", [(17, 6, 64, 8, 3), (17, 6, 256, 256, 147), (11, 3, 21, 6, 2), (27, 8, 32, 16, 9),
+                                             (17, 6, 21, 6, 3), (27, 8, 32, 250, 130)])
 def test_one_network_per_launch_is_the_joint_sequence_bit_for_bit(D, A, N, n_wg, n_pf):
     """The critic's and the actor's halves of an update as separate launches (trl_ppo_batch_t.n_wg_pf = n_wg / -1,
     trl_ppo_reduce_adam_net_f32, each with its own workspace) against the joint launches of the same split
     (ppo.py:93-122 / 41-91 touch disjoint networks, optimisers and statistics): parameters, Adam moments, folded gradient,
-    statistics and norms bit for bit over three steps, whichever half is launched first."""
+    statistics and norms bit for bit over three steps, whichever half is launched first -- small grids, the full
+    256-workgroup grid, the compile-time shape with a ragged env count, both runtime-dims tiles, and a near-full grid with
+    more workgroups than tiles."""
     from torchrl_amd import _C
     lib = _C.lib()
     T, rows_mb = 8, 4

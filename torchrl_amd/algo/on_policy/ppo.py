@@ -169,17 +169,9 @@ class _FusedPPO:
         self.max_wg = 2 * max(1, self.n_cu // 2)
         self.partial = torch.zeros(self.max_wg, self.p_stride, device=self.dev)
         self.scal = torch.zeros(self.max_wg, 8, dtype=torch.float64, device=self.dev)
-        n_ws = lib.trl_ppo_cat_reduce_adam_workspace(self.D, self.H, self.A) if self.categorical else \
-            lib.trl_ppo_step_workspace(self.D, self.H, self.A)         # (begins with trl_ppo_reduce_adam_f32's workspace)
-        self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + flags / norm granules of the fused step
-        # TRL_PPO_STEP=fused (opt-in): the whole minibatch step as ONE launch (trl_ppo_minibatch_step_f32 -- its workgroups
-        # meet inside the launch, so the grid must be resident at once; one process per device).  Same bits as the default
-        # two-launch sequence (gradient, then fold / clip / Adam), and on MI355X 4 us per step SLOWER: rows that cross XCDs
-        # inside a launch must be written through to the coherence point and every dependent hop costs 2.2-2.6 us, which is
-        # what a graph-captured launch boundary costs too (profiles/NOTES_r06.md).
-        # (a categorical policy has no one-launch instantiation: it takes the split sequence whatever the switch says)
-        self.one_launch = os.environ.get("TRL_PPO_STEP", "split") == "fused" and not self.categorical
-        self.step_max_wg = _C.lib().trl_ppo_step_max_workgroups()
+        n_ws = (lib.trl_ppo_cat_reduce_adam_workspace if self.categorical else lib.trl_ppo_reduce_adam_workspace)(
+            self.D, self.H, self.A)
+        self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + norm granules of the fold / clip / Adam launch
         # One process: the critic's and the actor's updates of an epoch (ppo.py:93-122 / 41-91: separate networks, optimisers,
         # clips and statistics) run as TWO launch sequences on two streams (`_run_chains`); TRL_PPO_CHAINS=joint keeps the
         # single sequence in which every gradient launch carries both networks.  Same bits either way.
@@ -287,11 +279,10 @@ class _FusedPPO:
         fused = not dist.collectives_active()
         if self.categorical and not fused:
             raise _C.TrlError("the fused categorical update runs on one rank (no cross-rank fold exists for this head)")
-        one_launch = fused and self.one_launch and n_wg <= self.step_max_wg
         # (env shards on several ranks: the two chains need the in-launch gradient exchange of the peer transport, whose
         # granules and exchange counts are per network; over all-reduce CALLS the joint sequence stays)
         xrank_chains = not fused and self.chains_across_ranks()
-        if (fused or xrank_chains) and not one_launch and probe is None and self.two_chains and n_wg_pf >= 1 and n_wg - n_wg_pf >= 1:
+        if (fused or xrank_chains) and probe is None and self.two_chains and n_wg_pf >= 1 and n_wg - n_wg_pf >= 1:
             return self._run_chains(t, row_idx, N, pre, pre_key, defer, n_wg, n_wg_pf, loss_mode, n_global, xrank=not fused)
         for last in [self._pending] + list(self._chain_pend):
             if last is not None:                                       # its statistics still sit in the host twin this
@@ -335,7 +326,7 @@ class _FusedPPO:
         hyper = (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
                  int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
         use_graph = (fused or xrank or graph_coll) and probe is None and os.environ.get("TRL_NO_GRAPH") != "1"
-        key = (n_wg, n_wg_pf, loss_mode, n_global, rows_total, N, pre_key, pre is not None, xrank, in_place, one_launch) + hyper + tuple(
+        key = (n_wg, n_wg_pf, loss_mode, n_global, rows_total, N, pre_key, pre is not None, xrank, in_place) + hyper + tuple(
             0 if t.get(k) is None else t[k].data_ptr() for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"))
 
         def launch_all():
@@ -381,14 +372,6 @@ class _FusedPPO:
                 if probe is not None:
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                     ev[0].record()
-                if one_launch:                                         # gradient + fold + clip + Adam: one launch
-                    _C.check(lib.trl_ppo_minibatch_step_f32(C.byref(g), self.grads.data_ptr(), info_base + 192 * k,
-                                                            C.byref(a), self.red_ws.data_ptr(), stream),
-                             "trl_ppo_minibatch_step_f32")
-                    if probe is not None:
-                        ev[1].record()
-                        probe.append(ev)
-                    continue
                 _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
                 if probe is not None:
                     ev[1].record()
@@ -437,10 +420,6 @@ class _FusedPPO:
         def build(host):
             if xrank:
                 dist.check_comm(peek=True)                             # a rank that never delivered: raise, do not hang
-            if one_launch and host[4 * K:28 * K].view(K, 24)[:, 23].any():
-                raise _C.TrlError("trl_ppo_minibatch_step_f32: the in-launch rendezvous of a minibatch step timed out (its "
-                                  "workgroups were not resident together -- is another process using this GPU?); the "
-                                  "parameters of that step were left untouched.  TRL_PPO_STEP=split uses two launches.")
             return make(host[:4 * K].view(K, 4).numpy(), host[4 * K:28 * K].view(K, 24).numpy(),
                         host[28 * K:].view(torch.float32).view(K, 2).numpy(), n_global)
         pending = _PendingInfos(K, landed, host, build)
