@@ -278,7 +278,7 @@ int trl_ppo_minibatch_grad_f32(const trl_ppo_batch_t* args, void* stream);
  *  8..11 mean / unbiased std / max / min of the clamped logstd (ppo.py:82-85)
  *  12..15 sum / sum of squares / max / -min of the value prediction (a2c.py:89-92)
  *  16..19 mean / unbiased std over the A dims / max / min of std = exp(clamped logstd) (a2c.py:95-100)
- *  20 categorical heads: entropy sum (trl_cat_losses_f32)   21..23 unused
+ *  20 categorical and state-dependent-std heads: entropy sum (trl_cat_losses_f32, trl_gauss_sd_losses_f32)   21..23 unused
  * pf_params may be NULL (then 8..11 are left untouched). */
 int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
                        int D, int H, int A, const float* pf_params, float* grads, double* info,
@@ -312,6 +312,20 @@ int trl_cat_losses_f32(const float* logits, const float* acts, const float* advs
                        const float* rets, const float* v_old, const double* adv_raw, double n_global, int B, int A,
                        float clip_para, float entropy_coeff, int clipped_value_loss, int loss_mode, float* d_logits,
                        float* d_v, double* info, double* workspace, void* stream);
+/* The same for a state-dependent-std Gaussian head (GuassianContPolicy, continuous_policy.py:156-170): head (B, 2A) =
+ * [mean | raw log_std], 1 <= A <= 32, ls = clamp(head[A + o], -20, 2) per sample, acts (B, A).  log pi is
+ * trl_gauss_sd_logp_f32's (bit for bit), the entropy sum_o (1/2 + 1/2 log 2 pi + ls) (continuous_policy.py:142-143); advantage
+ * normalisation, ratio, clip, tie convention and value loss exactly as trl_ppo_generic_losses_f32 (shared helpers);
+ *   d_head[b, o]     = g_lp zc / var                      zc = [atanh](act) - mean, var = exp(2 ls)
+ *   d_head[b, A + o] = gate (g_lp (zc^2 / var - 1) - entropy_coeff / n_global),  gate = 1 where the raw value lies in [-20, 2].
+ * info: the same 24 slots; 8..11 mean / unbiased std / max / min of ls over all B * A elements (ppo.py:83-86), 16..19 the
+ * same of std = exp(ls) (a2c.py:96-101), 20 the entropy SUM over the local samples.
+ * workspace: trl_gauss_sd_losses_workspace(B, A) doubles. */
+int trl_gauss_sd_losses_workspace(int B, int A);
+int trl_gauss_sd_losses_f32(const float* head, const float* acts, const float* advs, const float* old_logp, const float* v,
+                            const float* rets, const float* v_old, const double* adv_raw, double n_global, int B, int A,
+                            float clip_para, float entropy_coeff, int clipped_value_loss, int tanh_action, int loss_mode,
+                            float* d_head, float* d_v, double* info, double* workspace, void* stream);
 
 /* --- V-MPO: the loss half of VMPO.update (torchrl/algo/on_policy/v_mpo.py:57-181) ----------------------
  * trl_adv_normalize_f32: out = (adv - mean) / (std_unbiased + eps) from trl_adv_stats_f64's {sum, sumsq, ..} (:175-177;
@@ -916,6 +930,17 @@ int trl_frame_stream_gather_u8(const uint8_t* stream, const int32_t* pos, const 
  *                      (torchrl/collector/base.py:220-224), straight from the reset mask */
 int trl_gauss_explore_f32(const float* mean, const float* logstd, const float* eps, float* act, float* logp,
                           int N, int A, int tanh_action, void* stream);
+/* The state-dependent-std counterpart of trl_gauss_explore_f32 (GuassianContPolicy.explore, continuous_policy.py:92-131,
+ * 156-170): head (N, 2A) = [mean | raw log_std], 1 <= A <= 32, ls = clamp(head[A + o], -20, 2);
+ * act (N, A) = [tanh](mean + exp(ls) * eps), logp (N, nullable) = log pi(act).  eps (N, A) NULL: the deterministic action
+ * [tanh](mean) (eval_act, :78-83). */
+int trl_gauss_sd_explore_f32(const float* head, const float* eps, float* act, float* logp, int N, int A, int tanh_action,
+                             void* stream);
+/* log pi(a) (B, nullable) and the entropy sum_o (1/2 + 1/2 log 2 pi + ls) (B, nullable) of (head (B, 2A), acts (B, A)) pairs:
+ * GuassianContPolicyBase.update's log_prob.sum(-1) / ent.sum(-1) (continuous_policy.py:134-153, distribution.py:33-45) with
+ * trl_gauss_sd_explore_f32's arithmetic, so log pi and log pi_old of the same (s, a, parameters) are bit-identical. */
+int trl_gauss_sd_logp_f32(const float* head, const float* acts, float* logp, float* ent, int B, int A, int tanh_action,
+                          void* stream);
 /* The categorical counterpart of trl_gauss_explore_f32 (CategoricalDisPolicy.explore, discrete_policies.py:136-150):
  * logits (N, A), 2 <= A <= 64 -> act (N, 1) holding the integer action as a float, logp (N, nullable) = log pi(a),
  * onehot (N, A, nullable).  m = max_k l_k, e_k = exp(l_k - m), S = sum e_k and the prefix sums in ascending k (fp32); the

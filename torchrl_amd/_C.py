@@ -286,6 +286,11 @@ SIGNATURES = {
     "trl_cat_losses_workspace": (C.c_int, [C.c_int] * 2),
     "trl_cat_losses_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]
                            + [C.c_void_p] * 5),
+    "trl_gauss_sd_losses_workspace": (C.c_int, [C.c_int] * 2),
+    "trl_gauss_sd_losses_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                                             C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "trl_gauss_sd_explore_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "trl_gauss_sd_logp_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_cat_act_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "trl_cat_logp_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
@@ -740,6 +745,69 @@ def cat_losses(logits, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, 
         dev_ptr(d_logits, name="d_logits"), dev_ptr(d_v, name="d_v"), dev_ptr(info, torch.float64, "info"),
         dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(logits.device)), "trl_cat_losses_f32")
     return d_logits, d_v
+
+
+def _gauss_sd_dims(head, what):
+    B, W = int(head.shape[0]), int(head.shape[1])
+    if W % 2 != 0 or not 1 <= W // 2 <= 32:
+        raise TrlError("%s: the head is (B, 2A) = [mean | log_std] with 1 <= A <= 32, got %s" % (what, (B, W)))
+    return B, W // 2
+
+
+def gauss_sd_losses(head, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, clip_para, entropy_coeff,
+                    clipped_value_loss, tanh_action, loss_mode, info, workspace=None):
+    """The loss half of a PPO / A2C minibatch for a state-dependent-std Gaussian head; returns (d_head (B, 2A), d_v (B, 1))."""
+    B, A = _gauss_sd_dims(head, "gauss_sd_losses")
+    need = lib().trl_gauss_sd_losses_workspace(B, A)
+    if need < 0:
+        raise TrlError("gauss_sd_losses: unsupported sizes B=%d A=%d (1 <= A <= 32)" % (B, A))
+    if tuple(acts.shape) != (B, A):
+        raise TrlError("gauss_sd_losses: acts must be (B, A) = %s, got %s" % ((B, A), tuple(acts.shape)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.float64, device=head.device)
+    d_head = torch.empty((B, 2 * A), dtype=torch.float32, device=head.device)
+    d_v = torch.empty((B, 1), dtype=torch.float32, device=head.device)
+    check(lib().trl_gauss_sd_losses_f32(
+        dev_ptr(head, name="head"), dev_ptr(acts, name="acts"), dev_ptr(advs, name="advs"),
+        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v"), dev_ptr(rets, name="rets"),
+        dev_ptr(v_old, name="v_old", allow_none=True), dev_ptr(adv_raw, torch.float64, "adv_raw"), float(n_global), B, A,
+        float(clip_para), float(entropy_coeff), int(bool(clipped_value_loss)), int(bool(tanh_action)), int(loss_mode),
+        dev_ptr(d_head, name="d_head"), dev_ptr(d_v, name="d_v"), dev_ptr(info, torch.float64, "info"),
+        dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(head.device)), "trl_gauss_sd_losses_f32")
+    return d_head, d_v
+
+
+def gauss_sd_explore(head, eps, tanh_action, act=None, logp=None):
+    """One vector step's action half for a state-dependent-std Gaussian policy: (act (N, A), logp (N,)); eps None: the
+    deterministic action [tanh](mean)."""
+    N, A = _gauss_sd_dims(head, "gauss_sd_explore")
+    if act is None:
+        act = torch.empty((N, A), dtype=torch.float32, device=head.device)
+    if logp is None:
+        logp = torch.empty((N,), dtype=torch.float32, device=head.device)
+    if tuple(act.shape) != (N, A) or int(logp.numel()) != N or (eps is not None and tuple(eps.shape) != (N, A)):
+        raise TrlError("gauss_sd_explore: act / eps are (N, A) and logp holds one value per row for a head %s" % ((N, 2 * A),))
+    check(lib().trl_gauss_sd_explore_f32(dev_ptr(head, name="head"), dev_ptr(eps, name="eps", allow_none=True),
+                                         dev_ptr(act, name="act"), dev_ptr(logp, name="logp"), N, A, int(bool(tanh_action)),
+                                         stream_ptr(head.device)), "trl_gauss_sd_explore_f32")
+    return act, logp
+
+
+def gauss_sd_logp(head, acts, tanh_action, out=None, ent=None, want_ent=False):
+    """(log pi(a) (B,), entropy (B,) or None) of stored (head (B, 2A), action (B, A)) pairs."""
+    B, A = _gauss_sd_dims(head, "gauss_sd_logp")
+    if tuple(acts.shape) != (B, A):
+        raise TrlError("gauss_sd_logp: acts must be (B, A) = %s, got %s" % ((B, A), tuple(acts.shape)))
+    if out is None:
+        out = torch.empty((B,), dtype=torch.float32, device=head.device)
+    if ent is None and want_ent:
+        ent = torch.empty((B,), dtype=torch.float32, device=head.device)
+    if int(out.numel()) != B or (ent is not None and int(ent.numel()) != B):
+        raise TrlError("gauss_sd_logp: outputs hold one value per sample")
+    check(lib().trl_gauss_sd_logp_f32(dev_ptr(head, name="head"), dev_ptr(acts, name="acts"), dev_ptr(out, name="out"),
+                                      dev_ptr(ent, name="ent", allow_none=True), B, A, int(bool(tanh_action)),
+                                      stream_ptr(head.device)), "trl_gauss_sd_logp_f32")
+    return out, ent
 
 
 def cat_act(logits, seed=0, counter=0, env_offset=0, u=None, deterministic=False, act=None, logp=None, onehot=None):

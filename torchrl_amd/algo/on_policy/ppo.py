@@ -27,6 +27,7 @@ import torch.optim as optim
 from ... import _C
 from ... import dist
 from ...networks import flatten_into
+from ...policies.continuous_policy import is_state_std
 from .. import utils as atu
 from .a2c import A2C
 
@@ -67,6 +68,13 @@ class PPO(A2C):
             with torch.no_grad():
                 _C.cat_logp(tgt.logits(buf._obs.reshape(rows * n, -1)).contiguous(), buf._acts.reshape(rows * n),
                             out=buf._ensure_key("old_logp", (n, 1)).view(rows * n))
+            return
+        if is_state_std(tgt):                                          # [mean | log_std] head: MLP forward + trl_gauss_sd_logp_f32
+            from ... import ops
+            with torch.no_grad():
+                head, _ = ops.mlp_forward(ops.linear_layers(tgt), buf._obs.reshape(rows * n, -1), ops.act_code(tgt), keep=False)
+                _C.gauss_sd_logp(head, buf._acts.reshape(rows * n, -1), bool(tgt.tanh_action),
+                                 out=buf._ensure_key("old_logp", (n, 1)).view(rows * n))
             return
         with torch.no_grad():                                          # kernels only: MLP forward + trl_gauss_logp_f32
             mean, _, log_std = tgt.forward(buf._obs.reshape(rows * n, -1))
@@ -666,6 +674,15 @@ class _FusedPPO:
                     'ent': ent, 'log_prob': i[1] / n,
                 })
                 continue
+            if getattr(self, "state_std", False):                       # per-element statistics over all n * A values, as logged
+                ent = i[20] / n
+                out.append({
+                    'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
+                    'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15],
+                    'std/mean': i[16], 'std/std': i[17], 'std/max': i[18], 'std/min': i[19],
+                    'ent': ent, 'log_prob': i[1] / n,
+                })
+                continue
             ent = A * _HALF_LOG_2PI_PLUS_HALF + A * i[8]
             std_ss = (i[17] ** 2) * (A - 1) if A > 1 else 0.0            # sum over dims of (std - mean)^2
             out.append({
@@ -683,7 +700,8 @@ class _FusedPPO:
         adv_var = np.maximum((r[:, 1] - r[:, 0] * r[:, 0] / n) / (n - 1), 0.0)
         lp_var = np.maximum((i[:, 2] - i[:, 1] * i[:, 1] / n) / (n - 1), 0.0)
         categorical = getattr(self, "categorical", False)              # entropy: the kernel's sum; no log_std/* keys
-        ent = i[:, 20] / n if categorical else self.A * _HALF_LOG_2PI_PLUS_HALF + self.A * i[:, 8]
+        ent = i[:, 20] / n if (categorical or getattr(self, "state_std", False)) else \
+            self.A * _HALF_LOG_2PI_PLUS_HALF + self.A * i[:, 8]
         cols = (('advs/mean', r[:, 0] / n), ('advs/std', np.sqrt(adv_var)), ('advs/max', r[:, 2]), ('advs/min', -r[:, 3]),
                 ('Training/vf_loss', i[:, 7] / n), ('grad_norm/vf', norms[:, 1].astype(np.float64)),
                 ('Training/policy_loss', i[:, 0] / n - c_ent * ent),
@@ -737,6 +755,8 @@ def make_engine(algo):
                 and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
             return _FusedPPO(algo)
         return _GenericPPO(algo)
+    if is_state_std(pf):                                               # [mean | log_std] head: the generic engine only
+        return _GenericPPO(algo)
     if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
             and os.environ.get("TRL_GENERIC_PPO") != "1":
         return _FusedPPO(algo)
@@ -760,9 +780,20 @@ class _GenericPPO(_FusedPPO):
         pf, vf = algo.pf, algo.vf
         # a categorical head (policies.CategoricalDisPolicy): no logstd in the flat vector, trl_cat_losses_f32 for the loss half
         self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
-        if not self.categorical and not hasattr(pf, "logstd"):
-            raise _C.TrlError("PPO / A2C kernels need a state-independent-std policy (GuassianContPolicyBasicBias) or a "
+        # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; no logstd in the flat
+        # vector either, trl_gauss_sd_losses_f32 for the loss half, `self.A` = half the head's width
+        self.state_std = not self.categorical and is_state_std(pf)
+        if not self.categorical and not self.state_std and not hasattr(pf, "logstd"):
+            raise _C.TrlError("PPO / A2C kernels need a GuassianContPolicyBasicBias, a GuassianContPolicy or a "
                               "CategoricalDisPolicy")
+        if self.state_std:
+            head_w = int(ops.linear_layers(pf)[-1][0].shape[0])
+            if not 1 <= head_w // 2 <= 32:
+                raise _C.TrlError("a state-dependent-std policy emits [mean | log_std] with 1 <= A <= 32 action dimensions, "
+                                  "got a head of %d" % head_w)
+        if self.state_std and dist.collectives_active():
+            raise _C.TrlError("PPO / A2C with a state-dependent-std policy runs on one rank (the per-element log_std "
+                              "statistics have no cross-rank columns)")
         self.dev = next(pf.parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
@@ -770,12 +801,14 @@ class _GenericPPO(_FusedPPO):
         if ops.act_code(vf) != self.act:
             raise _C.TrlError("policy and value network must use the same activation")
         self.pf_layers, self.vf_layers = ops.linear_layers(pf), ops.linear_layers(vf)
-        tail = (lambda net: []) if self.categorical else (lambda net: [net.logstd])
+        tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = [t for wb in self.pf_layers for t in wb] + tail(pf)
         vf_list = [t for wb in self.vf_layers for t in wb]
         self.P_pf = sum(p.numel() for p in pf_list)
         self.P_vf = sum(p.numel() for p in vf_list)
         self.D, self.A = int(self.pf_layers[0][0].shape[1]), int(self.pf_layers[-1][0].shape[0])
+        if self.state_std:
+            self.A //= 2
         self.flat = flatten_into(pf_list + vf_list)                   # [pf | vf], parameters become views
         # nets that are MLP2 blocks hand their own flat view to the fused inference kernel (Net.flat_params): it must
         # be THIS storage, or the first forward after the engine exists would re-home the parameters away from it
@@ -800,7 +833,7 @@ class _GenericPPO(_FusedPPO):
                 gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
                 views.append((gw, gb))
             self.gviews.append(views)
-            if layers is self.pf_layers and not self.categorical:
+            if layers is self.pf_layers and not self.categorical and not self.state_std:
                 self.g_logstd = self.grads[off:off + self.A]; off += self.A
         self.step_state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
         self.lr_dev = torch.zeros(2, device=self.dev)
@@ -854,6 +887,10 @@ class _GenericPPO(_FusedPPO):
                         mean, acts.view(-1), advs.view(-1), None if old_lp is None else old_lp.view(-1), v.view(-1),
                         rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, hyper[0], hyper[1],
                         hyper[2], loss_mode, info[k])
+                elif self.state_std:                                   # `mean` holds the head [mean | log_std]
+                    d_mean, d_v = _C.gauss_sd_losses(
+                        mean, acts, advs.view(-1), None if old_lp is None else old_lp.view(-1), v.view(-1), rets.view(-1),
+                        None if v_old is None else v_old.view(-1), raw[k], n_global, *hyper, info[k])
                 else:
                     d_mean, d_v = _C.ppo_generic_losses(
                         mean, algo.pf.logstd.detach(), acts, advs.view(-1), None if old_lp is None else old_lp.view(-1),

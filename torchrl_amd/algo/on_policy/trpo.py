@@ -28,6 +28,10 @@ class TRPO(A2C):
         if getattr(kwargs.get("pf"), "continuous", True) is False:
             raise _C.TrlError("TRPO with a categorical policy is not built: its Fisher-vector product and line search are "
                               "kernels for the diagonal-Gaussian head; discrete actions run on PPO / A2C")
+        from .ppo import is_state_std
+        if is_state_std(kwargs.get("pf")):
+            raise _C.TrlError("TRPO with a state-dependent-std policy is not built: its Fisher-vector product and line search "
+                              "are kernels for the state-independent logstd; GuassianContPolicy runs on PPO / A2C")
         super().__init__(**kwargs)
         self.max_kl, self.cg_damping, self.cg_iters, self.residual_tol = max_kl, cg_damping, cg_iters, residual_tol
         self.v_opt_times = v_opt_times

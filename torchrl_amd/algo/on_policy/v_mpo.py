@@ -25,6 +25,10 @@ class VMPO(A2C):
         if getattr(pf, "continuous", True) is False:
             raise _C.TrlError("VMPO with a categorical policy is not built: its KL terms are kernels for the "
                               "diagonal-Gaussian head; discrete actions run on PPO / A2C")
+        from .ppo import is_state_std
+        if is_state_std(pf):
+            raise _C.TrlError("VMPO with a state-dependent-std policy is not built: its KL terms are kernels for the "
+                              "state-independent logstd; GuassianContPolicy runs on PPO / A2C")
         self.target_pf = copy.deepcopy(pf)
         super().__init__(pf=pf, **kwargs)
         self.eta_eps, self.alpha_eps = eta_eps, alpha_eps

@@ -294,8 +294,14 @@ class VecOnPolicyCollector(VecCollector):
         # ring's `acts` are (N, 1) indices.  The per-step route uses trl_cat_act_f32 in place of trl_gauss_explore_f32; the
         # persistent rollout has a categorical head for the shapes of trl_rollout_cat_supported (see the end of this method)
         self._cat = getattr(self.pf, "continuous", True) is False and hasattr(self.pf, "logits")
-        if not self._cat and not hasattr(self.pf, "logstd"):
-            raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias and CategoricalDisPolicy policies")
+        # a state-dependent-std Gaussian policy (policies.GuassianContPolicy): the head is [mean | log_std], `_dims[1]` = A is
+        # half its width.  Always the per-step route, with trl_gauss_sd_explore_f32 in place of trl_gauss_explore_f32 on the
+        # same (N, A) noise block; neither the persistent rollout nor the TRL_CAT_* routes apply (`_spec` stays None).
+        from ..policies.continuous_policy import is_state_std
+        self._sd = not self._cat and is_state_std(self.pf)
+        if not self._cat and not self._sd and not hasattr(self.pf, "logstd"):
+            raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias, GuassianContPolicy (an even "
+                              "[mean | log_std] head) and CategoricalDisPolicy policies")
         if self._cat and self.noise_mode != "device":
             raise _C.TrlError("a categorical policy draws its actions from the device Philox stream only "
                               "(noise_mode=\"device\"): the reference samples through torch.multinomial, whose host stream "
@@ -304,7 +310,12 @@ class VecOnPolicyCollector(VecCollector):
         vs = self.vf.mlp2_spec() if hasattr(self.vf, "mlp2_spec") else None
         self._act = ops.act_code(self.pf)
         layers = ops.linear_layers(self.pf)
-        self._dims = (int(layers[0][0].shape[1]), int(layers[-1][0].shape[0]) if self._cat else int(self.pf.logstd.numel()))
+        head_w = int(layers[-1][0].shape[0])
+        self._dims = (int(layers[0][0].shape[1]),
+                      head_w if self._cat else head_w // 2 if self._sd else int(self.pf.logstd.numel()))
+        self._head_w = head_w if (self._cat or self._sd) else self._dims[1]    # what the policy network emits per env
+        if self._sd and not 1 <= self._dims[1] <= 32:
+            raise _C.TrlError("a state-dependent-std policy carries 1 <= A <= 32 action dimensions, got a head of %d" % head_w)
         env_acts = int(getattr(self.env, "action_num", 0) or 0) if self._cat else self.env.act_dim
         if self._cat and not env_acts:
             raise _C.TrlError("a categorical policy needs an env with a Discrete action space")
@@ -326,6 +337,8 @@ class VecOnPolicyCollector(VecCollector):
         roll = pair and bool(lib.trl_rollout_supported(ps[0], ps[1], ps[2], ps[3])) and \
             (bool(mlp2) or os.environ.get("TRL_NO_RT_ROLLOUT") != "1")
         self._spec = ps if (roll and not getattr(self.env, "is_host_env", False)) else None   # ... and the rollout kernel
+        if self._sd:                                                        # per-step route on the dense-layer kernels: the
+            self._spec = self._mlp2 = None                                  # forward the update runs (same bits: ratio == 1)
         if self._cat:
             # the persistent rollout's categorical head (trl_rollout_synth_cat_f32): 64-wide pairs with 2..8 actions on a
             # device env that takes one-hot actions, one rank, no observation normaliser (its kernel is the Gaussian
@@ -516,7 +529,7 @@ class VecOnPolicyCollector(VecCollector):
             N, dev = env.env_nums, env.device
             f = lambda *shape: torch.empty(*shape, device=dev)
             W = 1 if self._cat else A                                       # stored action width
-            sb = self._sb = {"N": N, "mean": f(N, A), "eps": f(N, A), "nxt_raw": f(N, D), "v_next": f(N, 1),
+            sb = self._sb = {"N": N, "mean": f(N, self._head_w), "eps": f(N, A), "nxt_raw": f(N, D), "v_next": f(N, 1),
                              "done": f(N, 1), "any": torch.zeros(1, dtype=torch.int32, device=dev),
                              # rows used when nothing is stored (evaluation)
                              "obs": f(N, D), "next_obs": f(N, D), "acts": f(N, W), "values": f(N, 1), "rewards": f(N, 1),
@@ -539,7 +552,7 @@ class VecOnPolicyCollector(VecCollector):
         else:
             r = sb
         r["obs"].copy_(ob)
-        mean = self._forward(self.pf, ob, A, out=sb["mean"])
+        mean = self._forward(self.pf, ob, self._head_w, out=sb["mean"])
         self._forward(self.vf, ob, 1, out=r["values"])
         if self._cat:
             # `mean` holds the logits.  noise_t: this step's (N,) uniforms drawn up front (captured rollout); None: the
@@ -560,8 +573,11 @@ class VecOnPolicyCollector(VecCollector):
         else:                                                             # this rank's rows of the draw for ALL envs
             make = lambda m, f: _C.philox_normal(torch.empty(m, f, device=env.device), self._noise_seed, self.global_step)
             eps = dist.shard_rows_of_global(make, 1, N, A, env.device)
-        _C.gauss_explore(mean, self.pf.logstd.detach(), eps, bool(self.pf.tanh_action), act=r["acts"],
-                         logp=r["old_logp"].view(N))
+        if self._sd:                                                      # `mean` holds the head [mean | log_std]
+            _C.gauss_sd_explore(mean, eps, bool(self.pf.tanh_action), act=r["acts"], logp=r["old_logp"].view(N))
+        else:
+            _C.gauss_explore(mean, self.pf.logstd.detach(), eps, bool(self.pf.tanh_action), act=r["acts"],
+                             logp=r["old_logp"].view(N))
         return self._step_tail(env, r, sb, nz, r["acts"], store, step, max_frames)
 
     def _step_tail(self, env, r, sb, nz, env_act, store, step, max_frames):

@@ -80,6 +80,17 @@ class GuassianContPolicyBase:
                 "log_prob": lp, "ent": Normal(mean, std).entropy().sum(-1, keepdim=True)}
 
 
+def is_state_std(pf):
+    """Is `pf` a state-dependent-std Gaussian policy for the on-policy kernels (k_gauss_sd.hip): continuous, no `logstd`
+    parameter, and a head of even width that emits [mean | log_std]?  The one test both the on-policy collector and the
+    PPO / A2C engine use.  (Deterministic policies are continuous without a `logstd` too; they have no `explore`-time
+    distribution and are told apart by what they lack: the Gaussian protocol of GuassianContPolicyBase.)"""
+    if getattr(pf, "continuous", None) is not True or hasattr(pf, "logstd") or not isinstance(pf, GuassianContPolicyBase):
+        return False
+    from .. import ops
+    return int(ops.linear_layers(pf)[-1][0].shape[0]) % 2 == 0
+
+
 class GuassianContPolicy(networks.Net, GuassianContPolicyBase):
     """State-dependent std (SAC): head emits [mean | log_std] (continuous_policy.py:156-170)."""
 
@@ -92,6 +103,65 @@ class GuassianContPolicy(networks.Net, GuassianContPolicyBase):
         mean, log_std = super().forward(x).chunk(2, dim=-1)
         log_std = torch.clamp(log_std, LOG_SIG_MIN, LOG_SIG_MAX)
         return mean, torch.exp(log_std), log_std
+
+    # On the GPU without autograd the protocol below runs on k_gauss_sd.hip: the head (N, 2A) = [mean | raw log_std] comes
+    # from the network's forward kernels, actions / log pi / entropy from trl_gauss_sd_explore_f32 / trl_gauss_sd_logp_f32
+    # (the kernels PPO / A2C and the on-policy collector use for this head).  SAC does not come through here: TwinSACQ and
+    # the off-policy collector read `forward` and sample in their own rsample kernels.
+    def _head(self, x):
+        """The raw head (N, 2A) when the kernels apply: a CUDA input of rank <= 2 and no autograd graph wanted."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() <= 2):
+            return None
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return None
+        with torch.no_grad():
+            head = networks.Net.forward(self, x if x.dim() == 2 else x.unsqueeze(0))
+        return head.float().contiguous() if head.shape[-1] % 2 == 0 and head.shape[-1] <= 64 else None
+
+    @staticmethod
+    def _parts(head):
+        mean, log_std = head.chunk(2, dim=-1)
+        log_std = torch.clamp(log_std, LOG_SIG_MIN, LOG_SIG_MAX)
+        return mean, torch.exp(log_std), log_std
+
+    def update(self, obs, actions):
+        head = self._head(obs)
+        if head is None or obs.dim() != 2:
+            return super().update(obs, actions)
+        mean, std, log_std = self._parts(head)
+        acts = actions.to(device=head.device, dtype=torch.float32).reshape(head.shape[0], -1).contiguous()
+        lp, ent = _C.gauss_sd_logp(head, acts, self.tanh_action, want_ent=True)
+        return {"mean": mean, "dis": Normal(mean, std), "log_std": log_std, "std": std,
+                "log_prob": lp.unsqueeze(-1), "ent": ent.unsqueeze(-1)}
+
+    def explore(self, x, return_log_probs=False, return_pre_tanh=False):
+        """The base class's dict, key for key (`pre_tanh` of a tanh policy included), from the kernels.  One difference for
+        direct callers: the noise is one torch.randn block on the device, not Normal.sample / rsample's own draw."""
+        head = self._head(x)
+        if head is None:
+            return super().explore(x, return_log_probs=return_log_probs, return_pre_tanh=return_pre_tanh)
+        mean, std, log_std = self._parts(head)
+        N, A = head.shape[0], head.shape[1] // 2
+        eps = torch.randn(N, A, device=head.device)
+        act, lp = _C.gauss_sd_explore(head, eps, self.tanh_action)
+        _, ent = _C.gauss_sd_logp(head, act, self.tanh_action, want_ent=True)
+        squeeze = (lambda t: t.squeeze(0)) if x.dim() == 1 else (lambda t: t)
+        out = {"mean": squeeze(mean), "log_std": squeeze(log_std), "std": squeeze(std), "ent": squeeze(ent.unsqueeze(-1)),
+               "action": squeeze(act).squeeze(0)}
+        if return_log_probs:
+            out["log_prob"] = squeeze(lp.unsqueeze(-1))
+        if self.tanh_action and (return_log_probs or return_pre_tanh):
+            # z = mean + std * eps as the kernel forms it before its tanh: the same launch without the tanh, the same bits
+            z, _ = _C.gauss_sd_explore(head, eps, False)
+            out["pre_tanh"] = squeeze(z).squeeze(0)
+        return out
+
+    def torch_eval_act(self, x):
+        head = self._head(x)
+        if head is None:
+            return super().torch_eval_act(x)
+        act, _ = _C.gauss_sd_explore(head, None, self.tanh_action)
+        return act if x.dim() == 2 else act.squeeze(0)
 
 
 class GuassianContPolicyBasicBias(networks.Net, GuassianContPolicyBase):
