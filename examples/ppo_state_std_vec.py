@@ -5,6 +5,9 @@ the update runs on the generic engine (DESIGN.md sections 4 and 7):
 
     python examples/ppo_state_std_vec.py --config config/ppo_synth_halfcheetah_state_std.json \
         --vec_env_nums 256 --seed 0 --overwrite
+
+    TRL_SD_FUSED_ROLLOUT=1 python examples/ppo_state_std_vec.py --config config/ppo_synth_halfcheetah_state_std.json \
+        --vec_env_nums 256 --seed 0 --overwrite        # the same run, collected by the one-launch rollout (opt-in)
 """
 import os.path as osp
 import random

@@ -213,6 +213,16 @@ int trl_rollout_supported(int D, int H, int A, int act);
  * 2 <= A <= 8, Tanh or ReLU. */
 int trl_rollout_synth_cat_f32(const trl_rollout_t* args, int64_t noise_seed, int64_t env_offset, void* stream);
 int trl_rollout_cat_supported(int D, int H, int A, int act);
+/* The same rollout for a state-dependent-std Gaussian policy (GuassianContPolicy, continuous_policy.py:134-170): args->A
+ * (1..8) is the number of ACTION DIMENSIONS, not the head's width; pf_params is the MLP2 block D -> H -> H -> 2A WITHOUT a
+ * logstd tail, its head rows [0, A) the mean and [A, 2A) the raw log_std.  Per step and env: ls = clamp(raw, -20, 2),
+ * z = mean + exp(ls) * eps, action = [tanh](z), args->old_logp gets log pi of the action fed to the env step
+ * (trl_gauss_sd_explore_f32's forms).  eps is trl_rollout_synth_f32's: args->noise (n_steps, N, A), or the device Philox
+ * stream, or 0 with args->deterministic.  Everything else (value pass, bootstrap, resets, ring rows, header, episode log)
+ * is trl_rollout_synth_f32's.  args->norm_state / noise_flag / stage_n must be unset (TRL_EINVAL).  Shapes:
+ * trl_rollout_sd_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh or ReLU. */
+int trl_rollout_synth_sd_f32(const trl_rollout_t* args, void* stream);
+int trl_rollout_sd_supported(int D, int H, int A, int act);
 /* Page-locked host block -> device buffer by a KERNEL (the device reads host memory in place), meant for a stream of
  * its own next to the one that computes: n floats (n % 4 == 0, 16-byte aligned pointers); when every workgroup's part is
  * in device memory, state[0] = stamp is stored with device scope -- what a consumer launched on another stream polls

@@ -1,0 +1,218 @@
+"""The cases of the fused state-dependent-std rollout tests and their CPU restatement -- test infrastructure, imported by
+tests/test_gauss_sd_rollout_*.py only.  Builds on tests/_gauss_sd_ref.py (the head's arithmetic),
+tests/_categorical_rollout_ref.py (shapes, `cpu_rollout`'s bookkeeping) and oracle.synth_env.SynthVecEnvCPU.
+
+`cpu_rollout` is `_categorical_rollout_ref.cpu_rollout`'s counterpart for this head: it steps the synthetic env with
+act = [tanh](mean + exp(clamp(raw, -20, 2)) * eps) and the collector's bookkeeping, in float32 (SynthVecEnvCPU itself) or in
+float64 (the same env with its step restated in float64).  `step_terms` restates ONE step from given observations and
+noise, with the bounds a head error of 1e-5 * (1 + |head element|) allows on what follows from the head."""
+import numpy as np
+import torch
+
+import _categorical_rollout_ref as crr
+import _gauss_sd_ref as ref
+from oracle import philox
+from oracle.synth_env import SynthVecEnvCPU
+
+DISCOUNT = crr.DISCOUNT
+ACTS = crr.ACTS
+HOST_SEED = 11                                                        # torch.manual_seed in front of a host-noise run
+
+# fused vs per-step: the shapes of the categorical rollout tests (N = 40: two full 16-env tiles and a partial one;
+# horizon 5 < T = 12: resets inside a rollout; two epochs: the Philox keys continue).  (32, 8): the wide tile with a full
+# 16-row head; (4, 1): the smallest head (no lane has a second action dim).  Default head initialiser: std ~ 1.
+PAIR_N, PAIR_T, PAIR_HORIZON, PAIR_EPOCHS = crr.PAIR_N, crr.PAIR_T, crr.PAIR_HORIZON, crr.PAIR_EPOCHS
+PAIR_CASES = [dict(D=17, A=6, act="tanh", net_seed=21, env_seed=3, max_frames=999, tanh=True),
+              dict(D=5, A=3, act="relu", net_seed=22, env_seed=4, max_frames=4, tanh=True),
+              dict(D=32, A=8, act="tanh", net_seed=23, env_seed=5, max_frames=999, tanh=True),
+              dict(D=4, A=1, act="tanh", net_seed=24, env_seed=6, max_frames=999, tanh=True),
+              dict(D=17, A=6, act="tanh", net_seed=21, env_seed=3, max_frames=999, tanh=False)]
+CPU_CASE = dict(D=17, A=6, act="tanh", net_seed=0, env_seed=3, max_frames=999, tanh=True)
+CPU_N, CPU_T, CPU_HORIZON = crr.CPU_N, crr.CPU_T, crr.CPU_HORIZON
+# teacher-forced steps with stress heads, no tanh.  "span": the log_std rows of W3 are scaled by `ls_scale` and b3's log_std
+# half is set to `ls_bias`, so the raw log_std spans past +2 for a share of the elements and stays far above the lower
+# clamp.  "pinned": the same scaling around 0 with b3 of the LAST action dim at -25 (always clamped to -20: raw <= -20
+# needs the W3 part below 5) and of the FIRST at +3 (clamped to +2 wherever the W3 part is above -1).
+# SHARE_*: (min, max) share of ALL log_std elements the float64 restatement puts on that clamp -- asserted by the CPU test;
+# the GPU test exempts no more elements than SHARE_LO's maximum.
+STRESS_CASES = [dict(D=17, A=6, act="tanh", net_seed=31, env_seed=7, max_frames=999, tanh=False, stress="span",
+                     ls_scale=300.0, ls_bias=1.0, share_hi=(0.05, 0.60), share_lo=(0.0, 0.0)),
+                dict(D=32, A=8, act="tanh", net_seed=32, env_seed=8, max_frames=999, tanh=False, stress="span",
+                     ls_scale=300.0, ls_bias=1.0, share_hi=(0.05, 0.60), share_lo=(0.0, 0.0)),
+                dict(D=17, A=6, act="tanh", net_seed=33, env_seed=9, max_frames=999, tanh=False, stress="pinned",
+                     ls_scale=300.0, ls_bias=0.0, share_hi=(0.10, 0.40), share_lo=(1.0 / 6, 1.0 / 6)),
+                dict(D=32, A=8, act="tanh", net_seed=34, env_seed=10, max_frames=999, tanh=False, stress="pinned",
+                     ls_scale=300.0, ls_bias=0.0, share_hi=(0.08, 0.35), share_lo=(1.0 / 8, 1.0 / 8))]
+STRESS_N, STRESS_T, STRESS_HORIZON = 40, 6, 5
+
+
+def case_id(c):
+    return "D%d-A%d-%s-mf%d-%s%s" % (c["D"], c["A"], c["act"], c["max_frames"], "tanhact" if c["tanh"] else "plain",
+                                     "-" + c["stress"] if c.get("stress") else "")
+
+
+def nets_of(c, hidden=(64, 64), A=None):
+    """(pf, vf) on the CPU: policies.GuassianContPolicy with a 2A-wide head; the default initialiser, or a stress head."""
+    from torchrl_amd import networks, policies
+    A = c["A"] if A is None else A
+    torch.manual_seed(c["net_seed"])
+    net = dict(hidden_shapes=list(hidden), append_hidden_shapes=[], base_type=networks.MLPBase, activation_func=ACTS[c["act"]][0])
+    pf = policies.GuassianContPolicy(input_shape=c["D"], output_shape=2 * A, tanh_action=c["tanh"], **net)
+    vf = networks.Net(input_shape=(c["D"],), output_shape=1, **net)
+    if c.get("stress"):
+        last = pf.seq_append_fcs[-1]
+        with torch.no_grad():
+            last.weight[:A].mul_(100.0)                                # means of a few tenths
+            last.weight[A:].mul_(c["ls_scale"])
+            last.bias[A:].fill_(c["ls_bias"])
+            if c["stress"] == "pinned":
+                last.bias[2 * A - 1] = -25.0
+                last.bias[A] = 3.0
+    return pf, vf
+
+
+linear_params = crr.linear_params
+
+
+def params_of(mod, dtype):
+    return [p.detach().cpu().to(dtype) for p in linear_params(mod)]
+
+
+def forward(params, x, act, dtype):
+    h = torch.as_tensor(x).to(dtype)
+    n = len(params) // 2
+    for k in range(n):
+        h = h @ params[2 * k].t() + params[2 * k + 1]
+        if k < n - 1:
+            h = ACTS[act][1](h)
+    return h
+
+
+# ---------------------------------------------------------------- noise
+def host_noise(steps, N, A, seed=HOST_SEED):
+    """The reference's stream: one torch.randn(N, A) per step from the CPU generator seeded with `seed`."""
+    torch.manual_seed(seed)
+    return torch.stack([torch.randn(N, A) for _ in range(steps)])
+
+
+def device_noise(steps, N, A, env_seed, step0=0):
+    """The rollout kernel's Philox stream: step t of env n is keyed (global step, env seed * N + n), blocks 0 / 1."""
+    seeds = np.int64(env_seed) * np.int64(N) + np.arange(N, dtype=np.int64)
+    return torch.from_numpy(np.stack([philox.normal_vector(A, step0 + t, 0, philox.TAG_NOISE, seeds)
+                                      for t in range(steps)]).astype(np.float32))
+
+
+def noise_of(mode, steps, N, A, env_seed):
+    return host_noise(steps, N, A) if mode == "host" else device_noise(steps, N, A, env_seed)
+
+
+# ---------------------------------------------------------------- whole rollouts
+class SynthVecEnv64(SynthVecEnvCPU):
+    """SynthVecEnvCPU with the step restated in float64 (the same float32 matrices, reset draws and constants)."""
+
+    def step(self, actions):
+        actions = np.asarray(actions, dtype=np.float64).reshape(self.env_nums, self.act_dim)
+        nxt = np.tanh(self._obs.astype(np.float64) @ self.A.astype(np.float64) + actions @ self.B.astype(np.float64))
+        rew = nxt[:, 0] - np.float64(np.float32(0.1)) * np.sum(actions * actions, axis=1)
+        if self.training:
+            rew = rew * np.float64(np.float32(self._reward_scale))
+        self.t += 1
+        done = self.t >= self.horizon
+        self._obs = nxt
+        return nxt, rew[:, None], done[:, None], {"time_limit": done.copy()}
+
+
+def cpu_rollout(c, N, steps, horizon, nets, eps, dtype=torch.float32):
+    """`steps` vector steps from a fresh env on the noise block `eps` (steps, N, A) -> dict of (steps, N, .) arrays (obs,
+    next_obs, acts, values, rewards, terminals, time_limits, old_logp) in `dtype`, plus `epoch_reward` per step and
+    `episodes`: [(step, env, return)] in (step, env) order."""
+    D, A = c["D"], c["A"]
+    npd = np.float32 if dtype == torch.float32 else np.float64
+    pf, vf = nets
+    ppf, pvf = params_of(pf, dtype), params_of(vf, dtype)
+    env = (SynthVecEnvCPU if dtype == torch.float32 else SynthVecEnv64)(N, horizon=horizon, obs_dim=D, act_dim=A)
+    env.seed(c["env_seed"])
+    ob = torch.from_numpy(env.reset().astype(npd))
+    cur_step, run_ret = np.zeros(N, dtype=np.int64), np.zeros(N, dtype=npd)
+    keys = ("obs", "next_obs", "acts", "values", "rewards", "terminals", "time_limits", "old_logp", "epoch_reward")
+    out = {k: [] for k in keys}
+    episodes = []
+    with torch.no_grad():
+        for g in range(steps):
+            head, v = forward(ppf, ob, c["act"], dtype), forward(pvf, ob, c["act"], dtype)
+            a, lp = ref.explore(head, torch.as_tensor(eps[g]).to(dtype), c["tanh"])
+            nxt, rew, done, _ = env.step(a.numpy())
+            nxt, rew, done = nxt.astype(npd), rew.astype(npd), done[:, 0]
+            cur_step += 1
+            run_ret += rew[:, 0]
+            out["epoch_reward"].append(float(rew.astype(np.float64).sum()))
+            for n in np.nonzero(done)[0]:
+                episodes.append((g, int(n), float(run_ret[n])))
+            run_ret[done] = 0
+            surpass = cur_step >= c["max_frames"]
+            v_next = forward(pvf, torch.from_numpy(nxt), c["act"], dtype).numpy()[:, 0]
+            stored_rew = (rew[:, 0] + npd(np.float32(DISCOUNT)) * v_next * surpass.astype(npd)).astype(npd)
+            term = done | surpass
+            for k, val in (("obs", ob.numpy()), ("next_obs", nxt), ("acts", a.numpy()), ("values", v.numpy()),
+                           ("rewards", stored_rew[:, None]), ("terminals", term[:, None].astype(npd)),
+                           ("time_limits", done[:, None].astype(npd)), ("old_logp", lp.numpy()[:, None])):
+                out[k].append(np.array(val, dtype=npd))
+            cur_step[term] = 0
+            ob = torch.from_numpy(env.partial_reset(term).astype(npd))
+    res = {k: np.stack(v) for k, v in out.items()}
+    res["episodes"] = episodes
+    return res
+
+
+# bounds of the whole-trajectory comparisons: tests/test_categorical_rollout_gpu.py::TOL, stored actions abs 1e-5
+# (tests/test_gauss_sd_gpu.py), log pi_old rtol 1e-4 / atol 2e-3
+TOL = {"obs": (0, 1e-5), "next_obs": (0, 1e-5), "acts": (0, 1e-5), "values": (0, 1e-5), "rewards": (0, 1e-5),
+       "terminals": (0, 0), "time_limits": (0, 0), "old_logp": (1e-4, 2e-3)}
+
+
+def worst_ratio(got, want, rtol, atol):
+    """max over elements of |got - want| / (atol + rtol |want|) (exact keys: 0 if equal, inf otherwise) and max |err|."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    err = np.abs(got - want)
+    if rtol == 0 and atol == 0:
+        return (0.0 if not err.any() else float("inf")), float(err.max() if err.size else 0.0)
+    return float((err / (atol + rtol * np.abs(want))).max() if err.size else 0.0), float(err.max() if err.size else 0.0)
+
+
+# ---------------------------------------------------------------- one step, teacher-forced
+def step_terms(c, params64, obs, eps, reward_scale=1.0):
+    """The float64 restatement of one step from the given (M, D) observations and (M, A) noise -> dict of float64 arrays:
+    head (M, 2A), ls, std, act, next_obs, reward (M,), and the bounds b_act (M, A), b_next (M, D), b_rew (M,) that a head
+    error of h = 1e-5 * (1 + |head element|) allows: the action mean + std * eps moves by at most h_mean + std |eps| h_ls
+    (d std = std d ls; 0 where the clamp holds the element, which only tightens what is needed), next_obs[f] by
+    1e-5 + sum_o |env_B[o, f]| b_o (|tanh'| <= 1), the raw reward by reward_scale * (1e-5 + 0.2 sum_o |a_o| b_o)."""
+    from oracle.synth_env import dynamics_matrices
+    D, A = c["D"], c["A"]
+    eA, eB = (torch.from_numpy(m).double() for m in dynamics_matrices(D, A))
+    obs, eps = torch.as_tensor(obs).double(), torch.as_tensor(eps).double()
+    with torch.no_grad():
+        head = forward(params64, obs, c["act"], torch.float64)
+        mean, ls, std = ref.parts(head)
+        z = mean + std * eps
+        act = torch.tanh(z) if c["tanh"] else z
+        nxt = torch.tanh(obs @ eA + act @ eB)
+        rew = reward_scale * (nxt[:, 0] - float(np.float32(0.1)) * (act * act).sum(-1))
+        h = 1e-5 * (1.0 + head.abs())
+        b_act = h[:, :A] + std * eps.abs() * h[:, A:]
+        b_next = 1e-5 + b_act @ eB.abs()
+        b_rew = reward_scale * (1e-5 + 0.2 * (act.abs() * b_act).sum(-1))
+    return {k: v.numpy() for k, v in dict(head=head, raw=head[:, A:], ls=ls, std=std, act=act, next_obs=nxt, reward=rew,
+                                          b_act=b_act, b_next=b_next, b_rew=b_rew).items()}
+
+
+def step_terms_f32(c, params32, obs, eps, reward_scale=1.0):
+    """The same step in float32 (what a kernel computes, up to summation order): act, next_obs, reward, old_logp."""
+    from oracle.synth_env import dynamics_matrices
+    eA, eB = (torch.from_numpy(m) for m in dynamics_matrices(c["D"], c["A"]))
+    obs, eps = torch.as_tensor(obs).float(), torch.as_tensor(eps).float()
+    with torch.no_grad():
+        head = forward(params32, obs, c["act"], torch.float32)
+        act, lp = ref.explore(head, eps, c["tanh"])
+        nxt = torch.tanh(obs @ eA + act @ eB)
+        rew = np.float32(reward_scale) * (nxt[:, 0] - np.float32(0.1) * (act * act).sum(-1))
+    return dict(head=head.numpy(), act=act.numpy(), next_obs=nxt.numpy(), reward=rew.numpy(), old_logp=lp.numpy())

@@ -131,6 +131,8 @@ SIGNATURES = {
     "trl_rollout_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_rollout_synth_cat_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int64, C.c_int64, C.c_void_p]),
     "trl_rollout_cat_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_rollout_synth_sd_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_void_p]),
+    "trl_rollout_sd_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_stage_h2d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trl_ppo_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_mlp2_forward_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -561,6 +563,12 @@ def rollout_cat(args, noise_seed, env_offset, device):
     env_offset + env index), as trl_cat_act_f32 keys them."""
     check(lib().trl_rollout_synth_cat_f32(C.byref(args), int(noise_seed), int(env_offset), stream_ptr(device)),
           "trl_rollout_synth_cat_f32")
+
+
+def rollout_sd(args, device):
+    """The persistent rollout with a state-dependent-std Gaussian head [mean | log_std]: args.A is the number of action
+    dimensions (half the head's width), args.acts rows are (N, A)."""
+    check(lib().trl_rollout_synth_sd_f32(C.byref(args), stream_ptr(device)), "trl_rollout_synth_sd_f32")
 
 
 def ppo_partial_stride(D, H, A):

@@ -295,8 +295,9 @@ class VecOnPolicyCollector(VecCollector):
         # persistent rollout has a categorical head for the shapes of trl_rollout_cat_supported (see the end of this method)
         self._cat = getattr(self.pf, "continuous", True) is False and hasattr(self.pf, "logits")
         # a state-dependent-std Gaussian policy (policies.GuassianContPolicy): the head is [mean | log_std], `_dims[1]` = A is
-        # half its width.  Always the per-step route, with trl_gauss_sd_explore_f32 in place of trl_gauss_explore_f32 on the
-        # same (N, A) noise block; neither the persistent rollout nor the TRL_CAT_* routes apply (`_spec` stays None).
+        # half its width.  The per-step route uses trl_gauss_sd_explore_f32 in place of trl_gauss_explore_f32 on the same
+        # (N, A) noise block; the persistent rollout has a head for it for the shapes of trl_rollout_sd_supported, opt-in
+        # (see the end of this method).  The TRL_CAT_* routes do not apply.
         from ..policies.continuous_policy import is_state_std
         self._sd = not self._cat and is_state_std(self.pf)
         if not self._cat and not self._sd and not hasattr(self.pf, "logstd"):
@@ -337,8 +338,21 @@ class VecOnPolicyCollector(VecCollector):
         roll = pair and bool(lib.trl_rollout_supported(ps[0], ps[1], ps[2], ps[3])) and \
             (bool(mlp2) or os.environ.get("TRL_NO_RT_ROLLOUT") != "1")
         self._spec = ps if (roll and not getattr(self.env, "is_host_env", False)) else None   # ... and the rollout kernel
-        if self._sd:                                                        # per-step route on the dense-layer kernels: the
-            self._spec = self._mlp2 = None                                  # forward the update runs (same bits: ratio == 1)
+        if self._sd:
+            # the per-step route runs on the dense-layer kernels, the forward the update runs (same bits: ratio == 1).  The
+            # persistent rollout's state-dependent-std head (trl_rollout_synth_sd_f32) takes 64-wide pairs with 1..8 action
+            # dims (`ps[2]` is the head's width 2A) on a device env with continuous actions, one rank, no observation
+            # normaliser, no noise prefetch; opt-in, TRL_SD_FUSED_ROLLOUT=1: its stored actions differ from the per-step
+            # route's at the 1e-6 level (profiles/NOTES_state_std_rollout.md).  `_mlp2` stays None either way: the fused
+            # two-layer forward is not instantiated for 2A outputs.
+            A = self._dims[1]
+            fused = pair and ps[2] == 2 * A and bool(lib.trl_rollout_sd_supported(ps[0], ps[1], A, ps[3])) and \
+                os.environ.get("TRL_SD_FUSED_ROLLOUT") == "1" and \
+                os.environ.get("TRL_NO_RT_ROLLOUT") != "1" and dist.world_size() == 1 and not self.prefetch_noise and \
+                all(not getattr(e, "discrete", False) and hasattr(e, "env_B") and not getattr(e, "is_host_env", False)
+                    and not hasattr(e, "_obs_normalizer") for e in (self.env, self.eval_env) if e is not None)
+            self._spec = (ps[0], ps[1], A, ps[3]) if fused else None
+            self._mlp2 = None
         if self._cat:
             # the persistent rollout's categorical head (trl_rollout_synth_cat_f32): 64-wide pairs with 2..8 actions on a
             # device env that takes one-hot actions, one rank, no observation normaliser (its kernel is the Gaussian
@@ -465,6 +479,8 @@ class VecOnPolicyCollector(VecCollector):
             self._published = True
         if self._cat:                                                   # the draw trl_cat_act_f32 makes at these steps
             _C.rollout_cat(a, self._noise_seed, self._noise_layout(env)[1], env.device)
+        elif self._sd:                                                  # a.A = action dims, pf_params has a 2A-row head
+            _C.rollout_sd(a, env.device)
         else:
             _C.rollout(a, env.device)
         self._idle_hdr_clean = True

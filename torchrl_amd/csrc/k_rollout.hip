@@ -83,11 +83,15 @@ __device__ __forceinline__ float ro_row_sum16(float v) {          // sum over th
 }
 #define NORM_SLOT 40                                 // doubles per workgroup partial: sum x [D] | sum x^2 [D] | any flag | .. | stamp
 
-template <int D, int H, int A> struct RoShape {
+// HC: head capacity, the rows of the 16-row head tile that are exchanged through LDS -- 8 (the A <= 8 means or logits), or
+// 16 for the state-dependent-std head [mean | log_std] of up to 2 x 8 rows.
+template <int D, int H, int A, int HC_ = 8> struct RoShape {
   static_assert(H == 64 && D > 16 && D <= 32 && A <= 8, "instantiated for 16 < D <= 32, H == 64, A <= 8");
-  // LDS: b1[H] | b2[H] | b3[8] | logstd[8] | H1 staging [H][TL] | headp [4][8][16] | eps [RO_NB][8][16]
-  static constexpr int O_B1 = 0, O_B2 = H, O_B3 = 2 * H, O_LS = O_B3 + 8, O_H1 = O_LS + 8, O_HP = O_H1 + H * TL,
-                       O_EPS = O_HP + 4 * 8 * 16, LDS_FLOATS = O_EPS + RO_NB * 8 * 16;
+  static_assert(HC_ == 8 || HC_ == 16, "the head exchange carries half or all of the 16-row head tile");
+  static constexpr int HC = HC_;
+  // LDS: b1[H] | b2[H] | b3[HC] | logstd[8] | H1 staging [H][TL] | headp [4][HC][16] | eps [RO_NB][8][16]
+  static constexpr int O_B1 = 0, O_B2 = H, O_B3 = 2 * H, O_LS = O_B3 + HC, O_H1 = O_LS + 8, O_HP = O_H1 + H * TL,
+                       O_EPS = O_HP + 4 * HC * 16, LDS_FLOATS = O_EPS + RO_NB * 8 * 16;
 };
 
 // Host block -> device buffer with device-scope stores (past the per-XCD L2: nothing to write back or invalidate when the
@@ -136,17 +140,25 @@ __device__ __forceinline__ void stage_block(const f32x4* __restrict__ src, unsig
 // noise (one (step, env) per thread).  The env takes the one-hot row of the drawn index: lane group g feeds action
 // dims g and 4 + g to the env GEMM as before, now 1.0 where the index matches -- a row selection of env_B, no one-hot row
 // in memory.  The ring's `acts` is (N, 1): the index as a float.  The parameter block has no logstd tail.
-template <int D, int H, int A, int ACT, bool NORM, bool RT = false, bool CAT = false>
+// SD = true: a state-dependent-std Gaussian head (policies.GuassianContPolicy) over Ar = 1..8 action dims.  The head's
+// 2 Ar <= 16 outputs are [mean | raw log_std] -- the whole 16-row head tile, which the other heads compute and half discard:
+// W3 is (2 Ar, H), b3 (2 Ar), no logstd tail; all four lane groups publish their partial head rows (headp [4][16][16]),
+// and after the exchange a lane reads the mean of its action dim o at row o and the raw log_std at row Ar + o.  The clamp
+// to [-20, 2], std = exp(ls) and 1 / std^2 = exp(-2 ls) are then PER STEP (gauss_sd_explore_kernel's forms, k_gauss_sd.hip)
+// instead of once per launch; noise, env step, bookkeeping and the value pass are the Gaussian head's, unchanged.
+template <int D, int H, int A, int ACT, bool NORM, bool RT = false, bool CAT = false, bool SD = false>
 __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
-  using S = RoShape<D, H, A>;
+  using S = RoShape<D, H, A, SD ? 16 : 8>;
   constexpr bool WIDE = D > 17;
   static_assert(!CAT || RT, "the categorical head exists as a runtime-dims instantiation only");
+  static_assert(!SD || (RT && !NORM && !CAT), "the state-dependent-std head exists as a runtime-dims instantiation only");
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!(RT && NORM), "the cooperative (normalised) rollout is instantiated for the benchmark shape");
   const int Dr = RT ? a.D : D, Ar = RT ? a.A : A;   // actual dims (row strides of obs / acts, parameter offsets)
+  const int HW = SD ? 2 * Ar : Ar;                  // rows of W3 / b3: what the head emits per env
   // offsets inside the flat parameter block for the actual dims (MlpFlat, trl_mlp.h)
-  const int F_W1 = 0, F_B1 = H * Dr, F_W2 = F_B1 + H, F_B2 = F_W2 + H * H, F_W3 = F_B2 + H, F_B3 = F_W3 + Ar * H,
-            F_LS = F_B3 + Ar;
+  const int F_W1 = 0, F_B1 = H * Dr, F_W2 = F_B1 + H, F_B2 = F_W2 + H * H, F_W3 = F_B2 + H, F_B3 = F_W3 + HW * H,
+            F_LS = F_B3 + HW;
   __shared__ __attribute__((aligned(16))) float lds[S::LDS_FLOATS];
   if (!NORM && (int)blockIdx.x >= a.n_ro_wg) {
     // ---- a stager: the NEXT rollout's noise block, host -> device, next to this rollout's own workgroups ----
@@ -195,7 +207,10 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
 
   // ---- one-time setup: biases / logstd to LDS, this wave's weight slices to registers ----
   for (int e = tid; e < H; e += RO_THREADS) { lds[S::O_B1 + e] = gp[F_B1 + e]; lds[S::O_B2 + e] = gp[F_B2 + e]; }
-  if (tid < 8) {
+  if constexpr (SD) {
+    if (tid < 16) lds[S::O_B3 + tid] = tid < HW ? gp[F_B3 + (tid < HW ? tid : 0)] : 0.0f;
+    if (tid < 8) lds[S::O_LS + tid] = 0.0f;           // (no logstd tail: the launch-wide std below is not used)
+  } else if (tid < 8) {
     lds[S::O_B3 + tid] = tid < Ar ? gp[F_B3 + (tid < Ar ? tid : 0)] : 0.0f;
     lds[S::O_LS + tid] = (!CAT && tid < Ar) ? gp[F_LS + (tid < Ar ? tid : 0)] : 0.0f;
   }
@@ -225,7 +240,7 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) w2r[sl][r] = gp[F_W2 + row * H + 16 * sl + 4 * g + r];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) w3a[r] = (i < Ar) ? gp[F_W3 + (i < Ar ? i : 0) * H + 16 * mo + 4 * g + r] : 0.0f;
+    for (int r = 0; r < 4; ++r) w3a[r] = (i < HW) ? gp[F_W3 + (i < HW ? i : 0) * H + 16 * mo + 4 * g + r] : 0.0f;
     // env GEMM next^T[f][j] = sum_k M[f][k] [obs; act]^T[k][j] for features f = 0..15 (we0, MFMA A operand of
     // row f = i) and, wide tile, f = 16..31 (we1); narrow tile: feature 16 is a per-lane partial dot over the lane's own
     // inputs (w16) + a lane-group sum
@@ -255,9 +270,10 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
   const float* b2s = lds + S::O_B2 + 16 * mo + 4 * g;
 
   // the lane's two action dims
-  const float ls_lo = fminf(fmaxf(lds[S::O_LS + o_lo], -20.0f), 2.0f), ls_hi = fminf(fmaxf(lds[S::O_LS + o_hi], -20.0f), 2.0f);
-  const float std_lo = __expf(ls_lo), std_hi = __expf(ls_hi);
-  const float iv_lo = __expf(-2.0f * ls_lo), iv_hi = __expf(-2.0f * ls_hi);
+  // (SD: the std is the env's own, from the head's rows Ar + o -- these are overwritten every step)
+  float ls_lo = fminf(fmaxf(lds[S::O_LS + o_lo], -20.0f), 2.0f), ls_hi = fminf(fmaxf(lds[S::O_LS + o_hi], -20.0f), 2.0f);
+  float std_lo = __expf(ls_lo), std_hi = __expf(ls_hi);
+  float iv_lo = __expf(-2.0f * ls_lo), iv_hi = __expf(-2.0f * ls_hi);
   const float b3_lo = lds[S::O_B3 + o_lo], b3_hi = lds[S::O_B3 + o_hi];
 
   // ---- per-env state (replicated in all 4 waves and all 4 lane groups) ----
@@ -368,16 +384,28 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
     f32x4 hp = f32x4{0.f, 0.f, 0.f, 0.f};                  // partial head over the own 16 features: D[o][env]
 #pragma unroll
     for (int r = 0; r < 4; ++r) hp = mfma16(w3a[r], h2[r], hp);
-    if (g < 2) {
+    if (SD || g < 2) {                                     // lane group g holds head rows 4g .. 4g + 3
 #pragma unroll
-      for (int r = 0; r < 4; ++r) headp[(mo * 8 + 4 * g + r) * 16 + j] = hp[r];
+      for (int r = 0; r < 4; ++r) headp[(mo * S::HC + 4 * g + r) * 16 + j] = hp[r];
     }
     CLK(3)
     __syncthreads();
     CLK(4)
     float mean_lo = b3_lo, mean_hi = b3_hi;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) { mean_lo += headp[(w * 8 + o_lo) * 16 + j]; mean_hi += headp[(w * 8 + o_hi) * 16 + j]; }
+    for (int w = 0; w < 4; ++w) { mean_lo += headp[(w * S::HC + o_lo) * 16 + j]; mean_hi += headp[(w * S::HC + o_hi) * 16 + j]; }
+    if constexpr (SD) {
+      // this step's std from the raw log_std rows Ar + o of the head (0 <= Ar + o < 2 Ar <= 16)
+      float raw_lo = lds[S::O_B3 + Ar + o_lo], raw_hi = lds[S::O_B3 + Ar + o_hi];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        raw_lo += headp[(w * S::HC + Ar + o_lo) * 16 + j];
+        raw_hi += headp[(w * S::HC + Ar + o_hi) * 16 + j];
+      }
+      ls_lo = fminf(fmaxf(raw_lo, -20.0f), 2.0f); ls_hi = fminf(fmaxf(raw_hi, -20.0f), 2.0f);
+      std_lo = __expf(ls_lo); std_hi = __expf(ls_hi);
+      iv_lo = __expf(-2.0f * ls_lo); iv_hi = __expf(-2.0f * ls_hi);
+    }
 
     // categorical head (discrete_policies.py:136-150): cat_act_kernel's rule on the env's Ar logits
     int cat_k = 0;
@@ -812,14 +840,14 @@ static int rollout_norm_capacity() {
   return cus * per_cu * RO_ENVS;
 }
 
-template <int D, int H, int A, int ACT, bool RT = false, bool CAT = false>
+template <int D, int H, int A, int ACT, bool RT = false, bool CAT = false, bool SD = false>
 static int launch_rollout(const RolloutDev& d, hipStream_t s, hipEvent_t value_wait = nullptr) {
   const int n_wg = trl_ceil_div(d.N, RO_ENVS);
   if constexpr (RT) {
     if (d.norm_state) { trl_set_error("rollout: the normalised rollout is instantiated for the benchmark shape only"); return TRL_EUNSUPPORTED; }
     RolloutDev e = d;
     e.n_ro_wg = n_wg;
-    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true, CAT>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
+    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true, CAT, SD>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
   } else if (d.norm_state) {
     const int cap = rollout_norm_capacity<D, H, A, ACT>();
     if (d.norm_update && d.N > cap) {
@@ -880,8 +908,15 @@ extern "C" int trl_rollout_cat_supported(int D, int H, int A, int act) {
   return H == 64 && D >= 2 && D <= 32 && A >= 2 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
 }
 
+// State-dependent-std Gaussian heads on the persistent rollout: the 64-wide two-layer pairs of the runtime-dims
+// instantiations with 1..8 action dims -- a head of 2 A <= 16 rows, one MFMA head tile (no running observation normaliser).
+extern "C" int trl_rollout_sd_supported(int D, int H, int A, int act) {
+  return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
+}
+
 // cat: the categorical entry point (trl_rollout_synth_cat_f32) with its draw's key and first global env index
-static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t cat_seed, int64_t cat_env0) {
+// sd: the state-dependent-std entry point (trl_rollout_synth_sd_f32); p->A is the number of action dims
+static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t cat_seed, int64_t cat_env0, bool sd = false) {
   if (!p) { trl_set_error("rollout: null descriptor"); return TRL_EINVAL; }
   TRL_REQUIRE(p->pf_params && p->vf_params && p->env_A && p->env_B, "null network / env pointer");
   TRL_REQUIRE(p->cur_obs && p->t_env && p->cur_step && p->episode_idx && p->ep_return, "null env state pointer");
@@ -900,6 +935,15 @@ static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t
     TRL_REQUIRE(!p->norm_state, "categorical: no running observation normaliser in the persistent rollout");
     if (!trl_rollout_cat_supported(p->D, p->H, p->A, p->act)) {
       trl_set_error("rollout: categorical shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
+      return TRL_EUNSUPPORTED;
+    }
+  }
+  if (sd) {
+    TRL_REQUIRE(!p->norm_state, "state-dependent std: no running observation normaliser in the persistent rollout");
+    TRL_REQUIRE(!p->noise_flag && !p->stage_n,
+                "state-dependent std: the noise block is stream-ordered in front of the launch (no noise gate, nothing staged)");
+    if (!trl_rollout_sd_supported(p->D, p->H, p->A, p->act)) {
+      trl_set_error("rollout: state-dependent-std shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
       return TRL_EUNSUPPORTED;
     }
   }
@@ -948,6 +992,14 @@ static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t
     if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true, true>(d, s, vw);
     return launch_rollout<32, 64, 8, TRL_ACT_RELU, true, true>(d, s, vw);
   }
+  if (sd) {
+    if (p->D <= 17) {
+      if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 8, TRL_ACT_TANH, true, false, true>(d, s, vw);
+      return launch_rollout<17, 64, 8, TRL_ACT_RELU, true, false, true>(d, s, vw);
+    }
+    if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true, false, true>(d, s, vw);
+    return launch_rollout<32, 64, 8, TRL_ACT_RELU, true, false, true>(d, s, vw);
+  }
   if (p->D == 17 && p->H == 64 && p->A == 6) {
     if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 6, TRL_ACT_TANH>(d, s, vw);
     if (p->act == TRL_ACT_RELU) return launch_rollout<17, 64, 6, TRL_ACT_RELU>(d, s, vw);
@@ -968,6 +1020,10 @@ extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) { ret
 
 extern "C" int trl_rollout_synth_cat_f32(const trl_rollout_t* p, int64_t noise_seed, int64_t env_offset, void* stream) {
   return rollout_synth(p, stream, true, noise_seed, env_offset);
+}
+
+extern "C" int trl_rollout_synth_sd_f32(const trl_rollout_t* p, void* stream) {
+  return rollout_synth(p, stream, false, 0, 0, true);
 }
 
 extern "C" int trl_rollout_norm_workspace(int N) {
