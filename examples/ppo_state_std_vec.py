@@ -8,6 +8,10 @@ the update runs on the generic engine (DESIGN.md sections 4 and 7):
 
     TRL_SD_FUSED_ROLLOUT=1 python examples/ppo_state_std_vec.py --config config/ppo_synth_halfcheetah_state_std.json \
         --vec_env_nums 256 --seed 0 --overwrite        # the same run, collected by the one-launch rollout (opt-in)
+
+    TRL_SD_FUSED_ROLLOUT=1 TRL_SD_FUSED_UPDATE=1 python examples/ppo_state_std_vec.py ...
+                                                       # ... and updated by the fused two-launch sequence (opt-in; 64-wide
+                                                       # two-layer nets, 1-8 action dimensions, Adam, one rank)
 """
 import os.path as osp
 import random

@@ -471,6 +471,37 @@ int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const double* scal_par
                                     int D, int H, int A, float* grads, double* info,
                                     const trl_adam_t* adam, float* workspace, void* stream);
 
+/* --- the fused minibatch update for a STATE-DEPENDENT-STD Gaussian policy (GuassianContPolicy, 1 <= A <= 8) ----------
+ * The entry points above with a [mean | log_std] head on the policy network (the gradient kernel's SD instantiations): the head
+ * has 2A rows, mean rows 0..A-1 then log_std rows A..2A-1; args->A is the number of ACTION dimensions, args->acts is
+ * (rows, N, A), args->pf_params is [W1 b1 W2 b2 W3 b3] (no logstd: P_pf = H D + H + H H + H + 2A H + 2A).  Per element
+ * ls = clamp(raw, -20, 2) and the arithmetic of trl_gauss_sd_losses_f32: d(loss)/d(mean) = g_lp zc / std^2,
+ * d(loss)/d(raw) = gate (g_lp (zc^2 / std^2 - 1) - entropy_coeff / n_global), gate = 1 inside the clamp, an exact 0 outside.
+ * Shapes: trl_ppo_sd_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh / ReLU.  All n_wg_pf
+ * modes of trl_ppo_batch_t work.  partial rows are trl_ppo_sd_partial_stride(D, H, A) floats.  scal_partial holds
+ * n_wg x trl_ppo_sd_scalar_stride() doubles: the n_wg x 8 block of the other heads (entropy sum in the policy rows' eighth
+ * column), then n_wg x 16 -- per policy workgroup log_std {sum, sum of squares, max, -min}, std {the same four}, samples, 7 x 0.
+ * The folds take the same arguments as their Gaussian counterparts (pf_params of trl_ppo_sd_reduce_f32 is not read); the
+ * optimiser groups are [policy without logstd | value]; the info row is trl_gauss_sd_losses_f32's: info[8..11] / [16..19] =
+ * mean, unbiased std, max, min of the clamped log_std / of std = exp(log_std) over all local samples x A elements, info[20] =
+ * the entropy sum.  Same row fold order, norm rendezvous and Adam arithmetic: a single-network launch folded by
+ * trl_ppo_sd_reduce_adam_net_f32 gives the bits of the joint launch + trl_ppo_sd_reduce_adam_f32.  There is no cross-rank
+ * variant for this head. */
+int trl_ppo_sd_supported(int D, int H, int A, int act);
+int trl_ppo_sd_partial_stride(int D, int H, int A);
+int trl_ppo_sd_scalar_stride(void);
+int trl_ppo_sd_minibatch_grad_f32(const trl_ppo_batch_t* args, void* stream);
+int trl_ppo_sd_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                          int D, int H, int A, const float* pf_params, float* grads, double* info,
+                          void* stream);
+int trl_ppo_sd_reduce_adam_workspace(int D, int H, int A);
+int trl_ppo_sd_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                               int D, int H, int A, float* grads, double* info,
+                               const trl_adam_t* adam, float* workspace, void* stream);
+int trl_ppo_sd_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,
+                                   int D, int H, int A, float* grads, double* info,
+                                   const trl_adam_t* adam, float* workspace, void* stream);
+
 typedef struct trl_comm trl_comm_t;   /* opaque communicator, see the collectives section below */
 /* --- C1 / C2 / C3: collectives of the multi-GPU path ---------------
  * The reference has no distributed backend; with envs sharded by index over one process per GPU

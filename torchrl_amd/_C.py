@@ -195,6 +195,16 @@ SIGNATURES = {
                                               C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
     "trl_ppo_cat_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
+    "trl_ppo_sd_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_sd_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_sd_scalar_stride": (C.c_int, []),
+    "trl_ppo_sd_minibatch_grad_f32": (C.c_int, [C.POINTER(PpoBatchArgs), C.c_void_p]),
+    "trl_ppo_sd_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trl_ppo_sd_reduce_adam_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_ppo_sd_reduce_adam_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
+    "trl_ppo_sd_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
     "trl_synth_reset_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "trl_gauss_logp_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_concat2_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
@@ -595,6 +605,31 @@ def ppo_cat_reduce(partial, scal_partial, n_wg, D, H, A, grads, info, n_wg_pf=0)
                                        dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A,
                                        None, dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
                                        stream_ptr(partial.device)), "trl_ppo_cat_reduce_f32")
+
+
+def ppo_sd_partial_stride(D, H, A):
+    ps = lib().trl_ppo_sd_partial_stride(D, H, A)
+    if ps < 0:
+        check(ps, "trl_ppo_sd_partial_stride")
+    return ps
+
+
+def ppo_sd_scalar_stride():
+    """Doubles of `scal_partial` per workgroup for the state-dependent-std launches (8 of every head + 16 of its own)."""
+    return lib().trl_ppo_sd_scalar_stride()
+
+
+def ppo_sd_minibatch_grad(args, device):
+    """The fused minibatch gradient for a state-dependent-std Gaussian policy: args.A action dimensions, a head of 2 args.A
+    rows [mean | log_std], args.pf_params has no logstd, args.scal_partial holds n_wg x ppo_sd_scalar_stride() doubles."""
+    check(lib().trl_ppo_sd_minibatch_grad_f32(C.byref(args), stream_ptr(device)), "trl_ppo_sd_minibatch_grad_f32")
+
+
+def ppo_sd_reduce(partial, scal_partial, n_wg, D, H, A, grads, info, n_wg_pf=0):
+    check(lib().trl_ppo_sd_reduce_f32(dev_ptr(partial, name="partial"),
+                                      dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A,
+                                      None, dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
+                                      stream_ptr(partial.device)), "trl_ppo_sd_reduce_f32")
 
 
 def ppo_minibatch_grad(args, device):

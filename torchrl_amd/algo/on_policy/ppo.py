@@ -135,8 +135,20 @@ class _FusedPPO:
         # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's CAT instantiations and their folds
         # (trl_ppo_cat_*); no logstd in the flat vector, the entropy arrives through info slot 20
         self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
-        if ps is None or vs is None or not (self.categorical or hasattr(pf, "logstd")):
-            raise _C.TrlError("fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias or CategoricalDisPolicy policy")
+        # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; the gradient kernel's SD
+        # instantiations and their folds (trl_ppo_sd_*); no logstd in the flat vector either, `self.A` = half the head's width,
+        # entropy and the per-element log_std / std statistics arrive through info slots 20, 8-11 and 16-19
+        self.state_std = not self.categorical and is_state_std(pf)
+        if ps is None or vs is None or not (self.categorical or self.state_std or hasattr(pf, "logstd")):
+            raise _C.TrlError("fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias, GuassianContPolicy or "
+                              "CategoricalDisPolicy policy")
+        if self.state_std:
+            ps = (ps[0], ps[1], ps[2] // 2, ps[3])
+            if not _C.lib().trl_ppo_sd_supported(*ps):
+                raise _C.TrlError("the fused state-dependent-std update carries H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh / ReLU; "
+                                  "got %s" % (ps,))
+            if dist.collectives_active():
+                raise _C.TrlError("the fused state-dependent-std update runs on one rank (no cross-rank fold exists for this head)")
         if self.categorical and not _C.lib().trl_ppo_cat_supported(*ps):
             raise _C.TrlError("the fused categorical update carries H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU; got %s" % (ps,))
         if self.categorical and dist.collectives_active():
@@ -147,7 +159,7 @@ class _FusedPPO:
         self.dev = next(pf.parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the fused path needs a GPU (no CPU path exists)" % self.dev)
-        tail = (lambda net: []) if self.categorical else (lambda net: [net.logstd])
+        tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = pf._mlp2_param_list() + tail(pf)
         vf_list = vf._mlp2_param_list()
         self.P_pf = sum(p.numel() for p in pf_list)
@@ -163,22 +175,23 @@ class _FusedPPO:
         self.target_flat = None
         if tgt is not None:
             self.target_flat = flatten_into(tgt._mlp2_param_list() + tail(tgt))
-            if self.categorical:                                       # (its logits() forward must find THIS storage, see _GenericPPO)
+            if self.categorical or self.state_std:                     # (its forward must find THIS storage, see _GenericPPO)
                 tgt._flat = self.target_flat
         self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
         self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
         lib = _C.lib()
-        sfx = "cat_" if self.categorical else ""
+        sfx = "cat_" if self.categorical else ("sd_" if self.state_std else "")
         self._k_grad = (getattr(lib, "trl_ppo_%sminibatch_grad_f32" % sfx), "trl_ppo_%sminibatch_grad_f32" % sfx)
         self._k_fold = (getattr(lib, "trl_ppo_%sreduce_adam_f32" % sfx), "trl_ppo_%sreduce_adam_f32" % sfx)
         self._k_fold_net = (getattr(lib, "trl_ppo_%sreduce_adam_net_f32" % sfx), "trl_ppo_%sreduce_adam_net_f32" % sfx)
-        self.p_stride = (_C.ppo_cat_partial_stride if self.categorical else _C.ppo_partial_stride)(self.D, self.H, self.A)
+        self.p_stride = getattr(_C, "ppo_%spartial_stride" % sfx)(self.D, self.H, self.A)
+        # doubles of scalar statistics per workgroup (SD: a second block of rows behind the n_wg x 8 of every head)
+        self.scal_w = _C.ppo_sd_scalar_stride() if self.state_std else 8
         self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         self.max_wg = 2 * max(1, self.n_cu // 2)
         self.partial = torch.zeros(self.max_wg, self.p_stride, device=self.dev)
-        self.scal = torch.zeros(self.max_wg, 8, dtype=torch.float64, device=self.dev)
-        n_ws = (lib.trl_ppo_cat_reduce_adam_workspace if self.categorical else lib.trl_ppo_reduce_adam_workspace)(
-            self.D, self.H, self.A)
+        self.scal = torch.zeros(self.max_wg, self.scal_w, dtype=torch.float64, device=self.dev)
+        n_ws = getattr(lib, "trl_ppo_%sreduce_adam_workspace" % sfx)(self.D, self.H, self.A)
         self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + norm granules of the fold / clip / Adam launch
         # One process: the critic's and the actor's updates of an epoch (ppo.py:93-122 / 41-91: separate networks, optimisers,
         # clips and statistics) run as TWO launch sequences on two streams (`_run_chains`); TRL_PPO_CHAINS=joint keeps the
@@ -285,8 +298,9 @@ class _FusedPPO:
         loss_mode = int(getattr(algo, "loss_mode", _C.LOSS_PPO_CLIP))
         probe = getattr(self, "probe", None)                           # bench.py: HIP events around the grad kernel
         fused = not dist.collectives_active()
-        if self.categorical and not fused:
-            raise _C.TrlError("the fused categorical update runs on one rank (no cross-rank fold exists for this head)")
+        if (self.categorical or self.state_std) and not fused:
+            raise _C.TrlError("the fused %s update runs on one rank (no cross-rank fold exists for this head)"
+                              % ("categorical" if self.categorical else "state-dependent-std"))
         # (env shards on several ranks: the two chains need the in-launch gradient exchange of the peer transport, whose
         # granules and exchange counts are per network; over all-reduce CALLS the joint sequence stays)
         xrank_chains = not fused and self.chains_across_ranks()
@@ -521,7 +535,8 @@ class _FusedPPO:
                  int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
         n_wg_vf = n_wg - n_wg_pf
         if self._chain_rows is None:
-            self._chain_rows = (torch.zeros(self.max_wg, self.p_stride, device=dev), torch.zeros(self.max_wg, 8, dtype=torch.float64, device=dev))
+            self._chain_rows = (torch.zeros(self.max_wg, self.p_stride, device=dev),
+                                torch.zeros(self.max_wg, self.scal_w, dtype=torch.float64, device=dev))
         partial_v, scal_v = self._chain_rows                           # (the policy chain uses self.partial / self.scal)
         shape_key = (n_wg, n_wg_pf, loss_mode, n_global, rows_total, N, pre_key, pre is not None, xrank) + hyper
         key = shape_key + (turn,) + tuple(
@@ -755,7 +770,16 @@ def make_engine(algo):
                 and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
             return _FusedPPO(algo)
         return _GenericPPO(algo)
-    if is_state_std(pf):                                               # [mean | log_std] head: the generic engine only
+    if is_state_std(pf):
+        # [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_SD_FUSED_UPDATE=1, opt-in) AND
+        # both nets have a shape its SD instantiations carry, the optimiser is Adam and this is the only rank
+        if os.environ.get("TRL_SD_FUSED_UPDATE") == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
+                and ps is not None and vs is not None and ps[2] % 2 == 0 \
+                and _C.lib().trl_ppo_sd_supported(ps[0], ps[1], ps[2] // 2, ps[3]) \
+                and _C.lib().trl_ppo_sd_supported(vs[0], vs[1], ps[2] // 2, vs[3]) \
+                and (vs[0], vs[1], vs[2], vs[3]) == (ps[0], ps[1], 1, ps[3]) \
+                and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
+            return _FusedPPO(algo)
         return _GenericPPO(algo)
     if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
             and os.environ.get("TRL_GENERIC_PPO") != "1":

@@ -78,6 +78,23 @@ template <int D, int H, int A> struct WvShape {
   static constexpr int LDS_FLOATS = MAIN > FOLD ? MAIN : FOLD;
 };
 
+// State-dependent-std head (SD): up to 16 head rows [mean | log_std] and no logstd tail -- a gradient image of its own
+// stride (the Gaussian's assumes at most 8 head rows + 8 logstd floats).  The main-loop layout is WvShape's; at the 17-wide
+// tile the four images (4 x 6400 floats) exceed it by 128 floats, at the 32-wide tile they set the size (4 x 7360 floats).
+template <int D, int H, int A> struct WvShapeSD : WvShape<D, H, A> {
+  using B = WvShape<D, H, A>;
+  static constexpr int P_PF_SD = H * D + H + H * H + H + 2 * A * H + 2 * A, P_VF = MlpFlat<D, H, 1>::P_VF;
+  static constexpr int P_STRIDE = ((P_PF_SD > P_VF ? P_PF_SD : P_VF) + 63) & ~63;
+  static constexpr int FOLD = WV_WAVES * P_STRIDE;
+  static constexpr int LDS_FLOATS = B::MAIN > FOLD ? B::MAIN : FOLD;
+};
+template <int D, int H, int A, bool SD> struct WvPick { using T = WvShape<D, H, A>; };
+template <int D, int H, int A> struct WvPick<D, H, A, true> { using T = WvShapeSD<D, H, A>; };
+#define SD_HALF_LOG_2PI_PLUS_HALF 1.4189385332046727f   /* k_gauss_sd.hip's constant: entropy of a unit normal */
+// SD: doubles per workgroup in the SECOND block of scalar rows (behind the n_wg x 8 block every head writes):
+//   0 log_std sum  1 sum of squares  2 max  3 -min   4 std sum  5 sum of squares  6 max  7 -min   8 samples   9..15 zero
+#define SD_SCAL 16
+
 __device__ __forceinline__ f32x4 lds4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // sum over the 16 lanes of a DPP row (same lane group g, all sample lanes j) with row rotations on the
 // VALU (no LDS round trips); every lane ends with the total, callers read lane j == 0
@@ -102,18 +119,31 @@ __device__ __forceinline__ float row_sum16(float v) {
 // `acts` rows are (N, 1)), the flat policy block has no logstd tail ([W1 b1 W2 b2 W3 b3]) and the per-sample entropy sum
 // leaves through the eighth column of the scalar row.  Only the block between the head MFMAs and `dout` differs: softmax,
 // log pi and entropy in k_categorical.hip's fixed arithmetic, d(loss)/d(logits) as in cat_losses_kernel.
-template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, bool CAT = false>
+// SD (policy pass, RT only): a state-dependent-std Gaussian head (policies.GuassianContPolicy;
+// torchrl/policies/continuous_policy.py:134-170).  The head has 2 a.A rows [mean | log_std] (MlpFlat order), the flat policy
+// block has no logstd tail.  Tile row k < 8 is mean k, tile row 8 + k is log_std k, whatever a.A is: lanes (j, g) and
+// (j, g ^ 2) hold a mean and its log_std, one xor-32 exchange apart.  The head row of tile row o -- o < 8 ? o : a.A + (o - 8)
+// -- appears where W3 / b3 are loaded and where dW3 / db3 go to the gradient image.  Per element the arithmetic is
+// gauss_sd_losses_kernel's (k_gauss_sd.hip); the per-sample statistics of log_std and std leave through a second block of
+// scalar rows (trl_ppo_sd_scalar_stride).
+template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
 __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_wg_net) {
-  using S = WvShape<D, H, A>;
+  using S = typename WvPick<D, H, A, SD>::T;
   constexpr bool WIDE = D > 17;                      // a second 16-feature group (features 16 .. 31) on the matrix pipe
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!CAT || (IS_PF && RT), "the categorical head is a policy pass of the runtime-dims kernels");
+  static_assert(!SD || (RT && !CAT), "the state-dependent-std head belongs to the runtime-dims kernels");
+  constexpr bool SDP = SD && IS_PF;                  // (SD's value pass differs in the stride of its gradient image only)
   constexpr int AS = CAT ? 1 : 0;                    // CAT: floats per stored action (0: the Gaussian's O)
   const int Dr = RT ? a.D : D;                       // input features = row stride of obs and of W1
   const int O = IS_PF ? (RT ? a.A : A) : 1;          // outputs
   // offsets inside the flat parameter block for the actual dims (MlpFlat, trl_mlp.h)
-  const int F_W1 = 0, F_B1 = H * Dr, F_W2 = F_B1 + H, F_B2 = F_W2 + H * H, F_W3 = F_B2 + H, F_B3 = F_W3 + O * H,
-            F_LS = F_B3 + O, F_END = CAT ? F_LS : F_LS + O;      // (no logstd tail behind a categorical head)
+  const int OH = SDP ? 2 * O : O;                     // head rows (SD: [mean | log_std])
+  const int F_W1 = 0, F_B1 = H * Dr, F_W2 = F_B1 + H, F_B2 = F_W2 + H * H, F_W3 = F_B2 + H, F_B3 = F_W3 + OH * H,
+            F_LS = F_B3 + OH, F_END = (CAT || SDP) ? F_LS : F_LS + O;      // (no logstd tail behind a categorical / SD head)
+  // SD: does tile row o exist, and which head row is it
+  auto sd_has = [&](int o) -> bool { return (o & 7) < O; };
+  auto sd_row = [&](int o) -> int { return o < 8 ? o : O + (o - 8); };
   const int PS = RT ? a.p_stride : S::P_STRIDE;      // floats of a partial row (the LDS images keep the template's stride)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, g = lane >> 4, i = j;
@@ -163,7 +193,8 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     oxt[q] = (unsigned)((4 * g + q) * Dr + (jv ? i : 0)) * 4u;
     oxq2[q] = (unsigned)(j * Dr + (fv2[q] ? 16 + 4 * g + q : 0)) * 4u;
     oxt2[q] = (unsigned)((4 * g + q) * Dr + (jv2 ? 16 + i : 0)) * 4u;
-    oa_[q] = CAT ? (unsigned)j * 4u : (unsigned)(j * O + (4 * g + q < O ? 4 * g + q : 0)) * 4u;
+    if constexpr (SDP) oa_[q] = (unsigned)(j * O + (4 * (g & 1) + q < O ? 4 * (g & 1) + q : 0)) * 4u;   // lanes g, g ^ 2: the same action
+    else oa_[q] = CAT ? (unsigned)j * 4u : (unsigned)(j * O + (4 * g + q < O ? 4 * g + q : 0)) * 4u;
   }
   auto ldb = [](const float* base, unsigned byte_off) -> float {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -218,7 +249,10 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     }
     if constexpr (IS_PF) {
       if constexpr (CAT) { lq[0] = a.acts[p]; lq[1] = lq[2] = lq[3] = 0.0f; }
-      else {
+      else if constexpr (SDP) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lq[r] = a.acts[p * O + (4 * (g & 1) + r < O ? 4 * (g & 1) + r : 0)];
+      } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) lq[r] = a.acts[p * O + (4 * g + r < O ? 4 * g + r : 0)];
       }
@@ -309,7 +343,11 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if constexpr (IS_PF) {
+      if constexpr (SDP) {
+        const int o = 4 * g + r;
+        w3h[so][r] = sd_has(i) ? gp[F_W3 + (sd_has(i) ? sd_row(i) : 0) * H + 16 * so + 4 * g + r] : 0.0f;   // head: W3[row of tile row i][k]
+        w3t[so][r] = sd_has(o) ? gp[F_W3 + (sd_has(o) ? sd_row(o) : 0) * H + row] : 0.0f;                   // dH2: W3[row of tile row o][own f]
+      } else if constexpr (IS_PF) {
         w3h[so][r] = (i < O) ? gp[F_W3 + (i < O ? i : 0) * H + 16 * so + 4 * g + r] : 0.0f;     // head: W3[o = i][k]
         const int o = 4 * g + r;
         w3t[so][r] = (o < O) ? gp[F_W3 + (o < O ? o : 0) * H + row] : 0.0f;                     // dH2: W3[k = o][own f]
@@ -324,11 +362,12 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int o = 4 * g + r;
-    const float raw = (IS_PF && !CAT && o < O) ? gp[F_LS + (o < O ? o : 0)] : 0.0f;
+    const float raw = (IS_PF && !CAT && !SDP && o < O) ? gp[F_LS + (o < O ? o : 0)] : 0.0f;
     lsv[r] = fminf(fmaxf(raw, -20.0f), 2.0f);                   // continuous_policy.py:8-9,185
     ivv[r] = __expf(-2.0f * lsv[r]);
     lspass[r] = (raw >= -20.0f && raw <= 2.0f) ? 1.0f : 0.0f;   // clamp passes gradient inside [-20, 2]
-    b3v[r] = (o < O) ? gp[F_B3 + (o < O ? o : 0)] : 0.0f;
+    if constexpr (SDP) b3v[r] = sd_has(o) ? gp[F_B3 + (sd_has(o) ? sd_row(o) : 0)] : 0.0f;      // (lsv / ivv are per tile, see the loop)
+    else b3v[r] = (o < O) ? gp[F_B3 + (o < O ? o : 0)] : 0.0f;
   }
   const float vb3 = IS_PF ? 0.0f : gp[F_B3];
 #pragma unroll
@@ -353,7 +392,10 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
   f32x4 gW1b[4];                                     // WIDE: dW1[f1 slice][16 <= k < 32]
   float gb1[4][4], gb2[4][4], gW1c[4][4];           // per-lane (own sample) partials: db1, db2, dW1[:, 16]
   float db3[4], dls[4], stv[7];
-  float ent_sum = 0.0f;                              // CAT: sum of the per-sample entropies (lanes g == 0)
+  float ent_sum = 0.0f;                              // CAT / SD: sum of the per-sample entropies (lanes g == 0)
+  // SD: the lane's log_std / std elements (lanes g < 2 own outputs 4g + r): sum, sum of squares, max, -min of each; the
+  // valid samples of lanes g == 0
+  float sdst[8] = {0.0f, 0.0f, -INFINITY, -INFINITY, 0.0f, 0.0f, -INFINITY, -INFINITY}, sd_cnt = 0.0f;
 #pragma unroll
   for (int x = 0; x < 4; ++x) {
     gW1[x] = gW3[x] = gW1b[x] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -495,6 +537,25 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
         }
         lp += __shfl_xor(lp, 16, 64);                                // the action's lane holds log pi, the other an exact zero
         ent += __shfl_xor(ent, 16, 64);                              // H = -sum_k p_k log p_k (logits 0..3 + 4..7)
+      } else if constexpr (SDP) {
+        // Lane (j, g < 2) holds means 4g + r of sample j, lane (j, g + 2) the raw log_std of the same outputs.  After the
+        // exchange ALL FOUR lane groups run the per-element arithmetic of gauss_sd_losses_kernel on (mean, raw) -- the same
+        // instructions on the same values, so both halves hold the same log pi -- and each keeps its own half of d(head).
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool has = 4 * (g & 1) + r < O;
+          const float mine = oa[r] + ob[r], oth = __shfl_xor(mine, 32, 64);
+          const float mean = g < 2 ? mine : oth, raw = g < 2 ? oth : mine;
+          lsv[r] = fminf(fmaxf(raw, -20.0f), 2.0f);
+          ivv[r] = __expf(-2.0f * lsv[r]);
+          lspass[r] = (raw >= -20.0f && raw <= 2.0f) ? 1.0f : 0.0f;   // d clamp / d raw
+          const float t = gauss_logp_term((valid && has) ? lin[r] : 0.0f, has ? mean : 0.0f, ivv[r], lsv[r], a.tanh_action, zc[r]);
+          lp += has ? t : 0.0f;
+          ent += has ? SD_HALF_LOG_2PI_PLUS_HALF + lsv[r] : 0.0f;
+          zc[r] = has ? zc[r] : 0.0f;
+        }
+        lp += __shfl_xor(lp, 16, 64);                                // outputs 0..3 + 4..7, in both halves
+        ent += __shfl_xor(ent, 16, 64);
       } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                                  // branch-free: lanes without an output compute on zeros
@@ -513,12 +574,12 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       if (a.loss_mode == TRL_LOSS_A2C) {                            // L = -mean(log pi * adv) (a2c.py:69-70)
         ratio = 1.0f;
         s1 = s2 = lp * advn;
-        g_lp = (valid && g < 2) ? -advn * inv_b : 0.0f;
+        g_lp = (valid && (SDP || g < 2)) ? -advn * inv_b : 0.0f;
       } else {                                                     // clipped surrogate (ppo.py:58-66)
         ratio = __expf(lp - lin[5]);
         s1 = ratio * advn;
         s2 = fminf(fmaxf(ratio, 1.0f - a.clip_para), 1.0f + a.clip_para) * advn;
-        g_lp = (valid && g < 2 && s1 <= s2) ? -advn * ratio * inv_b : 0.0f;
+        g_lp = (valid && (SDP || g < 2) && s1 <= s2) ? -advn * ratio * inv_b : 0.0f;
       }
       WCLK(20)
       float dout[4];
@@ -533,6 +594,24 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
           if (g < 2) DOS[(4 * g + r) * LDT + j] = dout[r];           // dout^T[o][s] for dW3
         }
         if (valid && g == 0) ent_sum += ent;
+      } else if constexpr (SDP) {
+        // tile rows 4g + r: d(loss)/d(mean) in lanes g < 2, d(loss)/d(raw log_std) in lanes g >= 2 (a clamped element: gate
+        // 0, an exact zero); both halves go to the DOS rows of dW3 / dH2 and to db3
+        const float ce = a.entropy_coeff * inv_b;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool own = valid && 4 * (g & 1) + r < O;
+          const float dm = g_lp * zc[r] * ivv[r], dr = lspass[r] * (g_lp * (zc[r] * zc[r] * ivv[r] - 1.0f) - ce);
+          dout[r] = own ? (g < 2 ? dm : dr) : 0.0f;
+          db3[r] += dout[r];
+          DOS[(4 * g + r) * LDT + j] = dout[r];                      // dout^T[tile row][s] for dW3
+          if (own && g < 2) {                                        // log_std/*, std/* over the elements (ppo.py:83-86, a2c.py:96-101)
+            const float x = lsv[r], ex = expf(x);
+            sdst[0] += x; sdst[1] = fmaf(x, x, sdst[1]); sdst[2] = fmaxf(sdst[2], x); sdst[3] = fmaxf(sdst[3], -x);
+            sdst[4] += ex; sdst[5] = fmaf(ex, ex, sdst[5]); sdst[6] = fmaxf(sdst[6], ex); sdst[7] = fmaxf(sdst[7], -ex);
+          }
+        }
+        if (valid && g == 0) { ent_sum += ent; sd_cnt += 1.0f; }
       } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -705,7 +784,8 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       if (j == 0) { if (f16) gimg[F_W1 + f * Dr + 16] = c16; gimg[F_B1 + f] = s1; gimg[F_B2 + f] = s2; }
       if constexpr (IS_PF) {
         const int o = 4 * g + r;                                   // gW3 rows are outputs
-        if (o < O) gimg[F_W3 + o * H + 16 * so + j] = gW3[so][r];
+        if constexpr (SDP) { if (sd_has(o)) gimg[F_W3 + sd_row(o) * H + 16 * so + j] = gW3[so][r]; }
+        else if (o < O) gimg[F_W3 + o * H + 16 * so + j] = gW3[so][r];
       } else {
         const float w3s = row_sum16(gW3[so][r]);
         if (j == 0) gimg[F_W3 + f] = w3s;
@@ -715,7 +795,8 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
   for (int r = 0; r < 4; ++r) {
     const int o = 4 * g + r;
     const float b3 = row_sum16(db3[r]), dl = row_sum16(dls[r]);
-    if (j == 0 && o < O) {
+    if constexpr (SDP) { if (j == 0 && sd_has(o)) gimg[F_B3 + sd_row(o)] = b3; }
+    else if (j == 0 && o < O) {
       gimg[F_B3 + o] = b3;
       if (IS_PF && !CAT) gimg[F_LS + o] = dl;
     }
@@ -744,10 +825,20 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     const float v2 = wave_max(own ? stv[2] : -INFINITY), v3 = wave_max(own ? stv[3] : -INFINITY),
                 v4 = wave_max(own ? stv[4] : -INFINITY), v5 = wave_max(own ? stv[5] : -INFINITY);
     double v7 = 0.0;                                   // CAT: the entropy sum rides in the row's free eighth column
-    if constexpr (CAT) v7 = wave_sum(own ? (double)ent_sum : 0.0);
+    if constexpr (CAT || SDP) v7 = wave_sum(own ? (double)ent_sum : 0.0);
     if (lane == 0) {
       double* p = sred + wave * 8;
       p[0] = v0; p[1] = v1; p[2] = v2; p[3] = v3; p[4] = v4; p[5] = v5; p[6] = v6; p[7] = v7;
+    }
+    if constexpr (SDP) {                                // the wave's element statistics and its count of samples
+      double e[SD_SCAL];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) e[k] = (k & 2) ? (double)wave_max(sdst[k]) : wave_sum((double)sdst[k]);
+      e[8] = wave_sum((double)sd_cnt);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < SD_SCAL; ++k) sred[WV_WAVES * 8 + wave * SD_SCAL + k] = k < 9 ? e[k] : 0.0;
+      }
     }
   }
   __syncthreads();
@@ -758,6 +849,17 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       r = (tid >= 2 && tid <= 5) ? fmax(r, o) : r + o;
     }
     a.scal_partial[(size_t)wg * 8 + tid] = r;
+  }
+  if constexpr (SDP) {                                  // second block of scalar rows, behind the n_wg x 8 of every head
+    if (tid >= 64 && tid < 64 + SD_SCAL) {
+      const int k = tid - 64;
+      double r = sred[WV_WAVES * 8 + k];
+      for (int w = 1; w < WV_WAVES; ++w) {
+        const double o = sred[WV_WAVES * 8 + w * SD_SCAL + k];
+        r = (k < 8 && (k & 2)) ? fmax(r, o) : r + o;
+      }
+      a.scal_partial[(size_t)a.n_wg * 8 + (size_t)wg * SD_SCAL + k] = r;
+    }
   }
 }
 
@@ -891,10 +993,40 @@ __device__ __noinline__ void fold_entropy_stats(const double* __restrict__ base,
   }
 }
 
+// one wave, state-dependent-std head: the entropy sum (eighth column of the policy's scalar rows) into info[20], and
+// log_std/{mean,std,max,min}, std/{...} over all samples x n_act elements from the second block of scalar rows (`sd`: SD_SCAL
+// doubles per workgroup, see there) into info[8..11] / info[16..19] -- the row trl_gauss_sd_losses_f32 writes.  A lane adds
+// its rows lane, lane + 64, ... in that order.  (out of line, like the others: see ppo_reduce_adam_kernel's register bound)
+__device__ __noinline__ void fold_sd_stats(const double* __restrict__ base, const double* __restrict__ sd, int nrow, int n_act,
+                                           int lane, double* __restrict__ info) {
+  double v[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) v[k] = (k < 8 && (k & 2)) ? -INFINITY : 0.0;
+  for (int w = lane; w < nrow; w += 64) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const double o = sd[(size_t)w * SD_SCAL + k];
+      v[k] = (k < 8 && (k & 2)) ? fmax(v[k], o) : v[k] + o;
+    }
+    v[9] += base[(size_t)w * 8 + 7];
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) v[k] = (k < 8 && (k & 2)) ? wave_max(v[k]) : wave_sum(v[k]);
+  if (lane == 0) {
+    const double n = v[8] * (double)n_act, lm = v[0] / n, em = v[4] / n;
+    info[8] = lm; info[9] = n > 1.0 ? sqrt(fmax((v[1] - v[0] * lm) / (n - 1.0), 0.0)) : NAN;
+    info[10] = v[2]; info[11] = -v[3];
+    info[16] = em; info[17] = n > 1.0 ? sqrt(fmax((v[5] - v[4] * em) / (n - 1.0), 0.0)) : NAN;
+    info[18] = v[6]; info[19] = -v[7];
+    info[20] = v[9];
+  }
+}
+
 // returns (wave 0 lanes) the reduced gradient value of chunk `bx` (64 parameters) of network `net`, 0 outside the parameter
 // range; `stats`: this call also takes the network's scalar statistics (waves 2 / 3)
 // CAT: the policy block has no logstd tail (logstd is null) and wave 3 folds the entropy column instead
-template <bool CAT = false>
+// SD: no logstd tail either; wave 3 folds the entropy column and the second block of scalar rows (behind the n_wg x 8)
+template <bool CAT = false, bool SD = false>
 __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ partial,
                                                   const double* __restrict__ scal, int n_wg, int n_pf,
                                                   int p_stride, int p_pf, int p_vf,
@@ -921,7 +1053,10 @@ __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ part
   // path of the blocks whose 64 parameters matter: wave 2 its network's statistics, wave 3 of the policy's block log_std
   // and std.
   if (stats && wave == 2) fold_scalar_stats(scal + (size_t)row0 * 8, nrow, net, lane, info);
-  if constexpr (CAT) {
+  if constexpr (SD) {
+    if (stats && net == 0 && wave == 3)
+      fold_sd_stats(scal + (size_t)row0 * 8, scal + (size_t)n_wg * 8 + (size_t)row0 * SD_SCAL, nrow, n_act, lane, info);
+  } else if constexpr (CAT) {
     if (stats && net == 0 && wave == 3) fold_entropy_stats(scal + (size_t)row0 * 8, nrow, lane, info);
   } else {
     if (stats && net == 0 && wave == 3 && logstd) fold_logstd_stats(logstd, n_act, lane, info);
@@ -929,13 +1064,13 @@ __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ part
   return gval;
 }
 
-template <bool CAT = false>
+template <bool CAT = false, bool SD = false>
 __global__ __launch_bounds__(64 * RED_WAVES) void ppo_reduce_kernel(const float* __restrict__ partial,
                                                          const double* __restrict__ scal, int n_wg, int n_pf,
                                                          int p_stride, int p_pf, int p_vf,
                                                          const float* __restrict__ logstd, int n_act,
                                                          float* __restrict__ grads, double* __restrict__ info) {
-  ppo_reduce_block<CAT>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
+  ppo_reduce_block<CAT, SD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
                         blockIdx.x == gridDim.x - 1);
 }
 
@@ -1040,7 +1175,7 @@ __device__ __forceinline__ void adam_element(const AdamDev& a, int e, float gr) 
 // blocks -- 4 waves per SIMD -- resident beside each other.  With the statistics inlined into the job loop the kernel took
 // 156 registers: the second rank's blocks found no room next to the first's, its norm rendezvous could not complete, and
 // both ranks sat out their time-outs -- round 6, caught by tests/test_bench_multirank_gpu.py)
-template <bool LOOP, bool CAT = false>                // LOOP false: the grid has one block per job (no job loop: the common launch)
+template <bool LOOP, bool CAT = false, bool SD = false>   // LOOP false: the grid has one block per job (no job loop: the common launch)
 __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(const float* __restrict__ partial,
                                                               const double* __restrict__ scal, int n_wg, int n_pf,
                                                               int p_stride, int p_pf, int p_vf,
@@ -1084,7 +1219,7 @@ __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(cons
   for (int j = blk; j < (LOOP ? n_jobs : blk + 1); j += LOOP ? grid : 1) {
     const int net = j / nb, bx = j - net * nb;
     if (j != blk) __syncthreads();                                // the fold's LDS image is read by wave 0 of the previous job
-    float gval = ppo_reduce_block<CAT>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
+    float gval = ppo_reduce_block<CAT, SD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
     if (wave == 0) {
       if (xrank) {
         // C1 of SURVEY.md 8(e) inside the launch: every rank pushes its 64 folded values into its slot on all ranks and
@@ -1181,15 +1316,16 @@ __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(cons
 }
 
 // ---------------------------------------------------------------- the gradient launch: one network pass per workgroup
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
 __global__ __launch_bounds__(WV_THREADS, 1) void ppo_grad_wave_kernel(PpoDev a) {
   static_assert(!CAT || RT, "categorical head: runtime-dims tiles");
+  static_assert(!SD || (RT && !CAT), "state-dependent-std head: runtime-dims tiles");
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef TRL_CHAIN_CLK                                  /* tools/time_chains.py: when did this workgroup start and end (100 MHz) */
   const unsigned long long clk0 = wall_clock64();
 #endif
-  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, CAT>(a, lds, blockIdx.x, a.n_pf);
-  else                          ppo_wave_pass<D, H, A, ACT, false, CONTIG, RT>(a, lds, blockIdx.x - a.n_pf, a.n_wg - a.n_pf);
+  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, CAT, SD>(a, lds, blockIdx.x, a.n_pf);
+  else                          ppo_wave_pass<D, H, A, ACT, false, CONTIG, RT, false, SD>(a, lds, blockIdx.x - a.n_pf, a.n_wg - a.n_pf);
 #ifdef TRL_CHAIN_CLK
   __syncthreads();
   if (threadIdx.x == 0) {                             // the row's unused 8th scalar and the last three padding floats of the partial row
@@ -1265,25 +1401,51 @@ extern "C" int trl_ppo_cat_partial_stride(int D, int H, int A) {
   trl_set_error("trl_ppo_cat_partial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8)", D, H, A);
   return TRL_EUNSUPPORTED;
 }
-static int ppo_stride_for(int D, int H, int A, bool cat) { return cat ? trl_ppo_cat_partial_stride(D, H, A) : trl_ppo_partial_stride(D, H, A); }
+
+// State-dependent-std head (ppo_wave_pass<..., SD = true>): the runtime-dims tiles only; the flat policy block is
+// [W1 b1 W2 b2 W3 b3] with 2A head rows [mean | log_std] (no logstd tail), up to 1040 head floats against the Gaussian's 528.
+#define HEAD_GAUSS 0
+#define HEAD_CAT 1
+#define HEAD_SD 2
+static bool ppo_sd_shape(int D, int H, int A) { return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8; }
+extern "C" int trl_ppo_sd_supported(int D, int H, int A, int act) {
+  return (ppo_sd_shape(D, H, A) && (act == TRL_ACT_TANH || act == TRL_ACT_RELU)) ? 1 : 0;
+}
+static int ppo_p_pf_head(int D, int H, int A, int head) { return head == HEAD_SD ? ppo_p_pf(D, H, 2 * A, true) : ppo_p_pf(D, H, A, head == HEAD_CAT); }
+extern "C" int trl_ppo_sd_partial_stride(int D, int H, int A) {
+  if (ppo_sd_shape(D, H, A)) {
+    const int p_pf = ppo_p_pf_head(D, H, A, HEAD_SD), p_vf = ppo_p_vf(D, H);
+    return ((p_pf > p_vf ? p_pf : p_vf) + 63) & ~63;
+  }
+  trl_set_error("trl_ppo_sd_partial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, 1 <= A <= 8)", D, H, A);
+  return TRL_EUNSUPPORTED;
+}
+// doubles of scal_partial per workgroup: the n_wg x 8 block of every head, then n_wg x SD_SCAL (see SD_SCAL)
+extern "C" int trl_ppo_sd_scalar_stride(void) { return 8 + SD_SCAL; }
+static_assert(WvShapeSD<17, 64, 8>::P_STRIDE == 6400 && WvShapeSD<32, 64, 8>::P_STRIDE == 7360, "SD image strides at A = 8");
+static_assert(WvShapeSD<32, 64, 8>::LDS_FLOATS * sizeof(float) <= 160 * 1024, "SD fold images fit the LDS");
+static int ppo_stride_for(int D, int H, int A, int head) {
+  return head == HEAD_SD ? trl_ppo_sd_partial_stride(D, H, A)
+                         : (head == HEAD_CAT ? trl_ppo_cat_partial_stride(D, H, A) : trl_ppo_partial_stride(D, H, A));
+}
 
 // Kernel generations that were built and measured on MI355X before this one (profiles/README.md): groups of
 // 4 waves per tile with LDS rendezvous (85 us per 65 536-sample minibatch), this wave-per-tile kernel (64 us),
 // and a PAIR of waves per tile with two waves per SIMD (75 us) -- on gfx950 the fp32 MFMA and the VALU do not
 // overlap across the two waves of a SIMD (tools/ubench/mfma_valu.hip: an MFMA-only wave and a VALU-only wave
 // on one SIMD take the SUM of their times), so a second wave only adds its duplicated loss / fetch work.
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
 static int launch_ppo_v(const PpoDev& d, hipStream_t s) {
-  using S = WvShape<D, H, A>;
+  using S = typename WvPick<D, H, A, SD>::T;
   const size_t lds = S::LDS_FLOATS * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT>,
+    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT, SD>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { trl_set_error("ppo_grad: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_set = true;
   }
-  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d);
+  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT, SD>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d);
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
@@ -1297,6 +1459,12 @@ template <int D, int ACT>
 static int launch_ppo_cat(const PpoDev& d, hipStream_t s) {
   return (d.N % 16 == 0) ? launch_ppo_v<D, 64, 8, ACT, true, true, true>(d, s)
                          : launch_ppo_v<D, 64, 8, ACT, false, true, true>(d, s);
+}
+
+template <int D, int ACT>
+static int launch_ppo_sd(const PpoDev& d, hipStream_t s) {
+  return (d.N % 16 == 0) ? launch_ppo_v<D, 64, 8, ACT, true, true, false, true>(d, s)
+                         : launch_ppo_v<D, 64, 8, ACT, false, true, false, true>(d, s);
 }
 
 // Policy / value split of the grid.  A policy tile costs more than a value tile (head, log-prob loss,
@@ -1321,8 +1489,14 @@ extern "C" int trl_ppo_wg_split(int D, int H, int A, int n_tiles, int n_wg) {
 // as separate, concurrent launch sequences)
 static int resolve_pf_wgs(int n_wg, int n_wg_pf) { return n_wg_pf < 0 ? 0 : (n_wg_pf > 0 ? n_wg_pf : n_wg / 2); }
 
-static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, bool cat = false) {
+static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HEAD_GAUSS) {
+  const bool cat = head == HEAD_CAT, sd = head == HEAD_SD;
   if (!p) { trl_set_error("ppo_grad: null descriptor"); return TRL_EINVAL; }
+  if (sd && !trl_ppo_sd_supported(p->D, p->H, p->A, p->act)) {
+    trl_set_error("ppo_sd_grad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh / ReLU)",
+                  p->D, p->H, p->A, p->act);
+    return TRL_EUNSUPPORTED;
+  }
   if (cat && !trl_ppo_cat_supported(p->D, p->H, p->A, p->act)) {
     trl_set_error("ppo_cat_grad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU)",
                   p->D, p->H, p->A, p->act);
@@ -1342,7 +1516,7 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, bool cat = fa
   const int D = p->D, H = p->H, A = p->A;
   TRL_REQUIRE(((uintptr_t)p->partial & 15) == 0 && (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 3) == 0,
               "partial rows must be 16-byte aligned, parameter blocks 4-byte aligned");
-  TRL_REQUIRE(cat || !SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
+  TRL_REQUIRE(cat || sd || !SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
               "parameter blocks of the benchmark shape must be 16-byte aligned");
   PpoDev d;
   d.obs = p->obs; d.acts = p->acts; d.advs = p->advs; d.rets = p->rets; d.old_values = p->old_values;
@@ -1359,6 +1533,11 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, bool cat = fa
     d.tanh_action = 0;
     if (D <= 17) return p->act == TRL_ACT_TANH ? launch_ppo_cat<17, TRL_ACT_TANH>(d, s) : launch_ppo_cat<17, TRL_ACT_RELU>(d, s);
     return p->act == TRL_ACT_TANH ? launch_ppo_cat<32, TRL_ACT_TANH>(d, s) : launch_ppo_cat<32, TRL_ACT_RELU>(d, s);
+  }
+  if (sd) {                                           // acts is (rows, N, A), pf_params [W1 b1 W2 b2 W3 b3] with 2A head rows
+    d.p_stride = trl_ppo_sd_partial_stride(D, H, A);
+    if (D <= 17) return p->act == TRL_ACT_TANH ? launch_ppo_sd<17, TRL_ACT_TANH>(d, s) : launch_ppo_sd<17, TRL_ACT_RELU>(d, s);
+    return p->act == TRL_ACT_TANH ? launch_ppo_sd<32, TRL_ACT_TANH>(d, s) : launch_ppo_sd<32, TRL_ACT_RELU>(d, s);
   }
   if (SHAPE_IS(17, 64, 6)) {
     d.p_stride = PpoShape<17, 64, 6>::P_STRIDE;
@@ -1381,16 +1560,26 @@ extern "C" int trl_ppo_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream
 // The same launch for a categorical policy (2 <= A <= 8 logits): acts is (rows, N, 1) -- the action index as a float --,
 // pf_params is [W1 b1 W2 b2 W3 b3], tanh_action is ignored, partial rows are trl_ppo_cat_partial_stride floats and the
 // policy workgroups' scalar rows carry the entropy sum in their eighth column (trl_ppo_cat_reduce_*_f32 fold it).
-extern "C" int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, stream, true); }
+extern "C" int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, stream, HEAD_CAT); }
+// The same launch for a state-dependent-std Gaussian policy (1 <= A <= 8 action dimensions, a head of 2A rows
+// [mean | log_std]): acts is (rows, N, A), pf_params is [W1 b1 W2 b2 W3 b3], partial rows are trl_ppo_sd_partial_stride
+// floats and scal_partial holds n_wg x trl_ppo_sd_scalar_stride() doubles: the n_wg x 8 block (entropy sum in the policy
+// rows' eighth column), then the policy workgroups' log_std / std statistics (trl_ppo_sd_reduce_*_f32 fold both).
+extern "C" int trl_ppo_sd_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, stream, HEAD_SD); }
 
 static int launch_reduce(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
-                         const float* pf_params, float* grads, double* info, void* stream, bool cat) {
+                         const float* pf_params, float* grads, double* info, void* stream, int head) {
+  const bool cat = head == HEAD_CAT;
   TRL_REQUIRE(partial && scal_partial && grads && info, "null pointer");
   TRL_REQUIRE(n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg, "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
-  const int ps = ppo_stride_for(D, H, A, cat);
+  const int ps = ppo_stride_for(D, H, A, head);
   if (ps < 0) return ps;
-  const int p_pf = ppo_p_pf(D, H, A, cat), p_vf = ppo_p_vf(D, H);
-  if (cat)                                            // no logstd tail: nothing of it is folded, the entropy column is
+  const int p_pf = ppo_p_pf_head(D, H, A, head), p_vf = ppo_p_vf(D, H);
+  if (head == HEAD_SD)                                // no logstd tail; wave 3 folds the entropy column and the second scalar block
+    hipLaunchKernelGGL((ppo_reduce_kernel<false, true>), dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
+                       (const float*)nullptr, A, grads, info);
+  else if (cat)                                            // no logstd tail: nothing of it is folded, the entropy column is
     hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
                        partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
                        (const float*)nullptr, A, grads, info);
@@ -1403,13 +1592,20 @@ static int launch_reduce(const float* partial, const double* scal_partial, int n
 }
 extern "C" int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
                                   int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
-  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, false);
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, HEAD_GAUSS);
 }
 // categorical head: pf_params is accepted for symmetry and not read (there is no logstd); info[20] = entropy sum
 extern "C" int trl_ppo_cat_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
                                       int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
   (void)pf_params;
-  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, true);
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, HEAD_CAT);
+}
+// state-dependent-std head: pf_params is accepted for symmetry and not read; info[8..11] / info[16..19] = log_std / std
+// statistics over all samples x A elements, info[20] = entropy sum (trl_gauss_sd_losses_f32's row)
+extern "C" int trl_ppo_sd_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
+                                     int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
+  (void)pf_params;
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, HEAD_SD);
 }
 
 static int fill_adam(const trl_adam_t* p, AdamDev& d) {
@@ -1444,15 +1640,16 @@ extern "C" int trl_ppo_reduce_adam_workspace(int D, int H, int A) {
 
 static int launch_reduce_adam(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
                               float* grads, double* info, const trl_adam_t* adam, float* workspace, const XrArgs* xr,
-                              int max_blocks, void* stream, int only_net = -1, bool cat = false) {
+                              int max_blocks, void* stream, int only_net = -1, int head = HEAD_GAUSS) {
+  const bool cat = head == HEAD_CAT;
   TRL_REQUIRE(partial && scal_partial && grads && info && workspace, "null pointer");
   TRL_REQUIRE(only_net >= 0 ? n_wg >= 1 : (n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg), "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
-  const int ps = ppo_stride_for(D, H, A, cat);
+  const int ps = ppo_stride_for(D, H, A, head);
   if (ps < 0) return ps;
   AdamDev d;
   int rc = fill_adam(adam, d);
   if (rc) return rc;
-  const int p_pf = ppo_p_pf(D, H, A, cat), p_vf = ppo_p_vf(D, H);
+  const int p_pf = ppo_p_pf_head(D, H, A, head), p_vf = ppo_p_vf(D, H);
   TRL_REQUIRE(adam->n_groups == 2 && adam->group_sizes[0] == p_pf && adam->group_sizes[1] == p_vf,
               "optimiser groups must be [policy | value] of this shape");
   TRL_REQUIRE(adam->grads == grads, "adam->grads must be the reduce output");
@@ -1464,6 +1661,18 @@ static int launch_reduce_adam(const float* partial, const double* scal_partial, 
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
   const int n_pf = only_net == 0 ? n_wg : (only_net == 1 ? 0 : resolve_pf_wgs(n_wg, n_wg_pf));
   const int jobs = (only_net >= 0 ? 1 : 2) * trl_ceil_div(ps, RED_CHUNK);
+  if (head == HEAD_SD) {                              // no logstd pointer; wave 3 folds the entropy column and the second scalar block
+    if (grid == jobs)
+      hipLaunchKernelGGL((ppo_reduce_adam_kernel<false, false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
+                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
+    else
+      hipLaunchKernelGGL((ppo_reduce_adam_kernel<true, false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
+                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
+                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
+    TRL_LAUNCH_CHECK();
+    return TRL_OK;
+  }
   if (cat) {                                          // no logstd pointer: its statistics do not exist; wave 3 folds the entropy column
     if (grid == jobs)
       hipLaunchKernelGGL((ppo_reduce_adam_kernel<false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
@@ -1518,13 +1727,33 @@ extern "C" int trl_ppo_cat_reduce_adam_workspace(int D, int H, int A) {
 extern "C" int trl_ppo_cat_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
                                            int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
                                            float* workspace, void* stream) {
-  return launch_reduce_adam(partial, scal_partial, n_wg, n_wg_pf, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, -1, true);
+  return launch_reduce_adam(partial, scal_partial, n_wg, n_wg_pf, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, -1, HEAD_CAT);
 }
 extern "C" int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,
                                                int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
                                                float* workspace, void* stream) {
   TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
-  return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net, true);
+  return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net, HEAD_CAT);
+}
+
+// The state-dependent-std head's folds (rows of trl_ppo_sd_minibatch_grad_f32; same row fold order, norm rendezvous and Adam
+// arithmetic; optimiser groups [policy with 2A head rows, no logstd | value]).  The `_net` fold of a policy-only launch reads
+// the second scalar block behind THAT launch's n_wg x 8.  The cross-rank variants do not exist for this head.
+extern "C" int trl_ppo_sd_reduce_adam_workspace(int D, int H, int A) {
+  const int ps = trl_ppo_sd_partial_stride(D, H, A);
+  if (ps < 0) return ps;
+  return 16 + 4 * trl_ceil_div(ps, RED_CHUNK);
+}
+extern "C" int trl_ppo_sd_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
+                                          int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
+                                          float* workspace, void* stream) {
+  return launch_reduce_adam(partial, scal_partial, n_wg, n_wg_pf, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, -1, HEAD_SD);
+}
+extern "C" int trl_ppo_sd_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,
+                                              int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
+                                              float* workspace, void* stream) {
+  TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
+  return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net, HEAD_SD);
 }
 
 // Env shards on several ranks: the same launch with the gradient SUM over ranks between the fold and the clip
