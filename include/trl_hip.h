@@ -1005,6 +1005,29 @@ int trl_select_on_flag_f32(const int32_t* flag, const float* a, const float* b, 
 int trl_select_on_mask_f32(const uint8_t* mask, int N, const float* a, const float* b, float* out, int64_t n,
                            void* stream);
 
+/* --- LayerNorm layers of `add_ln=True` MLPs (torchrl/networks/base.py:29-41, nets.py:28-37; csrc/k_layernorm.hip) ---------
+ * The reference's module list is [Linear, act, LayerNorm] * n: the norm follows the activation, runs over the feature axis
+ * with the biased variance and eps 1e-5, and has an affine weight (gamma) and bias (beta).  1 <= H <= 1024
+ * (trl_layernorm_supported); all tensors fp32, contiguous, caller-owned.
+ *   fwd   a (M, H), gamma (H), beta (H) -> y (M, H) = gamma * (a - mean) * rstd + beta, rstd = 1 / sqrt(var + 1e-5);
+ *         stats (M, 2) = per-row (mean, rstd) for the backward pass.  Mean and variance are two passes over the row in fp32.
+ *   bwd   dy (M, H), a, stats, gamma, act (TRL_ACT_* of the layer that produced a; TRL_ACT_NONE: no gate) ->
+ *         dz (M, H) = rstd * (g - mean_row(g) - xhat * mean_row(g * xhat)) * act'(a) with xhat = (a - mean) * rstd,
+ *         g = dy * gamma -- already gated for the layer below (dz may be dy); dgamma (H) = sum_rows dy * xhat,
+ *         dbeta (H) = sum_rows dy, from per-workgroup slabs in `workspace` (trl_layernorm_bwd_workspace(M, H) floats) added
+ *         in a fixed order by a second launch: no atomics, the same bits on every run.
+ * The trunk's LAST LayerNorm is replaced by a second activation (base.py:39-40); for Tanh that is tanh(tanh(z)):
+ *   act2_fwd   t2[0..n) = act(t1)                          (ReLU is idempotent: callers launch nothing)
+ *   act2_bwd   dz[0..n) = d * act'(t2) * act'(t1), through the stored outputs t1 and t2 (dz may be d). */
+int trl_layernorm_supported(int H);
+int trl_layernorm_fwd_f32(const float* a, const float* gamma, const float* beta, float* y, float* stats, int M, int H,
+                          void* stream);
+int trl_layernorm_bwd_workspace(int M, int H);
+int trl_layernorm_bwd_f32(const float* dy, const float* a, const float* stats, const float* gamma, int act, float* dz,
+                          float* dgamma, float* dbeta, float* workspace, int M, int H, void* stream);
+int trl_act2_fwd_f32(const float* t1, float* t2, int64_t n, int act, void* stream);
+int trl_act2_bwd_f32(const float* d, const float* t1, const float* t2, float* dz, int64_t n, int act, void* stream);
+
 /* --- K18: running observation normaliser (torchrl/env/base_wrapper.py:44-121) --------------
  * state = {mean[D], var[D], count} fp64 on the device (Normalizer._mean/_var/_count; a fresh
  * normaliser is mean 0, var 1, count 1e-4, :64-69).  sums = {sum x [D], sum x^2 [D], n}.

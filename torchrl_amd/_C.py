@@ -313,6 +313,12 @@ SIGNATURES = {
                                        + [C.c_int] * 3 + [C.c_void_p]),
     "trl_linear_bwd_weight_group_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
                                         + [C.c_int] * 3 + [C.c_void_p]),
+    "trl_layernorm_supported": (C.c_int, [C.c_int]),
+    "trl_layernorm_fwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
+    "trl_layernorm_bwd_workspace": (C.c_int, [C.c_int, C.c_int]),
+    "trl_layernorm_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
+    "trl_act2_fwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "trl_act2_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "trl_outer_gate_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "trl_mlp3_forward_ok": (C.c_int, [C.c_int] * 4),
     "trl_mlp3_forward_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
@@ -851,6 +857,77 @@ def gauss_sd_logp(head, acts, tanh_action, out=None, ent=None, want_ent=False):
                                       dev_ptr(ent, name="ent", allow_none=True), B, A, int(bool(tanh_action)),
                                       stream_ptr(head.device)), "trl_gauss_sd_logp_f32")
     return out, ent
+
+
+LN_MAX_H = 1024
+
+
+def _ln_dims(a, what):
+    if a.dim() != 2:
+        raise TrlError("%s: expected a (M, H) tensor, got %s" % (what, tuple(a.shape)))
+    M, H = int(a.shape[0]), int(a.shape[1])
+    if not lib().trl_layernorm_supported(H):
+        raise TrlError("%s: LayerNorm kernels carry rows of 1 <= H <= %d features, got H = %d" % (what, LN_MAX_H, H))
+    return M, H
+
+
+def layernorm_fwd(a, gamma, beta, y=None, stats=None):
+    """y = gamma * (a - mean) * rstd + beta over the last axis of a (M, H) (biased variance, eps 1e-5);
+    returns (y, stats (M, 2) = per-row (mean, rstd))."""
+    M, H = _ln_dims(a, "layernorm_fwd")
+    if int(gamma.numel()) != H or int(beta.numel()) != H:
+        raise TrlError("layernorm_fwd: gamma / beta hold H = %d values" % H)
+    if y is None:
+        y = torch.empty((M, H), dtype=torch.float32, device=a.device)
+    if stats is None:
+        stats = torch.empty((M, 2), dtype=torch.float32, device=a.device)
+    if tuple(y.shape) != (M, H) or int(stats.numel()) != 2 * M:
+        raise TrlError("layernorm_fwd: y is (M, H) and stats (M, 2)")
+    check(lib().trl_layernorm_fwd_f32(dev_ptr(a, name="a"), dev_ptr(gamma, name="gamma"), dev_ptr(beta, name="beta"),
+                                      dev_ptr(y, name="y"), dev_ptr(stats, name="stats"), M, H, stream_ptr(a.device)),
+          "trl_layernorm_fwd_f32")
+    return y, stats
+
+
+def layernorm_bwd(dy, a, stats, gamma, act, dgamma, dbeta, dz=None, workspace=None):
+    """The backward pass of `layernorm_fwd`; `act` (ACT_*): the activation that produced `a` -- the returned dz (M, H) is the
+    gradient at that layer's pre-activation (ACT_NONE: at `a` itself).  dgamma / dbeta (H) are written in place."""
+    M, H = _ln_dims(a, "layernorm_bwd")
+    if tuple(dy.shape) != (M, H) or int(stats.numel()) != 2 * M or any(int(t.numel()) != H for t in (gamma, dgamma, dbeta)):
+        raise TrlError("layernorm_bwd: dy is (M, H) = %s, stats (M, 2), gamma / dgamma / dbeta (H)" % ((M, H),))
+    need = lib().trl_layernorm_bwd_workspace(M, H)
+    if need < 0:
+        raise TrlError("layernorm_bwd: unsupported sizes M=%d H=%d" % (M, H))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.float32, device=a.device)
+    if dz is None:
+        dz = torch.empty((M, H), dtype=torch.float32, device=a.device)
+    check(lib().trl_layernorm_bwd_f32(dev_ptr(dy, name="dy"), dev_ptr(a, name="a"), dev_ptr(stats, name="stats"),
+                                      dev_ptr(gamma, name="gamma"), int(act), dev_ptr(dz, name="dz"),
+                                      dev_ptr(dgamma, name="dgamma"), dev_ptr(dbeta, name="dbeta"),
+                                      dev_ptr(workspace, name="workspace"), M, H, stream_ptr(a.device)),
+          "trl_layernorm_bwd_f32")
+    return dz
+
+
+def act2_fwd(t1, act, out=None):
+    """The second activation of a LayerNorm trunk's last hidden layer: act(t1), elementwise."""
+    if out is None:
+        out = torch.empty_like(t1)
+    check(lib().trl_act2_fwd_f32(dev_ptr(t1, name="t1"), dev_ptr(out, name="out"), int(t1.numel()), int(act),
+                                 stream_ptr(t1.device)), "trl_act2_fwd_f32")
+    return out
+
+
+def act2_bwd(d, t1, t2, act, out=None):
+    """d * act'(t2) * act'(t1): the gradient at the pre-activation under two stacked activations."""
+    if d.shape != t1.shape or t1.shape != t2.shape:
+        raise TrlError("act2_bwd: d, t1 and t2 have one shape")
+    if out is None:
+        out = torch.empty_like(d)
+    check(lib().trl_act2_bwd_f32(dev_ptr(d, name="d"), dev_ptr(t1, name="t1"), dev_ptr(t2, name="t2"), dev_ptr(out, name="out"),
+                                 int(d.numel()), int(act), stream_ptr(d.device)), "trl_act2_bwd_f32")
+    return out
 
 
 def cat_act(logits, seed=0, counter=0, env_offset=0, u=None, deterministic=False, act=None, logp=None, onehot=None):

@@ -72,7 +72,8 @@ class PPO(A2C):
         if is_state_std(tgt):                                          # [mean | log_std] head: MLP forward + trl_gauss_sd_logp_f32
             from ... import ops
             with torch.no_grad():
-                head, _ = ops.mlp_forward(ops.linear_layers(tgt), buf._obs.reshape(rows * n, -1), ops.act_code(tgt), keep=False)
+                layers, code = ops.net_layers(tgt)
+                head, _ = ops.mlp_forward(layers, buf._obs.reshape(rows * n, -1), code, keep=False)
                 _C.gauss_sd_logp(head, buf._acts.reshape(rows * n, -1), bool(tgt.tanh_action),
                                  out=buf._ensure_key("old_logp", (n, 1)).view(rows * n))
             return
@@ -789,6 +790,7 @@ def make_engine(algo):
 
 class _GenericPPO(_FusedPPO):
     defers = False                                                     # (its run returns the dicts)
+    carries_layernorm = True                                           # `add_ln` nets run here (ops.net_plan, k_layernorm.hip)
     """PPO / A2C minibatch loop for ARBITRARY MLP shapes (any observation / action size, width, depth): the layers run
     on the generic dense-layer kernels (k_gemm.hip, through ops.mlp_forward / mlp_backward), the loss half on
     trl_ppo_generic_losses_f32, clip + Adam on trl_clip_adam_f32.  Same interface, statistics block and info dicts
@@ -821,13 +823,16 @@ class _GenericPPO(_FusedPPO):
         self.dev = next(pf.parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
-        self.act = ops.act_code(pf)
-        if ops.act_code(vf) != self.act:
+        # `add_ln` nets: the layer lists carry their post-ops (ops.net_plan) and gamma / beta of every LayerNorm join the flat
+        # vector, the gradient views and the Adam moments behind their layer's W, b; the two nets may differ in `add_ln`
+        # (TRPO / V-MPO build on this engine and walk the plain layer lists themselves: they keep refusing LayerNorm nets)
+        layers_of = ops.net_layers if self.carries_layernorm else (lambda net: (ops.linear_layers(net), ops.act_code(net)))
+        (self.pf_layers, self.act), (self.vf_layers, vf_act) = layers_of(pf), layers_of(vf)
+        if vf_act != self.act:
             raise _C.TrlError("policy and value network must use the same activation")
-        self.pf_layers, self.vf_layers = ops.linear_layers(pf), ops.linear_layers(vf)
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
-        pf_list = [t for wb in self.pf_layers for t in wb] + tail(pf)
-        vf_list = [t for wb in self.vf_layers for t in wb]
+        pf_list = ops.plan_params(self.pf_layers) + tail(pf)
+        vf_list = ops.plan_params(self.vf_layers)
         self.P_pf = sum(p.numel() for p in pf_list)
         self.P_vf = sum(p.numel() for p in vf_list)
         self.D, self.A = int(self.pf_layers[0][0].shape[1]), int(self.pf_layers[-1][0].shape[0])
@@ -844,7 +849,7 @@ class _GenericPPO(_FusedPPO):
         tgt = getattr(algo, "target_pf", None)
         self.target_flat = None
         if tgt is not None:
-            self.target_flat = flatten_into([t for wb in ops.linear_layers(tgt) for t in wb] + tail(tgt))
+            self.target_flat = flatten_into(ops.plan_params(layers_of(tgt)[0]) + tail(tgt))
             if getattr(tgt, "mlp2_spec", lambda: None)() is not None:  # (same storage for its fused forward, as for pf / vf)
                 tgt._flat = self.target_flat
         self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
@@ -852,10 +857,11 @@ class _GenericPPO(_FusedPPO):
         self.gviews, off = [], 0
         for layers in (self.pf_layers, self.vf_layers):
             views = []
-            for w, b in layers:
-                gw = self.grads[off:off + w.numel()].view(w.shape); off += w.numel()
-                gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
-                views.append((gw, gb))
+            for layer in layers:
+                view = []
+                for p in ops.plan_params([layer]):                     # W, b (, gamma, beta)
+                    view.append(self.grads[off:off + p.numel()].view(p.shape)); off += p.numel()
+                views.append(tuple(view))
             self.gviews.append(views)
             if layers is self.pf_layers and not self.categorical and not self.state_std:
                 self.g_logstd = self.grads[off:off + self.A]; off += self.A
@@ -866,7 +872,7 @@ class _GenericPPO(_FusedPPO):
 
     def _ws(self, B):
         need = max(_C.lib().trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0]))
-                   for w, _ in self.pf_layers + self.vf_layers)
+                   for w in (l[0] for l in self.pf_layers + self.vf_layers))
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, device=self.dev)
         return self.workspace

@@ -69,6 +69,8 @@ class TRPO(A2C):
 
 
 class _TRPOEngine(_GenericPPO):
+    carries_layernorm = False                                          # (its own passes walk the plain layer lists)
+
     def __init__(self, algo):
         super().__init__(algo)
         self._stat = torch.zeros(4 + 5 + 1 + 1, dtype=torch.float64, device=self.dev)   # adv raw | info | scalar | vf loss

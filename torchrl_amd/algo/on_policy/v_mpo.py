@@ -66,6 +66,8 @@ class VMPO(A2C):
 
 
 class _VMPOEngine(_GenericPPO):
+    carries_layernorm = False                                          # (its own passes walk the plain layer lists)
+
     def __init__(self, algo):
         super().__init__(algo)
         if algo.optimizer_class is not torch.optim.Adam:

@@ -309,7 +309,7 @@ class VecOnPolicyCollector(VecCollector):
                               "is not reproduced -- noise_mode=%r is not built" % (self.noise_mode,))
         ps = self.pf.mlp2_spec() if hasattr(self.pf, "mlp2_spec") else None
         vs = self.vf.mlp2_spec() if hasattr(self.vf, "mlp2_spec") else None
-        self._act = ops.act_code(self.pf)
+        self._act = ops.net_layers(self.pf)[1]                              # (an `add_ln` net: its plan's activation, ops.net_plan)
         layers = ops.linear_layers(self.pf)
         head_w = int(layers[-1][0].shape[0])
         self._dims = (int(layers[0][0].shape[1]),
@@ -376,7 +376,7 @@ class VecOnPolicyCollector(VecCollector):
             D, H, A, act = self._mlp2
             return _C.mlp2_forward(net.flat_params(), x, D, H, out_dim, act, out=out)
         from .. import ops
-        y, _ = ops.mlp_forward(ops.linear_layers(net), x, self._act)
+        y, _ = ops.mlp_forward(ops.net_layers(net)[0] if net.base.add_ln else ops.linear_layers(net), x, self._act)
         if out is not None:
             out.copy_(y)
             return out

@@ -7,7 +7,9 @@ no LayerNorm and no extra hidden layers is an "MLP2" block (include/trl_hip.h):
 views into ONE contiguous fp32 buffer  W1 b1 W2 b2 W3 b3 [logstd]  so kernels
 read/write the very storage `state_dict()` / `parameters()` expose.
 
-`forward` on a GPU MLP2 under no_grad runs trl_mlp2_forward_f32.  With autograd
+`forward` on a GPU MLP2 under no_grad runs trl_mlp2_forward_f32; other MLPs run
+layer by layer on the dense-layer kernels, `add_ln=True` ones with their
+LayerNorm layers on k_layernorm.hip in between (ops.net_plan).  With autograd
 enabled (algorithms outside this repo's hot-path scope) it is the plain
 nn.Module graph.
 """
@@ -140,13 +142,20 @@ class Net(nn.Module):
                 x2 = x.reshape(-1, D).float().contiguous()
                 return _C.mlp2_forward(self.flat_params(), x2, D, H, O, act).reshape(tuple(lead) + (O,))
             from .. import ops
+            ln = self.add_ln and isinstance(self.base, MLPBase)
             try:
-                layers, act = ops.linear_layers(self), ops.act_code(self)
+                # LayerNorm layers: k_layernorm.hip between the dense layers (ops.net_plan)
+                layers, act = ops.net_layers(self) if ln else (ops.linear_layers(self), ops.act_code(self))
             except _C.TrlError:
-                layers = None                                       # LayerNorm / conv trunk / other activations: torch modules
+                if ln and self.base.activation_func in ops.ACT_OF:
+                    raise                                           # a norm the kernels do not carry: say so, do not go eager
+                layers = None                                       # conv trunk / other activations: torch modules
             if layers is not None and isinstance(self.base, MLPBase):
                 x2 = x.reshape(-1, int(layers[0][0].shape[1])).float().contiguous()
-                out, _ = ops.mlp_forward([(w.detach(), b.detach()) for w, b in layers], x2, act)   # dense-layer kernels
+                if ops.has_post(layers):
+                    out, _ = ops.mlp_forward(layers, x2, act, keep=False)
+                else:
+                    out, _ = ops.mlp_forward([(w.detach(), b.detach()) for w, b in layers], x2, act)   # dense-layer kernels
                 return out.reshape(tuple(lead) + (self.out_dim,))
         if x.is_cuda:
             _C.note_eager(type(self).__name__ + ".forward", "autograd is on" if needs_graph else "no kernel for this trunk")

@@ -6,6 +6,10 @@ activation, then a linear head.  `mlp_forward` keeps the layer outputs (the "tap
 `mlp_backward` walks it back: dW / db of every layer straight into views of a flat
 gradient buffer, and optionally d(input).  act'(.) is applied inside the kernels through the
 stored layer OUTPUTS, so no pre-activation tensors are kept.
+
+`add_ln=True` nets carry post-ops behind their hidden layers (`net_plan`): a LayerNorm, or the second activation that
+replaces the trunk's last LayerNorm.  The ungrouped `mlp_forward` / `mlp_backward` run them on k_layernorm.hip; the
+grouped routes and the fused three-layer forward do not know them.
 """
 
 import torch
@@ -30,14 +34,83 @@ def act_code(net):
     return ACT_OF[a]
 
 
+def net_plan(net):
+    """[(W, b, post), ...] of a torchrl_amd.networks.Net whose trunk is an MLPBase, read off the module lists
+    `net.base.seq_fcs` and `net.seq_append_fcs` themselves.  post is what follows the layer's activation:
+    None, ("ln", gamma, beta) -- a LayerNorm over the layer's outputs -- or ("act",) -- the activation once more, which is
+    what the reference's construction leaves where it pops the trunk's last LayerNorm (networks/base.py::_trunk).  The
+    last entry is the linear head (no activation, post None)."""
+    a = net.base.activation_func
+    if a not in ACT_OF or net.base.last_activation_func is not a or not hasattr(net.base, "seq_fcs"):
+        raise _C.TrlError("dense kernels support Tanh / ReLU MLPs, with or without LayerNorm (got %s)" % a)
+    mods = list(net.base.seq_fcs) + list(net.seq_append_fcs)
+    plan, i = [], 0
+    while i < len(mods):
+        lin = mods[i]
+        if not isinstance(lin, nn.Linear):
+            raise _C.TrlError("dense kernels: expected a Linear layer at position %d of the module list, found %s" % (i, lin))
+        i += 1
+        n_act = 0
+        while i < len(mods) and type(mods[i]) is a:
+            n_act, i = n_act + 1, i + 1
+        norm = None
+        if i < len(mods) and isinstance(mods[i], nn.LayerNorm):
+            norm, i = mods[i], i + 1
+        head = i == len(mods)
+        if (head and (n_act or norm is not None)) or (not head and n_act not in (1, 2)) or (n_act == 2 and norm is not None):
+            raise _C.TrlError("dense kernels: a hidden layer is Linear, activation, then LayerNorm or one more activation; "
+                              "the head is a bare Linear (layer %d of %s)" % (len(plan), type(net).__name__))
+        post = ("act",) if n_act == 2 else None
+        if norm is not None:
+            H = int(lin.weight.shape[0])
+            if tuple(norm.normalized_shape) != (H,) or not norm.elementwise_affine or norm.bias is None or \
+                    float(norm.eps) != 1e-5:
+                raise _C.TrlError("LayerNorm kernels carry an affine norm over the layer's %d outputs with eps 1e-5, got %s"
+                                  % (H, norm))
+            if not 1 <= H <= _C.LN_MAX_H:
+                raise _C.TrlError("LayerNorm kernels carry rows of 1 <= H <= %d features, got a layer of %d" % (_C.LN_MAX_H, H))
+            post = ("ln", norm.weight, norm.bias)
+        plan.append((lin.weight, lin.bias, post))
+    return plan
+
+
+def has_post(layers):
+    return any(len(l) > 2 and l[2] is not None for l in layers)
+
+
+def net_layers(net):
+    """(layers, activation code) for `mlp_forward` / `mlp_backward`: `linear_layers` / `act_code` for a net without
+    post-ops (their errors included), the `net_plan` for an `add_ln` net."""
+    if not net.base.add_ln:
+        return linear_layers(net), act_code(net)
+    plan = net_plan(net)
+    return (plan if has_post(plan) else [(w, b) for w, b, _ in plan]), ACT_OF[net.base.activation_func]
+
+
+def plan_params(layers):
+    """The parameters of a layer list in module order: W, b, then gamma, beta of a layer's LayerNorm."""
+    out = []
+    for l in layers:
+        out += [l[0], l[1]]
+        if len(l) > 2 and l[2] is not None and l[2][0] == "ln":
+            out += [l[2][1], l[2][2]]
+    return out
+
+
 class Tape:
-    __slots__ = ("x", "outs", "layers", "act", "last_act")
+    # posts / stats (nets with post-ops only): per layer the post-op's output (the next layer's input) and the LayerNorm's
+    # (M, 2) row statistics; `outs` keeps the activation outputs, which gate the gradient
+    __slots__ = ("x", "outs", "layers", "act", "last_act", "posts", "stats")
 
 
 def mlp_forward(layers, x, act, last_act=None, keep=True):
     """layers: [(W, b), ...] (nn.Linear layout); returns (out, tape).  `last_act` (an ACT_* code) is applied to
     the head output inside the last layer's epilogue (deterministic policies: tanh(mlp(x))).  keep=False: no backward pass
     will follow (acting): the fused three-layer launch then leaves its hidden activations on chip."""
+    if has_post(layers):
+        return _mlp_forward_post(layers, x, act, last_act)
+    if any(len(l) > 2 for l in layers):                               # (a plan without post-ops)
+        layers = [(l[0], l[1]) for l in layers]
     if len(layers) == 3 and all(b is not None for _, b in layers[:2]) and \
             _C.mlp3_forward_ok(layers[0][0].shape[1], layers[0][0].shape[0], layers[1][0].shape[0], layers[2][0].shape[0]):
         outs, tapes = mlp_forward_group([layers], [x], act, last_act=last_act, keep=[bool(keep)])      # one fused launch
@@ -53,12 +126,71 @@ def mlp_forward(layers, x, act, last_act=None, keep=True):
     return h, t
 
 
+def _mlp_forward_post(layers, x, act, last_act):
+    """`mlp_forward` of a layer list with post-ops: one dense-layer launch per layer, one k_layernorm.hip launch per
+    LayerNorm and per second Tanh (a second ReLU changes nothing and is not launched)."""
+    t = Tape()
+    t.x, t.layers, t.act, t.outs, t.posts, t.stats = x, layers, act, [], [], []
+    t.last_act = _C.ACT_NONE if last_act is None else last_act
+    h = x
+    for k, (w, b, post) in enumerate(layers):
+        last = k == len(layers) - 1
+        if last and post is not None:
+            raise _C.TrlError("mlp_forward: the head carries no post-op")
+        h = _C.linear_fwd(h, w, b, t.last_act if last else act)
+        t.outs.append(h)
+        st = None
+        if post is not None and post[0] == "ln":
+            h, st = _C.layernorm_fwd(h, post[1].detach(), post[2].detach())
+        elif post is not None and act == _C.ACT_TANH:
+            h = _C.act2_fwd(h, act)
+        t.posts.append(h if post is not None else None)
+        t.stats.append(st)
+    return h, t
+
+
+def _mlp_backward_post(tape, d_out, grads, need_input, workspace):
+    """grads[k]: (dW, db) or, for a layer with a LayerNorm, (dW, db, dgamma, dbeta).  The post-op's backward launch emits
+    the gradient at the layer's pre-activation, so that layer's GEMMs run ungated."""
+    d = d_out
+    n = len(tape.layers)
+    for k in range(n - 1, -1, -1):
+        w, _b, post = tape.layers[k]
+        last = k == n - 1
+        gate_act = tape.last_act if last else tape.act
+        gate = None if (last and gate_act == _C.ACT_NONE) else tape.outs[k]
+        if post is not None and post[0] == "ln":
+            M, H = tape.outs[k].shape
+            if grads is not None:
+                dg, db_ = grads[k][2], grads[k][3]
+            else:
+                dg, db_ = torch.empty(H, device=d.device), torch.empty(H, device=d.device)
+            d = _C.layernorm_bwd(d, tape.outs[k], tape.stats[k], post[1].detach(), gate_act, dg, db_)
+            gate, gate_act = None, _C.ACT_NONE
+        elif post is not None and tape.act == _C.ACT_TANH:
+            d = _C.act2_bwd(d, tape.outs[k], tape.posts[k], tape.act)
+            gate, gate_act = None, _C.ACT_NONE
+        if k == 0:
+            inp = tape.x
+        else:
+            inp = tape.outs[k - 1] if tape.posts[k - 1] is None else tape.posts[k - 1]
+        if grads is not None:
+            _C.linear_bwd_weight(d, gate, gate_act, inp, dw=grads[k][0], db=grads[k][1], workspace=workspace)
+        if k > 0 or need_input:
+            d = _C.linear_bwd_input(d, gate, gate_act, w)
+    return d if need_input else None
+
+
 def mlp_backward(tape, d_out, grads=None, need_input=False, workspace=None, plan=None, head_dx=None):
     """d_out: gradient w.r.t. the network output.  grads: [(dW_view, db_view), ...] to fill (or None
     to skip weight gradients).  Returns d(input) if need_input.  plan (_C.FoldPlan): the weight gradients are only
     final after `plan.run()` (one fold launch for the whole pass).  head_dx (with plan): the gradient at the last hidden
     layer, ALREADY gated by that layer's act' (somebody computed it along the way): the last layer's input-gradient launch
     is skipped."""
+    if getattr(tape, "posts", None) is not None:
+        if plan is not None or head_dx is not None:
+            raise _C.TrlError("mlp_backward: LayerNorm nets run the ungrouped route (no fold plan, no head_dx)")
+        return _mlp_backward_post(tape, d_out, grads, need_input, workspace)
     if plan is not None:
         out = mlp_backward_group([tape], [d_out], None if grads is None else [grads], need_input, plan=plan,
                                  head_dx=None if head_dx is None else [head_dx])
