@@ -446,7 +446,7 @@ int trl_ppo_reduce_adam_net_f32(const float* partial, const double* scal_partial
                                 const trl_adam_t* adam, float* workspace, void* stream);
 
 /* --- the fused minibatch update for a CATEGORICAL policy (CategoricalDisPolicy, 2 <= A <= 8 actions) ----------
- * The entry points above with a categorical head on the policy network (the gradient kernel's CAT instantiations): the A head
+ * The entry points above with a categorical head on the policy network (the gradient kernel's HEAD_CAT instantiations): the A head
  * outputs are logits, args->acts is (rows, N, 1) -- the action index as a float --, args->pf_params is [W1 b1 W2 b2 W3 b3]
  * (no logstd: P_pf = H D + H + H H + H + A H + A), args->tanh_action is ignored.  Softmax, log pi and entropy follow
  * trl_cat_losses_f32's fixed arithmetic; d(loss)/d(logit k) = g_lp (1[k = a] - p_k) + (entropy_coeff / n_global) p_k (log p_k + H).
@@ -472,7 +472,7 @@ int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const double* scal_par
                                     const trl_adam_t* adam, float* workspace, void* stream);
 
 /* --- the fused minibatch update for a STATE-DEPENDENT-STD Gaussian policy (GuassianContPolicy, 1 <= A <= 8) ----------
- * The entry points above with a [mean | log_std] head on the policy network (the gradient kernel's SD instantiations): the head
+ * The entry points above with a [mean | log_std] head on the policy network (the gradient kernel's HEAD_SD instantiations): the head
  * has 2A rows, mean rows 0..A-1 then log_std rows A..2A-1; args->A is the number of ACTION dimensions, args->acts is
  * (rows, N, A), args->pf_params is [W1 b1 W2 b2 W3 b3] (no logstd: P_pf = H D + H + H H + H + 2A H + 2A).  Per element
  * ls = clamp(raw, -20, 2) and the arithmetic of trl_gauss_sd_losses_f32: d(loss)/d(mean) = g_lp zc / std^2,

@@ -24,6 +24,10 @@ PAIR_CASES = [dict(D=17, A=6, act="tanh", net_seed=21, env_seed=3, max_frames=99
               dict(D=5, A=3, act="relu", net_seed=22, env_seed=4, max_frames=4),
               dict(D=32, A=8, act="tanh", net_seed=23, env_seed=5, max_frames=999),
               dict(D=4, A=2, act="tanh", net_seed=24, env_seed=6, max_frames=999)]
+# the wide tile with ReLU at the smallest head on 24 envs (one full and one partial 16-env tile) x 2 steps: a branch of the
+# tile / activation / head dispatch no other case reaches.  horizon 2: every episode ends inside the rollout.
+WIDE_RELU_CASE = dict(D=18, A=2, act="relu", net_seed=25, env_seed=7, max_frames=999)
+WIDE_RELU_N, WIDE_RELU_T, WIDE_RELU_HORIZON = 24, 2, 2
 # fused vs CPU stepping: the shape of tests/test_categorical_gpu.py::test_collector_ring_vs_cpu_stepping with 64 x 64 nets
 CPU_CASE = dict(D=17, A=6, act="tanh", net_seed=0, env_seed=3, max_frames=999)
 CPU_N, CPU_T, CPU_HORIZON = 64, 16, 7

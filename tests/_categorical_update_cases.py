@@ -26,6 +26,10 @@ SHAPES = [(2, 2, "tanh"), (11, 3, "tanh"), (11, 3, "relu"), (17, 6, "tanh"), (17
 LAYOUTS = {"contig": (16, 6, 2), "ragged": (12, 7, 2), "multi": (16, 40, 6), "empty": (16, 1, 2)}
 LOSSES = [(ref.LOSS_PPO_CLIP, False), (ref.LOSS_PPO_CLIP, True), (ref.LOSS_A2C, False)]
 GRAD_CASES = [(D, A, act, lay) for (D, A, act) in SHAPES for lay in LAYOUTS]
+# the wide tile with ReLU on per-lane addressing at the smallest head -- a branch of the tile / activation / head dispatch
+# no case above reaches: 24 envs (one full and one partial 16-sample tile per time row), 2 time rows
+PARTIAL_LAYOUT = {"partial": (24, 2, 2)}
+GRAD_CASES.append((18, 2, "relu", "partial"))
 # the single-network launches: both tiles, both addressings
 NET_CASES = [(17, 6, "tanh", "multi"), (27, 8, "relu", "ragged"), (11, 3, "tanh", "empty")]
 # fused against generic engine: (D, A, seed)
@@ -68,7 +72,7 @@ def forward(params, x, act):
 
 def _grad_inputs(c, seed):
     D, A, act, lay = c
-    N, rows, n_wg = LAYOUTS[lay]
+    N, rows, n_wg = dict(LAYOUTS, **PARTIAL_LAYOUT)[lay]
     rs = np.random.RandomState(seed)
     R = rows + 3                                                              # stored time rows; the minibatch takes `rows` of them
     t = lambda *s: torch.from_numpy(rs.randn(*s).astype(np.float32))

@@ -27,6 +27,11 @@ PAIR_CASES = [dict(D=17, A=6, act="tanh", net_seed=21, env_seed=3, max_frames=99
               dict(D=32, A=8, act="tanh", net_seed=23, env_seed=5, max_frames=999, tanh=True),
               dict(D=4, A=1, act="tanh", net_seed=24, env_seed=6, max_frames=999, tanh=True),
               dict(D=17, A=6, act="tanh", net_seed=21, env_seed=3, max_frames=999, tanh=False)]
+# the wide tile with ReLU at the smallest and the largest head on 24 envs (one full and one partial 16-env tile) x 2 steps:
+# branches of the tile / activation / head dispatch no other case reaches.  horizon 2: every episode ends inside the rollout.
+WIDE_RELU_CASES = [dict(D=18, A=1, act="relu", net_seed=25, env_seed=7, max_frames=999, tanh=True),
+                   dict(D=18, A=8, act="relu", net_seed=26, env_seed=8, max_frames=999, tanh=True)]
+WIDE_RELU_N, WIDE_RELU_T, WIDE_RELU_HORIZON = crr.WIDE_RELU_N, crr.WIDE_RELU_T, crr.WIDE_RELU_HORIZON
 CPU_CASE = dict(D=17, A=6, act="tanh", net_seed=0, env_seed=3, max_frames=999, tanh=True)
 CPU_N, CPU_T, CPU_HORIZON = crr.CPU_N, crr.CPU_T, crr.CPU_HORIZON
 # teacher-forced steps with stress heads, no tanh.  "span": the log_std rows of W3 are scaled by `ls_scale` and b3's log_std

@@ -24,7 +24,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import _gauss_sd_ref as ref                                                   # noqa: E402
-from _categorical_update_cases import LAYOUTS, act_fn, forward, linear_params  # noqa: E402,F401
+from _categorical_update_cases import LAYOUTS, PARTIAL_LAYOUT, act_fn, forward, linear_params  # noqa: E402,F401
 
 H = 64
 CLIP, C_ENT = 0.2, 0.01
@@ -39,7 +39,10 @@ PLAIN_CASES = [(D, A, act, lay, False) for (D, A, act) in SHAPES for lay in LAYO
 # ... and the clamp cases: both tiles, both addressings, a full tile (A = 8), waves without a tile
 CLAMP_CASES = [(11, 3, "tanh", "ragged", True), (17, 6, "tanh", "empty", True), (17, 8, "tanh", "multi", True),
                (27, 8, "relu", "contig", True), (32, 5, "tanh", "multi", True), (18, 2, "tanh", "ragged", True)]
-GRAD_CASES = PLAIN_CASES + CLAMP_CASES
+# the wide tile with ReLU on per-lane addressing (24 envs x 2 time rows, _categorical_update_cases.PARTIAL_LAYOUT) at the
+# smallest and the largest head: branches of the tile / activation / head dispatch no case above reaches
+PARTIAL_CASES = [(18, 1, "relu", "partial", False), (18, 8, "relu", "partial", False)]
+GRAD_CASES = PLAIN_CASES + CLAMP_CASES + PARTIAL_CASES
 # the single-network launches: both tiles, both addressings, a clamp case among them
 NET_CASES = [(17, 6, "tanh", "multi", False), (27, 8, "relu", "ragged", False), (11, 3, "tanh", "empty", False),
              (17, 8, "tanh", "multi", True)]
@@ -84,7 +87,7 @@ def random_nets(rs, D, A, clamp):
 
 def _grad_inputs(c, seed):
     D, A, act, lay, clamp = c
-    N, rows, n_wg = LAYOUTS[lay]
+    N, rows, n_wg = dict(LAYOUTS, **PARTIAL_LAYOUT)[lay]
     tanh = not clamp
     rs = np.random.RandomState(seed)
     R = rows + 3                                                              # stored time rows; the minibatch takes `rows` of them

@@ -96,12 +96,15 @@ def test_argument_checks_return_before_any_launch(built_lib):
     bad(EUNSUPPORTED, b"not instantiated", act=_C.ACT_NONE)
 
 
-@pytest.mark.parametrize("case", rr.PAIR_CASES + [rr.CPU_CASE], ids=rr.case_id)
+@pytest.mark.parametrize("case", rr.PAIR_CASES + [rr.CPU_CASE, rr.WIDE_RELU_CASE], ids=rr.case_id)
 def test_borderline_share_of_the_gpu_cases(case):
     """On the restatement alone: the rows of each case on which a kernel may legitimately draw the neighbouring action
     (threshold within 1e-5 * S of a prefix sum) stay within the cap the GPU tests allow -- with room: at most half of it."""
-    pair = case is not rr.CPU_CASE
-    N, steps, horizon = (rr.PAIR_N, rr.PAIR_T * rr.PAIR_EPOCHS, rr.PAIR_HORIZON) if pair else (rr.CPU_N, rr.CPU_T, rr.CPU_HORIZON)
+    N, steps, horizon = (rr.PAIR_N, rr.PAIR_T * rr.PAIR_EPOCHS, rr.PAIR_HORIZON)
+    if case is rr.CPU_CASE:
+        N, steps, horizon = rr.CPU_N, rr.CPU_T, rr.CPU_HORIZON
+    if case is rr.WIDE_RELU_CASE:
+        N, steps, horizon = rr.WIDE_RELU_N, rr.WIDE_RELU_T * rr.PAIR_EPOCHS, rr.WIDE_RELU_HORIZON
     out = rr.cpu_rollout(case, N, steps, horizon)
     share = float(out["borderline"].mean())
     acts = out["acts"].reshape(-1)

@@ -108,7 +108,14 @@ def test_route_is_the_fused_rollout_for_64_wide_nets(monkeypatch):
 # ---------------------------------------------------------------- fused vs per-step
 @pytest.mark.parametrize("c", rr.PAIR_CASES, ids=rr.case_id)
 def test_fused_rollout_vs_per_step_route(c, monkeypatch):
-    N, T, horizon, epochs = rr.PAIR_N, rr.PAIR_T, rr.PAIR_HORIZON, rr.PAIR_EPOCHS
+    fused_vs_per_step(c, rr.PAIR_N, rr.PAIR_T, rr.PAIR_HORIZON, rr.PAIR_EPOCHS, monkeypatch)
+
+
+def test_fused_rollout_vs_per_step_route_wide_relu_partial_tile(monkeypatch):
+    fused_vs_per_step(rr.WIDE_RELU_CASE, rr.WIDE_RELU_N, rr.WIDE_RELU_T, rr.WIDE_RELU_HORIZON, rr.PAIR_EPOCHS, monkeypatch)
+
+
+def fused_vs_per_step(c, N, T, horizon, epochs, monkeypatch):
     monkeypatch.delenv("TRL_GENERIC_PPO", raising=False)
     monkeypatch.setenv(SWITCH, "1")
     pf, vf, env, buf, col = make_collector(c, N, T, horizon)

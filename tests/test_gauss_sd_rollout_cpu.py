@@ -90,13 +90,17 @@ def _report(label, worst):
     assert not bad, (label, bad)
 
 
-TRAJECTORIES = [(c, m) for c in rr.PAIR_CASES for m in ("host", "device")] + [(rr.CPU_CASE, "host")]
+TRAJECTORIES = [(c, m) for c in rr.PAIR_CASES for m in ("host", "device")] + [(rr.CPU_CASE, "host")] + \
+    [(c, "device") for c in rr.WIDE_RELU_CASES]
 
 
 @pytest.mark.parametrize("case,mode", TRAJECTORIES, ids=["%s-%s" % (rr.case_id(c), m) for c, m in TRAJECTORIES])
 def test_float32_rollouts_stay_inside_the_trajectory_bounds(case, mode):
-    pair = case is not rr.CPU_CASE
-    N, steps, horizon = (rr.PAIR_N, rr.PAIR_T * rr.PAIR_EPOCHS, rr.PAIR_HORIZON) if pair else (rr.CPU_N, rr.CPU_T, rr.CPU_HORIZON)
+    N, steps, horizon = (rr.PAIR_N, rr.PAIR_T * rr.PAIR_EPOCHS, rr.PAIR_HORIZON)
+    if case is rr.CPU_CASE:
+        N, steps, horizon = rr.CPU_N, rr.CPU_T, rr.CPU_HORIZON
+    if case in rr.WIDE_RELU_CASES:
+        N, steps, horizon = rr.WIDE_RELU_N, rr.WIDE_RELU_T * rr.PAIR_EPOCHS, rr.WIDE_RELU_HORIZON
     nets = rr.nets_of(case)
     eps = rr.noise_of(mode, steps, N, case["A"], case["env_seed"])
     lo, hi = (rr.cpu_rollout(case, N, steps, horizon, nets, eps, dt) for dt in (torch.float32, torch.float64))

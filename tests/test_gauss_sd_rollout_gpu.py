@@ -113,7 +113,15 @@ def test_route_is_the_fused_rollout_for_64_wide_nets(monkeypatch):
 @pytest.mark.parametrize("mode", ["host", "device"])
 @pytest.mark.parametrize("c", rr.PAIR_CASES, ids=rr.case_id)
 def test_fused_rollout_vs_per_step_route(c, mode, monkeypatch):
-    N, T, horizon, epochs = rr.PAIR_N, rr.PAIR_T, rr.PAIR_HORIZON, rr.PAIR_EPOCHS
+    fused_vs_per_step(c, mode, rr.PAIR_N, rr.PAIR_T, rr.PAIR_HORIZON, rr.PAIR_EPOCHS, monkeypatch)
+
+
+@pytest.mark.parametrize("c", rr.WIDE_RELU_CASES, ids=rr.case_id)
+def test_fused_rollout_vs_per_step_route_wide_relu_partial_tile(c, monkeypatch):
+    fused_vs_per_step(c, "device", rr.WIDE_RELU_N, rr.WIDE_RELU_T, rr.WIDE_RELU_HORIZON, rr.PAIR_EPOCHS, monkeypatch)
+
+
+def fused_vs_per_step(c, mode, N, T, horizon, epochs, monkeypatch):
     monkeypatch.delenv("TRL_GENERIC_PPO", raising=False)
     monkeypatch.setenv(SWITCH, "1")
     pf, vf, env, buf, col = make_collector(c, N, T, horizon, noise_mode=mode)

@@ -188,6 +188,32 @@ def test_fused_ppo_update_at_other_input_and_action_sizes_vs_oracle(D, A, act, t
     """64-wide two-layer networks with any D in [2, 32], A in [1, 8] stay on the fused two-launch update
     (trl_ppo_minibatch_grad_f32's runtime-dims instantiation + trl_ppo_reduce_adam_f32): three chained updates against
     the CPU oracle at the contract of the benchmark shape (scalars rel 1e-4 / abs 1e-5, post-step parameters abs 1e-6)."""
+    fused_updates_vs_oracle(D, A, act, tanh_action, clipped, B, 1, errlog)
+
+
+@pytest.mark.parametrize("A,clipped", [(1, False), (8, True)])
+def test_fused_ppo_update_wide_relu_partial_tile_vs_oracle(A, clipped, errlog):
+    """The same contract on a branch of the tile / activation dispatch the cases above do not reach: the wide tile (D = 18)
+    with ReLU on per-lane addressing, at the smallest and the largest head -- a minibatch of 2 time rows x 24 envs (one full
+    and one partial 16-sample tile per row)."""
+    fused_updates_vs_oracle(18, A, "relu", True, clipped, 48, 2, errlog)
+
+
+def update_as_rows(agent, batch, rows):
+    """PPO.update (one time row of B envs) with the same samples laid out as `rows` time rows of B // rows envs."""
+    as_t = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float32, device=agent.device).contiguous()
+    obs, acts = as_t(batch["obs"]), as_t(batch["acts"])
+    N = obs.shape[0] // rows
+    with torch.no_grad():
+        old_lp = agent.target_pf.update(obs, acts)["log_prob"].contiguous()
+    agent.training_update_num += 1
+    tensors = {"obs": obs, "acts": acts, "advs": as_t(batch["advs"]), "rets": as_t(batch["estimate_returns"]),
+               "old_values": as_t(batch["values"]), "old_logp": old_lp}
+    tensors = {k: v.reshape(rows, N, -1) for k, v in tensors.items()}
+    return agent.engine().run(tensors, np.arange(rows, dtype=np.int64).reshape(1, rows), N)[0]
+
+
+def fused_updates_vs_oracle(D, A, act, tanh_action, clipped, B, rows, errlog):
     from torchrl.algo import PPO
     act_cls = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}[act]
     pf, vf, agent, (pf0, ls0, vf0) = build(D, A, [64, 64], act_cls, tanh_action, PPO, clip_para=0.2, opt_epochs=2,
@@ -206,7 +232,7 @@ def test_fused_ppo_update_at_other_input_and_action_sizes_vs_oracle(D, A, act, t
                  "values": torch.randn(B, 1, generator=gen).numpy(), "estimate_returns": torch.randn(B, 1, generator=gen).numpy()}
         want = ref.update(batch)
         ref.sync_target()
-        got = agent.update(batch)
+        got = agent.update(batch) if rows == 1 else update_as_rows(agent, batch, rows)
         agent.engine().sync_target_pf()
         assert sorted(got) == sorted(want)
         keys = sorted(want)
@@ -278,6 +304,17 @@ def test_collect_and_train_with_the_fused_update_on_a_hopper_sized_env(D, A):
                                                  (17, 6, "tanh", False), (18, 1, "tanh", True), (32, 8, "relu", True),
                                                  (2, 1, "tanh", True), (16, 4, "tanh", True)])
 def test_runtime_dims_rollout_kernel_matches_the_oracle_collector(D, A, act, tanh_action, errlog, monkeypatch):
+    rollout_vs_oracle_collector(D, A, act, tanh_action, 48, 24, errlog, monkeypatch)
+
+
+@pytest.mark.parametrize("A", [1, 8])
+def test_runtime_dims_rollout_kernel_wide_relu_partial_tile(A, errlog, monkeypatch):
+    """The wide tile (D = 18) with ReLU at the smallest and the largest head on 24 envs (one full and one partial 16-env
+    tile) x 2 steps -- a branch of the tile / activation dispatch the cases above do not reach; too short for a reset."""
+    rollout_vs_oracle_collector(18, A, "relu", True, 24, 2, errlog, monkeypatch)
+
+
+def rollout_vs_oracle_collector(D, A, act, tanh_action, N, T, errlog, monkeypatch):
     """the persistent rollout kernel for other task shapes (Hopper 11 / 3, Ant 27 / 8, Swimmer 8 / 2,
     the edges of both tiles) -- ONE launch for the whole epoch -- against VecOnPolicyCollectorOracle
     (torchrl/collector/on_policy.py:90-155 restated) on a synthetic env of that shape, in the reference's noise stream:
@@ -293,7 +330,7 @@ def test_runtime_dims_rollout_kernel_matches_the_oracle_collector(D, A, act, tan
     from oracle import replay as oreplay
     from oracle.collector import VecOnPolicyCollectorOracle
     from oracle.synth_env import SynthVecEnvCPU
-    N, T, horizon, max_frames, seed = 48, 24, 10, 7, 5
+    horizon, max_frames, seed = 10, 7, 5
     act_cls = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}[act]
     net = dict(hidden_shapes=[64, 64], append_hidden_shapes=[], base_type=networks.MLPBase, activation_func=act_cls)
     torch.manual_seed(D * 31 + A)
@@ -331,7 +368,8 @@ def test_runtime_dims_rollout_kernel_matches_the_oracle_collector(D, A, act, tan
         err = np.abs(a - b).max()
         errlog("rt rollout %s D=%d A=%d abs" % (k, D, A), err, 1e-5)
         assert err < 1e-5, (k, err)
-    assert float(buf._terminals.sum()) > 0 and float((buf._terminals - buf._time_limits).abs().sum()) > 0   # both reset kinds
+    if T > horizon:
+        assert float(buf._terminals.sum()) > 0 and float((buf._terminals - buf._time_limits).abs().sum()) > 0   # both reset kinds
     assert abs(got_reward - float(ores["train_epoch_reward"])) < 1e-3 * max(1.0, abs(got_reward))
     np.testing.assert_allclose(got_eps, sorted(float(x) for x in ores["train_rewards"]), atol=1e-4)
     # log pi_old of the stored actions under the collecting policy (what target_pf recomputes, ppo.py:54-56)

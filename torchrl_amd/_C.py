@@ -587,18 +587,19 @@ def rollout_sd(args, device):
     check(lib().trl_rollout_synth_sd_f32(C.byref(args), stream_ptr(device)), "trl_rollout_synth_sd_f32")
 
 
-def ppo_partial_stride(D, H, A):
-    ps = lib().trl_ppo_partial_stride(D, H, A)
+def _partial_stride(name, D, H, A):
+    ps = getattr(lib(), name)(D, H, A)
     if ps < 0:
-        check(ps, "trl_ppo_partial_stride")
+        check(ps, name)
     return ps
+
+
+def ppo_partial_stride(D, H, A):
+    return _partial_stride("trl_ppo_partial_stride", D, H, A)
 
 
 def ppo_cat_partial_stride(D, H, A):
-    ps = lib().trl_ppo_cat_partial_stride(D, H, A)
-    if ps < 0:
-        check(ps, "trl_ppo_cat_partial_stride")
-    return ps
+    return _partial_stride("trl_ppo_cat_partial_stride", D, H, A)
 
 
 def ppo_cat_minibatch_grad(args, device):
@@ -614,10 +615,7 @@ def ppo_cat_reduce(partial, scal_partial, n_wg, D, H, A, grads, info, n_wg_pf=0)
 
 
 def ppo_sd_partial_stride(D, H, A):
-    ps = lib().trl_ppo_sd_partial_stride(D, H, A)
-    if ps < 0:
-        check(ps, "trl_ppo_sd_partial_stride")
-    return ps
+    return _partial_stride("trl_ppo_sd_partial_stride", D, H, A)
 
 
 def ppo_sd_scalar_stride():

@@ -27,7 +27,7 @@ import torch.optim as optim
 from ... import _C
 from ... import dist
 from ...networks import flatten_into
-from ...policies.continuous_policy import is_state_std
+from ...policies.continuous_policy import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, HEAD_TAG, head_kind, is_state_std  # noqa: F401
 from .. import utils as atu
 from .a2c import A2C
 
@@ -64,12 +64,13 @@ class PPO(A2C):
         buf = self.replay_buffer
         rows, n = buf._max_replay_buffer_size, buf.env_nums
         tgt = self.target_pf
-        if getattr(tgt, "continuous", True) is False:                  # categorical head: MLP forward + trl_cat_logp_f32
+        kind = head_kind(tgt)
+        if kind == HEAD_CAT:                                           # categorical head: MLP forward + trl_cat_logp_f32
             with torch.no_grad():
                 _C.cat_logp(tgt.logits(buf._obs.reshape(rows * n, -1)).contiguous(), buf._acts.reshape(rows * n),
                             out=buf._ensure_key("old_logp", (n, 1)).view(rows * n))
             return
-        if is_state_std(tgt):                                          # [mean | log_std] head: MLP forward + trl_gauss_sd_logp_f32
+        if kind == HEAD_SD:                                            # [mean | log_std] head: MLP forward + trl_gauss_sd_logp_f32
             from ... import ops
             with torch.no_grad():
                 layers, code = ops.net_layers(tgt)
@@ -133,27 +134,21 @@ class _FusedPPO:
         self.algo = algo
         pf, vf = algo.pf, algo.vf
         ps, vs = pf.mlp2_spec(), vf.mlp2_spec()
-        # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's CAT instantiations and their folds
+        # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's HEAD_CAT instantiations and their folds
         # (trl_ppo_cat_*); no logstd in the flat vector, the entropy arrives through info slot 20
-        self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
-        # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; the gradient kernel's SD
-        # instantiations and their folds (trl_ppo_sd_*); no logstd in the flat vector either, `self.A` = half the head's width,
-        # entropy and the per-element log_std / std statistics arrive through info slots 20, 8-11 and 16-19
-        self.state_std = not self.categorical and is_state_std(pf)
-        if ps is None or vs is None or not (self.categorical or self.state_std or hasattr(pf, "logstd")):
-            raise _C.TrlError("fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias, GuassianContPolicy or "
-                              "CategoricalDisPolicy policy")
-        if self.state_std:
-            ps = (ps[0], ps[1], ps[2] // 2, ps[3])
-            if not _C.lib().trl_ppo_sd_supported(*ps):
-                raise _C.TrlError("the fused state-dependent-std update carries H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh / ReLU; "
-                                  "got %s" % (ps,))
-            if dist.collectives_active():
-                raise _C.TrlError("the fused state-dependent-std update runs on one rank (no cross-rank fold exists for this head)")
-        if self.categorical and not _C.lib().trl_ppo_cat_supported(*ps):
-            raise _C.TrlError("the fused categorical update carries H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU; got %s" % (ps,))
-        if self.categorical and dist.collectives_active():
-            raise _C.TrlError("the fused categorical update runs on one rank (no cross-rank fold exists for this head)")
+        # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; the gradient kernel's
+        # HEAD_SD instantiations and their folds (trl_ppo_sd_*); no logstd in the flat vector either, `self.A` = half the head's
+        # width, entropy and the per-element log_std / std statistics arrive through info slots 20, 8-11 and 16-19
+        needs = "fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias, GuassianContPolicy or CategoricalDisPolicy policy"
+        if ps is None or vs is None:
+            raise _C.TrlError(needs)
+        self.head = head_kind(pf, refuse=needs)
+        self.categorical, self.state_std = self.head == HEAD_CAT, self.head == HEAD_SD
+        if self.head != HEAD_GAUSS:
+            ps = _head_spec(self.head, ps)
+            why = _fused_head_refusal(self.head, ps)
+            if why:
+                raise _C.TrlError(why)
         if vs[0] != ps[0] or vs[1] != ps[1] or vs[2] != 1 or vs[3] != ps[3]:
             raise _C.TrlError("policy %s and value %s must share input, width and activation" % (ps, vs))
         self.D, self.H, self.A, self.act = ps
@@ -181,7 +176,7 @@ class _FusedPPO:
         self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
         self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
         lib = _C.lib()
-        sfx = "cat_" if self.categorical else ("sd_" if self.state_std else "")
+        sfx = HEAD_TAG[self.head]
         self._k_grad = (getattr(lib, "trl_ppo_%sminibatch_grad_f32" % sfx), "trl_ppo_%sminibatch_grad_f32" % sfx)
         self._k_fold = (getattr(lib, "trl_ppo_%sreduce_adam_f32" % sfx), "trl_ppo_%sreduce_adam_f32" % sfx)
         self._k_fold_net = (getattr(lib, "trl_ppo_%sreduce_adam_net_f32" % sfx), "trl_ppo_%sreduce_adam_net_f32" % sfx)
@@ -680,33 +675,21 @@ class _FusedPPO:
         out = []
         c_ent = float(self.algo.entropy_coeff)
         A = self.A
+        categorical, state_std = getattr(self, "categorical", False), getattr(self, "state_std", False)
         for r, i, g in zip(raw, info, norms):
             v_var = max((i[13] - i[12] * i[12] / n) / (n - 1), 0.0)
-            if getattr(self, "categorical", False):                     # no `std` in the policy's dict: a2c.py:62-63, 96-101
-                ent = i[20] / n
-                out.append({
-                    'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
-                    'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15],
-                    'ent': ent, 'log_prob': i[1] / n,
-                })
-                continue
-            if getattr(self, "state_std", False):                       # per-element statistics over all n * A values, as logged
-                ent = i[20] / n
-                out.append({
-                    'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
-                    'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15],
-                    'std/mean': i[16], 'std/std': i[17], 'std/max': i[18], 'std/min': i[19],
-                    'ent': ent, 'log_prob': i[1] / n,
-                })
-                continue
-            ent = A * _HALF_LOG_2PI_PLUS_HALF + A * i[8]
-            std_ss = (i[17] ** 2) * (A - 1) if A > 1 else 0.0            # sum over dims of (std - mean)^2
-            out.append({
-                'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
-                'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15],
-                'std/mean': i[16], 'std/std': math.sqrt(n * std_ss / (n * A - 1)), 'std/max': i[18], 'std/min': i[19],
-                'ent': ent, 'log_prob': i[1] / n,
-            })
+            if categorical or state_std:                                # the kernel's entropy sum; SD: per-element statistics
+                ent, std_std = i[20] / n, i[17]                         # over all n * A values, as logged
+            else:
+                ent = A * _HALF_LOG_2PI_PLUS_HALF + A * i[8]
+                std_ss = (i[17] ** 2) * (A - 1) if A > 1 else 0.0        # sum over dims of (std - mean)^2
+                std_std = math.sqrt(n * std_ss / (n * A - 1))
+            d = {'Training/policy_loss': i[0] / n - c_ent * ent, 'Training/vf_loss': i[7] / n,
+                 'v_pred/mean': i[12] / n, 'v_pred/std': math.sqrt(v_var), 'v_pred/max': i[14], 'v_pred/min': -i[15]}
+            if not categorical:                                         # (no `std` in a categorical policy's dict: a2c.py:62-63, 96-101)
+                d.update({'std/mean': i[16], 'std/std': std_std, 'std/max': i[18], 'std/min': i[19]})
+            d['ent'], d['log_prob'] = ent, i[1] / n
+            out.append(d)
         return out
 
     def _infos(self, raw, info, norms, n):
@@ -756,30 +739,37 @@ class _PendingInfos:
         return self._infos
 
 
+_HEAD_OPT_IN = {HEAD_CAT: "TRL_CAT_FUSED_UPDATE", HEAD_SD: "TRL_SD_FUSED_UPDATE"}
+
+
+def _head_spec(kind, ps):
+    """(D, H, A, act) as the head's kernels count A: a [mean | log_std] head of width 2A has A action dimensions."""
+    return (ps[0], ps[1], ps[2] // 2, ps[3]) if kind == HEAD_SD else tuple(ps)
+
+
+def _fused_head_refusal(kind, ps):
+    """Why the fused update does not carry a categorical / state-dependent-std policy of `_head_spec` ps here, or None."""
+    if not getattr(_C.lib(), "trl_ppo_%ssupported" % HEAD_TAG[kind])(*ps):
+        return "the fused %s update carries H == 64, 2 <= D <= 32, %d <= A <= 8, Tanh / ReLU; got %s" \
+            % (HEAD_NAME[kind], 2 if kind == HEAD_CAT else 1, ps)
+    if dist.collectives_active():
+        return "the fused %s update runs on one rank (no cross-rank fold exists for this head)" % HEAD_NAME[kind]
+    return None
+
+
 def make_engine(algo):
     """The fused engine when the networks have the shape its kernels are instantiated for, the generic one otherwise."""
     pf, vf = algo.pf, algo.vf
     ps = pf.mlp2_spec() if hasattr(pf, "mlp2_spec") else None
     vs = vf.mlp2_spec() if hasattr(vf, "mlp2_spec") else None
-    if getattr(pf, "continuous", True) is False:
-        # categorical head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1, opt-in) AND
-        # both nets have a shape its CAT instantiations carry, the optimiser is Adam and this is the only rank
-        if os.environ.get("TRL_CAT_FUSED_UPDATE") == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
-                and hasattr(pf, "logits") and ps is not None and vs is not None \
-                and _C.lib().trl_ppo_cat_supported(*ps) and _C.lib().trl_ppo_cat_supported(vs[0], vs[1], ps[2], vs[3]) \
-                and (vs[0], vs[1], vs[2], vs[3]) == (ps[0], ps[1], 1, ps[3]) \
-                and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
-            return _FusedPPO(algo)
-        return _GenericPPO(algo)
-    if is_state_std(pf):
-        # [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_SD_FUSED_UPDATE=1, opt-in) AND
-        # both nets have a shape its SD instantiations carry, the optimiser is Adam and this is the only rank
-        if os.environ.get("TRL_SD_FUSED_UPDATE") == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
-                and ps is not None and vs is not None and ps[2] % 2 == 0 \
-                and _C.lib().trl_ppo_sd_supported(ps[0], ps[1], ps[2] // 2, ps[3]) \
-                and _C.lib().trl_ppo_sd_supported(vs[0], vs[1], ps[2] // 2, vs[3]) \
-                and (vs[0], vs[1], vs[2], vs[3]) == (ps[0], ps[1], 1, ps[3]) \
-                and getattr(algo, "optimizer_class", None) is optim.Adam and not dist.collectives_active():
+    kind = head_kind(pf)
+    if kind in _HEAD_OPT_IN:
+        # categorical / [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1 /
+        # TRL_SD_FUSED_UPDATE=1, opt-in) AND both nets have a shape the head's instantiations carry, the optimiser is Adam and
+        # this is the only rank
+        if os.environ.get(_HEAD_OPT_IN[kind]) == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
+                and ps is not None and vs is not None and _fused_head_refusal(kind, _head_spec(kind, ps)) is None \
+                and tuple(vs) == (ps[0], ps[1], 1, ps[3]) and getattr(algo, "optimizer_class", None) is optim.Adam:
             return _FusedPPO(algo)
         return _GenericPPO(algo)
     if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
@@ -805,13 +795,11 @@ class _GenericPPO(_FusedPPO):
         self.algo, self.ops = algo, ops
         pf, vf = algo.pf, algo.vf
         # a categorical head (policies.CategoricalDisPolicy): no logstd in the flat vector, trl_cat_losses_f32 for the loss half
-        self.categorical = getattr(pf, "continuous", True) is False and hasattr(pf, "logits")
         # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; no logstd in the flat
         # vector either, trl_gauss_sd_losses_f32 for the loss half, `self.A` = half the head's width
-        self.state_std = not self.categorical and is_state_std(pf)
-        if not self.categorical and not self.state_std and not hasattr(pf, "logstd"):
-            raise _C.TrlError("PPO / A2C kernels need a GuassianContPolicyBasicBias, a GuassianContPolicy or a "
-                              "CategoricalDisPolicy")
+        self.head = head_kind(pf, refuse="PPO / A2C kernels need a GuassianContPolicyBasicBias, a GuassianContPolicy or a "
+                                         "CategoricalDisPolicy")
+        self.categorical, self.state_std = self.head == HEAD_CAT, self.head == HEAD_SD
         if self.state_std:
             head_w = int(ops.linear_layers(pf)[-1][0].shape[0])
             if not 1 <= head_w // 2 <= 32:

@@ -25,11 +25,12 @@ from .ppo import _GenericPPO
 
 class TRPO(A2C):
     def __init__(self, max_kl, cg_damping, v_opt_times, cg_iters, residual_tol, **kwargs):
-        if getattr(kwargs.get("pf"), "continuous", True) is False:
+        from .ppo import HEAD_CAT, HEAD_SD, head_kind
+        kind = head_kind(kwargs.get("pf"))
+        if kind == HEAD_CAT:
             raise _C.TrlError("TRPO with a categorical policy is not built: its Fisher-vector product and line search are "
                               "kernels for the diagonal-Gaussian head; discrete actions run on PPO / A2C")
-        from .ppo import is_state_std
-        if is_state_std(kwargs.get("pf")):
+        if kind == HEAD_SD:
             raise _C.TrlError("TRPO with a state-dependent-std policy is not built: its Fisher-vector product and line search "
                               "are kernels for the state-independent logstd; GuassianContPolicy runs on PPO / A2C")
         super().__init__(**kwargs)

@@ -22,11 +22,12 @@ from .ppo import _GenericPPO
 
 class VMPO(A2C):
     def __init__(self, pf, opt_epochs=10, eta_eps=0.02, alpha_eps=0.1, clipped_value_loss=False, **kwargs):
-        if getattr(pf, "continuous", True) is False:
+        from .ppo import HEAD_CAT, HEAD_SD, head_kind
+        kind = head_kind(pf)
+        if kind == HEAD_CAT:
             raise _C.TrlError("VMPO with a categorical policy is not built: its KL terms are kernels for the "
                               "diagonal-Gaussian head; discrete actions run on PPO / A2C")
-        from .ppo import is_state_std
-        if is_state_std(pf):
+        if kind == HEAD_SD:
             raise _C.TrlError("VMPO with a state-dependent-std policy is not built: its KL terms are kernels for the "
                               "state-independent logstd; GuassianContPolicy runs on PPO / A2C")
         self.target_pf = copy.deepcopy(pf)

@@ -293,16 +293,14 @@ class VecOnPolicyCollector(VecCollector):
         # a categorical policy (policies.CategoricalDisPolicy) over Discrete(A): `_dims[1]` = A is the head's width, the
         # ring's `acts` are (N, 1) indices.  The per-step route uses trl_cat_act_f32 in place of trl_gauss_explore_f32; the
         # persistent rollout has a categorical head for the shapes of trl_rollout_cat_supported (see the end of this method)
-        self._cat = getattr(self.pf, "continuous", True) is False and hasattr(self.pf, "logits")
         # a state-dependent-std Gaussian policy (policies.GuassianContPolicy): the head is [mean | log_std], `_dims[1]` = A is
         # half its width.  The per-step route uses trl_gauss_sd_explore_f32 in place of trl_gauss_explore_f32 on the same
         # (N, A) noise block; the persistent rollout has a head for it for the shapes of trl_rollout_sd_supported, opt-in
         # (see the end of this method).  The TRL_CAT_* routes do not apply.
-        from ..policies.continuous_policy import is_state_std
-        self._sd = not self._cat and is_state_std(self.pf)
-        if not self._cat and not self._sd and not hasattr(self.pf, "logstd"):
-            raise _C.TrlError("the on-policy collector supports GuassianContPolicyBasicBias, GuassianContPolicy (an even "
-                              "[mean | log_std] head) and CategoricalDisPolicy policies")
+        from ..policies.continuous_policy import HEAD_CAT, HEAD_SD, head_kind
+        kind = head_kind(self.pf, refuse="the on-policy collector supports GuassianContPolicyBasicBias, GuassianContPolicy "
+                                         "(an even [mean | log_std] head) and CategoricalDisPolicy policies")
+        self._cat, self._sd = kind == HEAD_CAT, kind == HEAD_SD
         if self._cat and self.noise_mode != "device":
             raise _C.TrlError("a categorical policy draws its actions from the device Philox stream only "
                               "(noise_mode=\"device\"): the reference samples through torch.multinomial, whose host stream "

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include "trl_common.h"
 #include "trl_mlp.h"
+#include "trl_head.h"
 #include "trl_comm.h"
 
 struct PpoDev {
@@ -88,12 +89,9 @@ template <int D, int H, int A> struct WvShapeSD : WvShape<D, H, A> {
   static constexpr int FOLD = WV_WAVES * P_STRIDE;
   static constexpr int LDS_FLOATS = B::MAIN > FOLD ? B::MAIN : FOLD;
 };
-template <int D, int H, int A, bool SD> struct WvPick { using T = WvShape<D, H, A>; };
-template <int D, int H, int A> struct WvPick<D, H, A, true> { using T = WvShapeSD<D, H, A>; };
+template <int D, int H, int A, int HEAD> struct WvPick { using T = WvShape<D, H, A>; };
+template <int D, int H, int A> struct WvPick<D, H, A, HEAD_SD> { using T = WvShapeSD<D, H, A>; };
 #define SD_HALF_LOG_2PI_PLUS_HALF 1.4189385332046727f   /* k_gauss_sd.hip's constant: entropy of a unit normal */
-// SD: doubles per workgroup in the SECOND block of scalar rows (behind the n_wg x 8 block every head writes):
-//   0 log_std sum  1 sum of squares  2 max  3 -min   4 std sum  5 sum of squares  6 max  7 -min   8 samples   9..15 zero
-#define SD_SCAL 16
 
 __device__ __forceinline__ f32x4 lds4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // sum over the 16 lanes of a DPP row (same lane group g, all sample lanes j) with row rotations on the
@@ -126,14 +124,15 @@ __device__ __forceinline__ float row_sum16(float v) {
 // -- appears where W3 / b3 are loaded and where dW3 / db3 go to the gradient image.  Per element the arithmetic is
 // gauss_sd_losses_kernel's (k_gauss_sd.hip); the per-sample statistics of log_std and std leave through a second block of
 // scalar rows (trl_ppo_sd_scalar_stride).
-template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
+template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, int HEAD = HEAD_GAUSS>
 __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_wg_net) {
-  using S = typename WvPick<D, H, A, SD>::T;
-  constexpr bool WIDE = D > 17;                      // a second 16-feature group (features 16 .. 31) on the matrix pipe
+  using S = typename WvPick<D, H, A, HEAD>::T;
+  constexpr bool WIDE = D > 17,                      // a second 16-feature group (features 16 .. 31) on the matrix pipe
+                 CAT = HEAD == HEAD_CAT, SD = HEAD == HEAD_SD,
+                 SDP = SD && IS_PF;                  // (SD's value pass differs in the stride of its gradient image only)
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!CAT || (IS_PF && RT), "the categorical head is a policy pass of the runtime-dims kernels");
-  static_assert(!SD || (RT && !CAT), "the state-dependent-std head belongs to the runtime-dims kernels");
-  constexpr bool SDP = SD && IS_PF;                  // (SD's value pass differs in the stride of its gradient image only)
+  static_assert(!SD || RT, "the state-dependent-std head belongs to the runtime-dims kernels");
   constexpr int AS = CAT ? 1 : 0;                    // CAT: floats per stored action (0: the Gaussian's O)
   const int Dr = RT ? a.D : D;                       // input features = row stride of obs and of W1
   const int O = IS_PF ? (RT ? a.A : A) : 1;          // outputs
@@ -1026,7 +1025,7 @@ __device__ __noinline__ void fold_sd_stats(const double* __restrict__ base, cons
 // range; `stats`: this call also takes the network's scalar statistics (waves 2 / 3)
 // CAT: the policy block has no logstd tail (logstd is null) and wave 3 folds the entropy column instead
 // SD: no logstd tail either; wave 3 folds the entropy column and the second block of scalar rows (behind the n_wg x 8)
-template <bool CAT = false, bool SD = false>
+template <int HEAD = HEAD_GAUSS>
 __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ partial,
                                                   const double* __restrict__ scal, int n_wg, int n_pf,
                                                   int p_stride, int p_pf, int p_vf,
@@ -1053,10 +1052,10 @@ __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ part
   // path of the blocks whose 64 parameters matter: wave 2 its network's statistics, wave 3 of the policy's block log_std
   // and std.
   if (stats && wave == 2) fold_scalar_stats(scal + (size_t)row0 * 8, nrow, net, lane, info);
-  if constexpr (SD) {
+  if constexpr (HEAD == HEAD_SD) {
     if (stats && net == 0 && wave == 3)
       fold_sd_stats(scal + (size_t)row0 * 8, scal + (size_t)n_wg * 8 + (size_t)row0 * SD_SCAL, nrow, n_act, lane, info);
-  } else if constexpr (CAT) {
+  } else if constexpr (HEAD == HEAD_CAT) {
     if (stats && net == 0 && wave == 3) fold_entropy_stats(scal + (size_t)row0 * 8, nrow, lane, info);
   } else {
     if (stats && net == 0 && wave == 3 && logstd) fold_logstd_stats(logstd, n_act, lane, info);
@@ -1064,13 +1063,13 @@ __device__ __forceinline__ float ppo_reduce_block(const float* __restrict__ part
   return gval;
 }
 
-template <bool CAT = false, bool SD = false>
+template <int HEAD = HEAD_GAUSS>
 __global__ __launch_bounds__(64 * RED_WAVES) void ppo_reduce_kernel(const float* __restrict__ partial,
                                                          const double* __restrict__ scal, int n_wg, int n_pf,
                                                          int p_stride, int p_pf, int p_vf,
                                                          const float* __restrict__ logstd, int n_act,
                                                          float* __restrict__ grads, double* __restrict__ info) {
-  ppo_reduce_block<CAT, SD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
+  ppo_reduce_block<HEAD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, blockIdx.y, blockIdx.x,
                         blockIdx.x == gridDim.x - 1);
 }
 
@@ -1175,7 +1174,7 @@ __device__ __forceinline__ void adam_element(const AdamDev& a, int e, float gr) 
 // blocks -- 4 waves per SIMD -- resident beside each other.  With the statistics inlined into the job loop the kernel took
 // 156 registers: the second rank's blocks found no room next to the first's, its norm rendezvous could not complete, and
 // both ranks sat out their time-outs -- round 6, caught by tests/test_bench_multirank_gpu.py)
-template <bool LOOP, bool CAT = false, bool SD = false>   // LOOP false: the grid has one block per job (no job loop: the common launch)
+template <bool LOOP, int HEAD = HEAD_GAUSS>   // LOOP false: the grid has one block per job (no job loop: the common launch)
 __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(const float* __restrict__ partial,
                                                               const double* __restrict__ scal, int n_wg, int n_pf,
                                                               int p_stride, int p_pf, int p_vf,
@@ -1219,7 +1218,7 @@ __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(cons
   for (int j = blk; j < (LOOP ? n_jobs : blk + 1); j += LOOP ? grid : 1) {
     const int net = j / nb, bx = j - net * nb;
     if (j != blk) __syncthreads();                                // the fold's LDS image is read by wave 0 of the previous job
-    float gval = ppo_reduce_block<CAT, SD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
+    float gval = ppo_reduce_block<HEAD>(partial, scal, n_wg, n_pf, p_stride, p_pf, p_vf, logstd, n_act, grads, info, net, bx, bx == nb - 1);
     if (wave == 0) {
       if (xrank) {
         // C1 of SURVEY.md 8(e) inside the launch: every rank pushes its 64 folded values into its slot on all ranks and
@@ -1316,16 +1315,16 @@ __global__ __launch_bounds__(64 * RED_WAVES, 4) void ppo_reduce_adam_kernel(cons
 }
 
 // ---------------------------------------------------------------- the gradient launch: one network pass per workgroup
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, int HEAD = HEAD_GAUSS>
 __global__ __launch_bounds__(WV_THREADS, 1) void ppo_grad_wave_kernel(PpoDev a) {
-  static_assert(!CAT || RT, "categorical head: runtime-dims tiles");
-  static_assert(!SD || (RT && !CAT), "state-dependent-std head: runtime-dims tiles");
+  static_assert(HEAD == HEAD_GAUSS || RT, "categorical / state-dependent-std head: runtime-dims tiles");
+  constexpr int HEAD_VF = HEAD == HEAD_CAT ? HEAD_GAUSS : HEAD;   // the value pass of a categorical policy is the Gaussian's
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef TRL_CHAIN_CLK                                  /* tools/time_chains.py: when did this workgroup start and end (100 MHz) */
   const unsigned long long clk0 = wall_clock64();
 #endif
-  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, CAT, SD>(a, lds, blockIdx.x, a.n_pf);
-  else                          ppo_wave_pass<D, H, A, ACT, false, CONTIG, RT, false, SD>(a, lds, blockIdx.x - a.n_pf, a.n_wg - a.n_pf);
+  if ((int)blockIdx.x < a.n_pf) ppo_wave_pass<D, H, A, ACT, true, CONTIG, RT, HEAD>(a, lds, blockIdx.x, a.n_pf);
+  else                          ppo_wave_pass<D, H, A, ACT, false, CONTIG, RT, HEAD_VF>(a, lds, blockIdx.x - a.n_pf, a.n_wg - a.n_pf);
 #ifdef TRL_CHAIN_CLK
   __syncthreads();
   if (threadIdx.x == 0) {                             // the row's unused 8th scalar and the last three padding floats of the partial row
@@ -1372,99 +1371,54 @@ __global__ __launch_bounds__(256) void mlp2_forward_kernel(const float* __restri
 // ================================================================ host side
 #define SHAPE_IS(d, h, o) (D == (d) && H == (h) && A == (o))
 
-// Shapes the fused minibatch kernels carry: the benchmark shape as a compile-time instantiation, and any D in [2, 32],
-// A in [1, 8] at H = 64 through the runtime-dims instantiations (ppo_wave_pass<..., RT = true>: the 17- and the 32-wide tile).
-static bool ppo_shape_rt(int D, int H, int A) { return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8; }
-extern "C" int trl_ppo_partial_stride(int D, int H, int A) {
-  if (SHAPE_IS(17, 64, 6)) return PpoShape<17, 64, 6>::P_STRIDE;
-  if (ppo_shape_rt(D, H, A)) {
-    const int p_pf = H * D + H + H * H + H + A * H + A + A, p_vf = H * D + H + H * H + H + H + 1;
+// Shapes the fused minibatch kernels carry: the benchmark shape as a compile-time instantiation (Gaussian head only), and
+// any D in [2, 32] at H = 64 with the head's range of A (HEADS, trl_head.h) through the runtime-dims instantiations
+// (ppo_wave_pass<..., RT = true, HEAD>: the 17- and the 32-wide tile).  The flat policy block is [W1 b1 W2 b2 W3 b3] with
+// the head's rows, and the Gaussian's logstd tail: up to 1040 head floats (SD, 2A rows) against the Gaussian's 528.
+static int ppo_stride_for(int D, int H, int A, int head) {
+  if (head == HEAD_GAUSS && SHAPE_IS(17, 64, 6)) return PpoShape<17, 64, 6>::P_STRIDE;
+  if (head_shape_ok(head, D, H, A)) {
+    const int p_pf = ppo_p_pf(D, H, A, head), p_vf = ppo_p_vf(D, H);
     return ((p_pf > p_vf ? p_pf : p_vf) + 63) & ~63;
   }
-  trl_set_error("trl_ppo_partial_stride: shape D=%d H=%d A=%d not instantiated", D, H, A);
+  trl_set_error("trl_ppo_%spartial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, %d <= A <= %d)",
+                HEADS[head].tag, D, H, A, HEADS[head].a_min, HEADS[head].a_max);
   return TRL_EUNSUPPORTED;
 }
-
-// Categorical head (ppo_wave_pass<..., CAT = true>): the runtime-dims tiles only, at least two actions; the flat policy
-// block is [W1 b1 W2 b2 W3 b3] (no logstd tail).
-static bool ppo_cat_shape(int D, int H, int A) { return H == 64 && D >= 2 && D <= 32 && A >= 2 && A <= 8; }
-static int ppo_p_pf(int D, int H, int A, bool cat) { return H * D + H + H * H + H + A * H + A + (cat ? 0 : A); }
-static int ppo_p_vf(int D, int H) { return H * D + H + H * H + H + H + 1; }
-extern "C" int trl_ppo_cat_supported(int D, int H, int A, int act) {
-  return (ppo_cat_shape(D, H, A) && (act == TRL_ACT_TANH || act == TRL_ACT_RELU)) ? 1 : 0;
-}
-extern "C" int trl_ppo_cat_partial_stride(int D, int H, int A) {
-  if (ppo_cat_shape(D, H, A)) {
-    const int p_pf = ppo_p_pf(D, H, A, true), p_vf = ppo_p_vf(D, H);
-    return ((p_pf > p_vf ? p_pf : p_vf) + 63) & ~63;
-  }
-  trl_set_error("trl_ppo_cat_partial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8)", D, H, A);
-  return TRL_EUNSUPPORTED;
-}
-
-// State-dependent-std head (ppo_wave_pass<..., SD = true>): the runtime-dims tiles only; the flat policy block is
-// [W1 b1 W2 b2 W3 b3] with 2A head rows [mean | log_std] (no logstd tail), up to 1040 head floats against the Gaussian's 528.
-#define HEAD_GAUSS 0
-#define HEAD_CAT 1
-#define HEAD_SD 2
-static bool ppo_sd_shape(int D, int H, int A) { return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8; }
-extern "C" int trl_ppo_sd_supported(int D, int H, int A, int act) {
-  return (ppo_sd_shape(D, H, A) && (act == TRL_ACT_TANH || act == TRL_ACT_RELU)) ? 1 : 0;
-}
-static int ppo_p_pf_head(int D, int H, int A, int head) { return head == HEAD_SD ? ppo_p_pf(D, H, 2 * A, true) : ppo_p_pf(D, H, A, head == HEAD_CAT); }
-extern "C" int trl_ppo_sd_partial_stride(int D, int H, int A) {
-  if (ppo_sd_shape(D, H, A)) {
-    const int p_pf = ppo_p_pf_head(D, H, A, HEAD_SD), p_vf = ppo_p_vf(D, H);
-    return ((p_pf > p_vf ? p_pf : p_vf) + 63) & ~63;
-  }
-  trl_set_error("trl_ppo_sd_partial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, 1 <= A <= 8)", D, H, A);
-  return TRL_EUNSUPPORTED;
-}
+extern "C" int trl_ppo_partial_stride(int D, int H, int A) { return ppo_stride_for(D, H, A, HEAD_GAUSS); }
+extern "C" int trl_ppo_cat_partial_stride(int D, int H, int A) { return ppo_stride_for(D, H, A, HEAD_CAT); }
+extern "C" int trl_ppo_sd_partial_stride(int D, int H, int A) { return ppo_stride_for(D, H, A, HEAD_SD); }
+extern "C" int trl_ppo_cat_supported(int D, int H, int A, int act) { return head_supported(HEAD_CAT, D, H, A, act); }
+extern "C" int trl_ppo_sd_supported(int D, int H, int A, int act) { return head_supported(HEAD_SD, D, H, A, act); }
 // doubles of scal_partial per workgroup: the n_wg x 8 block of every head, then n_wg x SD_SCAL (see SD_SCAL)
-extern "C" int trl_ppo_sd_scalar_stride(void) { return 8 + SD_SCAL; }
+extern "C" int trl_ppo_sd_scalar_stride(void) { return HEADS[HEAD_SD].scal_stride; }
 static_assert(WvShapeSD<17, 64, 8>::P_STRIDE == 6400 && WvShapeSD<32, 64, 8>::P_STRIDE == 7360, "SD image strides at A = 8");
 static_assert(WvShapeSD<32, 64, 8>::LDS_FLOATS * sizeof(float) <= 160 * 1024, "SD fold images fit the LDS");
-static int ppo_stride_for(int D, int H, int A, int head) {
-  return head == HEAD_SD ? trl_ppo_sd_partial_stride(D, H, A)
-                         : (head == HEAD_CAT ? trl_ppo_cat_partial_stride(D, H, A) : trl_ppo_partial_stride(D, H, A));
-}
 
 // Kernel generations that were built and measured on MI355X before this one (profiles/README.md): groups of
 // 4 waves per tile with LDS rendezvous (85 us per 65 536-sample minibatch), this wave-per-tile kernel (64 us),
 // and a PAIR of waves per tile with two waves per SIMD (75 us) -- on gfx950 the fp32 MFMA and the VALU do not
 // overlap across the two waves of a SIMD (tools/ubench/mfma_valu.hip: an MFMA-only wave and a VALU-only wave
 // on one SIMD take the SUM of their times), so a second wave only adds its duplicated loss / fetch work.
-template <int D, int H, int A, int ACT, bool CONTIG, bool RT, bool CAT = false, bool SD = false>
+template <int D, int H, int A, int ACT, bool CONTIG, bool RT, int HEAD>
 static int launch_ppo_v(const PpoDev& d, hipStream_t s) {
-  using S = typename WvPick<D, H, A, SD>::T;
+  using S = typename WvPick<D, H, A, HEAD>::T;
   const size_t lds = S::LDS_FLOATS * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT, SD>,
+    hipError_t e = hipFuncSetAttribute((const void*)ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, HEAD>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { trl_set_error("ppo_grad: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_set = true;
   }
-  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, CAT, SD>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d);
+  hipLaunchKernelGGL((ppo_grad_wave_kernel<D, H, A, ACT, CONTIG, RT, HEAD>), dim3(d.n_wg), dim3(WV_THREADS), lds, s, d);
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
 // N % 16 == 0 (every tile = 16 consecutive envs of one time row): scalar tile addressing; any other N: per-lane cells.
-template <int D, int H, int A, int ACT, bool RT>
+template <int D, int H, int A, int ACT, bool RT, int HEAD = HEAD_GAUSS>
 static int launch_ppo(const PpoDev& d, hipStream_t s) {
-  return (d.N % 16 == 0) ? launch_ppo_v<D, H, A, ACT, true, RT>(d, s) : launch_ppo_v<D, H, A, ACT, false, RT>(d, s);
-}
-
-template <int D, int ACT>
-static int launch_ppo_cat(const PpoDev& d, hipStream_t s) {
-  return (d.N % 16 == 0) ? launch_ppo_v<D, 64, 8, ACT, true, true, true>(d, s)
-                         : launch_ppo_v<D, 64, 8, ACT, false, true, true>(d, s);
-}
-
-template <int D, int ACT>
-static int launch_ppo_sd(const PpoDev& d, hipStream_t s) {
-  return (d.N % 16 == 0) ? launch_ppo_v<D, 64, 8, ACT, true, true, false, true>(d, s)
-                         : launch_ppo_v<D, 64, 8, ACT, false, true, false, true>(d, s);
+  return (d.N % 16 == 0) ? launch_ppo_v<D, H, A, ACT, true, RT, HEAD>(d, s) : launch_ppo_v<D, H, A, ACT, false, RT, HEAD>(d, s);
 }
 
 // Policy / value split of the grid.  A policy tile costs more than a value tile (head, log-prob loss,
@@ -1490,16 +1444,10 @@ extern "C" int trl_ppo_wg_split(int D, int H, int A, int n_tiles, int n_wg) {
 static int resolve_pf_wgs(int n_wg, int n_wg_pf) { return n_wg_pf < 0 ? 0 : (n_wg_pf > 0 ? n_wg_pf : n_wg / 2); }
 
 static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HEAD_GAUSS) {
-  const bool cat = head == HEAD_CAT, sd = head == HEAD_SD;
   if (!p) { trl_set_error("ppo_grad: null descriptor"); return TRL_EINVAL; }
-  if (sd && !trl_ppo_sd_supported(p->D, p->H, p->A, p->act)) {
-    trl_set_error("ppo_sd_grad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh / ReLU)",
-                  p->D, p->H, p->A, p->act);
-    return TRL_EUNSUPPORTED;
-  }
-  if (cat && !trl_ppo_cat_supported(p->D, p->H, p->A, p->act)) {
-    trl_set_error("ppo_cat_grad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, 2 <= A <= 8, Tanh / ReLU)",
-                  p->D, p->H, p->A, p->act);
+  if (!head_supported(head, p->D, p->H, p->A, p->act)) {      // (the benchmark shape is inside the Gaussian's range)
+    trl_set_error("ppo_%sgrad: shape D=%d H=%d A=%d act=%d not instantiated (H == 64, 2 <= D <= 32, %d <= A <= %d, Tanh / ReLU)",
+                  HEADS[head].tag, p->D, p->H, p->A, p->act, HEADS[head].a_min, HEADS[head].a_max);
     return TRL_EUNSUPPORTED;
   }
   TRL_REQUIRE(p->obs && p->acts && p->advs && p->rets, "null rollout tensor");
@@ -1516,7 +1464,7 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HE
   const int D = p->D, H = p->H, A = p->A;
   TRL_REQUIRE(((uintptr_t)p->partial & 15) == 0 && (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 3) == 0,
               "partial rows must be 16-byte aligned, parameter blocks 4-byte aligned");
-  TRL_REQUIRE(cat || sd || !SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
+  TRL_REQUIRE(head != HEAD_GAUSS || !SHAPE_IS(17, 64, 6) || (((uintptr_t)p->pf_params | (uintptr_t)p->vf_params) & 15) == 0,
               "parameter blocks of the benchmark shape must be 16-byte aligned");
   PpoDev d;
   d.obs = p->obs; d.acts = p->acts; d.advs = p->advs; d.rets = p->rets; d.old_values = p->old_values;
@@ -1528,32 +1476,16 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HE
   d.n_pf = resolve_pf_wgs(p->n_wg, p->n_wg_pf);
   d.D = D; d.A = A;
   hipStream_t s = (hipStream_t)stream;
-  if (cat) {                                          // actual dims at run time inside the 17- / 32-feature tile; acts is (rows, N, 1)
-    d.p_stride = trl_ppo_cat_partial_stride(D, H, A);
-    d.tanh_action = 0;
-    if (D <= 17) return p->act == TRL_ACT_TANH ? launch_ppo_cat<17, TRL_ACT_TANH>(d, s) : launch_ppo_cat<17, TRL_ACT_RELU>(d, s);
-    return p->act == TRL_ACT_TANH ? launch_ppo_cat<32, TRL_ACT_TANH>(d, s) : launch_ppo_cat<32, TRL_ACT_RELU>(d, s);
-  }
-  if (sd) {                                           // acts is (rows, N, A), pf_params [W1 b1 W2 b2 W3 b3] with 2A head rows
-    d.p_stride = trl_ppo_sd_partial_stride(D, H, A);
-    if (D <= 17) return p->act == TRL_ACT_TANH ? launch_ppo_sd<17, TRL_ACT_TANH>(d, s) : launch_ppo_sd<17, TRL_ACT_RELU>(d, s);
-    return p->act == TRL_ACT_TANH ? launch_ppo_sd<32, TRL_ACT_TANH>(d, s) : launch_ppo_sd<32, TRL_ACT_RELU>(d, s);
-  }
-  if (SHAPE_IS(17, 64, 6)) {
-    d.p_stride = PpoShape<17, 64, 6>::P_STRIDE;
-    if (p->act == TRL_ACT_TANH) return launch_ppo<17, 64, 6, TRL_ACT_TANH, false>(d, s);
-    if (p->act == TRL_ACT_RELU) return launch_ppo<17, 64, 6, TRL_ACT_RELU, false>(d, s);
-  } else if (ppo_shape_rt(D, H, A) && D <= 17) {      // actual dims at run time inside the (17, 64, 8) tile
-    d.p_stride = trl_ppo_partial_stride(D, H, A);
-    if (p->act == TRL_ACT_TANH) return launch_ppo<17, 64, 8, TRL_ACT_TANH, true>(d, s);
-    if (p->act == TRL_ACT_RELU) return launch_ppo<17, 64, 8, TRL_ACT_RELU, true>(d, s);
-  } else if (ppo_shape_rt(D, H, A)) {                 // 18 .. 32 input features: the (32, 64, 8) tile
-    d.p_stride = trl_ppo_partial_stride(D, H, A);
-    if (p->act == TRL_ACT_TANH) return launch_ppo<32, 64, 8, TRL_ACT_TANH, true>(d, s);
-    if (p->act == TRL_ACT_RELU) return launch_ppo<32, 64, 8, TRL_ACT_RELU, true>(d, s);
-  }
-  trl_set_error("ppo_grad: shape D=%d H=%d A=%d act=%d not instantiated", D, H, A, p->act);
-  return TRL_EUNSUPPORTED;
+  d.p_stride = ppo_stride_for(D, H, A, head);
+  if (head == HEAD_CAT) d.tanh_action = 0;            // acts is (rows, N, 1): the action index
+  if (head == HEAD_GAUSS && SHAPE_IS(17, 64, 6))      // the compile-time instantiation of the benchmark shape
+    return p->act == TRL_ACT_TANH ? launch_ppo<17, 64, 6, TRL_ACT_TANH, false>(d, s) : launch_ppo<17, 64, 6, TRL_ACT_RELU, false>(d, s);
+  // actual dims at run time inside the (17, 64, 8) tile, or with 18 .. 32 input features the (32, 64, 8) tile
+  return with_head(head, [&](auto hd) {
+    return with_tile_act(D, p->act, [&](auto tile, auto act) {
+      return launch_ppo<decltype(tile)::value, 64, 8, decltype(act)::value, true, decltype(hd)::value>(d, s);
+    });
+  });
 }
 
 extern "C" int trl_ppo_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, stream); }
@@ -1567,26 +1499,22 @@ extern "C" int trl_ppo_cat_minibatch_grad_f32(const trl_ppo_batch_t* p, void* st
 // rows' eighth column), then the policy workgroups' log_std / std statistics (trl_ppo_sd_reduce_*_f32 fold both).
 extern "C" int trl_ppo_sd_minibatch_grad_f32(const trl_ppo_batch_t* p, void* stream) { return ppo_grad_launch(p, stream, HEAD_SD); }
 
+// pf_params: the Gaussian's logstd tail is read from it (may be null: no log_std / std statistics); the other heads have
+// none -- wave 3 folds the entropy column (and, SD, the second scalar block) instead
 static int launch_reduce(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
                          const float* pf_params, float* grads, double* info, void* stream, int head) {
-  const bool cat = head == HEAD_CAT;
   TRL_REQUIRE(partial && scal_partial && grads && info, "null pointer");
   TRL_REQUIRE(n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg, "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
   const int ps = ppo_stride_for(D, H, A, head);
   if (ps < 0) return ps;
-  const int p_pf = ppo_p_pf_head(D, H, A, head), p_vf = ppo_p_vf(D, H);
-  if (head == HEAD_SD)                                // no logstd tail; wave 3 folds the entropy column and the second scalar block
-    hipLaunchKernelGGL((ppo_reduce_kernel<false, true>), dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
-                       (const float*)nullptr, A, grads, info);
-  else if (cat)                                            // no logstd tail: nothing of it is folded, the entropy column is
-    hipLaunchKernelGGL(ppo_reduce_kernel<true>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
-                       (const float*)nullptr, A, grads, info);
-  else
-    hipLaunchKernelGGL(ppo_reduce_kernel<false>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                       partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
-                       pf_params ? pf_params + (p_pf - A) : (const float*)nullptr, A, grads, info);
+  const int p_pf = ppo_p_pf(D, H, A, head), p_vf = ppo_p_vf(D, H);
+  const float* logstd = (HEADS[head].logstd_tail && pf_params) ? pf_params + (p_pf - A) : nullptr;
+  with_head(head, [&](auto hd) {
+    hipLaunchKernelGGL(ppo_reduce_kernel<decltype(hd)::value>, dim3(trl_ceil_div(ps, RED_CHUNK), 2), dim3(64 * RED_WAVES), 0,
+                       (hipStream_t)stream, partial, scal_partial, n_wg, resolve_pf_wgs(n_wg, n_wg_pf), ps, p_pf, p_vf,
+                       logstd, A, grads, info);
+    return 0;
+  });
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
@@ -1597,15 +1525,13 @@ extern "C" int trl_ppo_reduce_f32(const float* partial, const double* scal_parti
 // categorical head: pf_params is accepted for symmetry and not read (there is no logstd); info[20] = entropy sum
 extern "C" int trl_ppo_cat_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
                                       int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
-  (void)pf_params;
-  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, HEAD_CAT);
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, HEAD_CAT);
 }
 // state-dependent-std head: pf_params is accepted for symmetry and not read; info[8..11] / info[16..19] = log_std / std
 // statistics over all samples x A elements, info[20] = entropy sum (trl_gauss_sd_losses_f32's row)
 extern "C" int trl_ppo_sd_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D,
                                      int H, int A, const float* pf_params, float* grads, double* info, void* stream) {
-  (void)pf_params;
-  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, nullptr, grads, info, stream, HEAD_SD);
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, HEAD_SD);
 }
 
 static int fill_adam(const trl_adam_t* p, AdamDev& d) {
@@ -1632,16 +1558,18 @@ static int fill_adam(const trl_adam_t* p, AdamDev& d) {
   return TRL_OK;
 }
 
-extern "C" int trl_ppo_reduce_adam_workspace(int D, int H, int A) {
-  const int ps = trl_ppo_partial_stride(D, H, A);
+static int reduce_adam_workspace(int D, int H, int A, int head) {
+  const int ps = ppo_stride_for(D, H, A, head);
   if (ps < 0) return ps;
   return 16 + 4 * trl_ceil_div(ps, RED_CHUNK);       // header + {ss, epoch} per block and network
 }
+extern "C" int trl_ppo_reduce_adam_workspace(int D, int H, int A) { return reduce_adam_workspace(D, H, A, HEAD_GAUSS); }
+extern "C" int trl_ppo_cat_reduce_adam_workspace(int D, int H, int A) { return reduce_adam_workspace(D, H, A, HEAD_CAT); }
+extern "C" int trl_ppo_sd_reduce_adam_workspace(int D, int H, int A) { return reduce_adam_workspace(D, H, A, HEAD_SD); }
 
 static int launch_reduce_adam(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
                               float* grads, double* info, const trl_adam_t* adam, float* workspace, const XrArgs* xr,
                               int max_blocks, void* stream, int only_net = -1, int head = HEAD_GAUSS) {
-  const bool cat = head == HEAD_CAT;
   TRL_REQUIRE(partial && scal_partial && grads && info && workspace, "null pointer");
   TRL_REQUIRE(only_net >= 0 ? n_wg >= 1 : (n_wg >= 2 && n_wg_pf >= 0 && n_wg_pf < n_wg), "need n_wg >= 2 and n_wg_pf in [0, n_wg)");
   const int ps = ppo_stride_for(D, H, A, head);
@@ -1649,7 +1577,7 @@ static int launch_reduce_adam(const float* partial, const double* scal_partial, 
   AdamDev d;
   int rc = fill_adam(adam, d);
   if (rc) return rc;
-  const int p_pf = ppo_p_pf_head(D, H, A, head), p_vf = ppo_p_vf(D, H);
+  const int p_pf = ppo_p_pf(D, H, A, head), p_vf = ppo_p_vf(D, H);
   TRL_REQUIRE(adam->n_groups == 2 && adam->group_sizes[0] == p_pf && adam->group_sizes[1] == p_vf,
               "optimiser groups must be [policy | value] of this shape");
   TRL_REQUIRE(adam->grads == grads, "adam->grads must be the reduce output");
@@ -1661,40 +1589,18 @@ static int launch_reduce_adam(const float* partial, const double* scal_partial, 
   if (max_blocks > 0 && max_blocks < grid) grid = max_blocks;
   const int n_pf = only_net == 0 ? n_wg : (only_net == 1 ? 0 : resolve_pf_wgs(n_wg, n_wg_pf));
   const int jobs = (only_net >= 0 ? 1 : 2) * trl_ceil_div(ps, RED_CHUNK);
-  if (head == HEAD_SD) {                              // no logstd pointer; wave 3 folds the entropy column and the second scalar block
-    if (grid == jobs)
-      hipLaunchKernelGGL((ppo_reduce_adam_kernel<false, false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
-                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
-    else
-      hipLaunchKernelGGL((ppo_reduce_adam_kernel<true, false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
-                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-  }
-  if (cat) {                                          // no logstd pointer: its statistics do not exist; wave 3 folds the entropy column
-    if (grid == jobs)
-      hipLaunchKernelGGL((ppo_reduce_adam_kernel<false, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
-                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
-    else
-      hipLaunchKernelGGL((ppo_reduce_adam_kernel<true, true>), dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                         partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, (const float*)nullptr, A, grads, info, d, workspace,
-                         (unsigned)adam->step_count, adam->device_state, 0, none, only_net);
-    TRL_LAUNCH_CHECK();
-    return TRL_OK;
-  }
-  if (grid == jobs)
-    hipLaunchKernelGGL(ppo_reduce_adam_kernel<false>, dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                       partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf,
-                       (const float*)(adam->params + (p_pf - A)), A, grads, info, d, workspace, (unsigned)adam->step_count,
-                       adam->device_state, xr ? 1 : 0, xr ? *xr : none, only_net);
-  else
-    hipLaunchKernelGGL(ppo_reduce_adam_kernel<true>, dim3(grid), dim3(64 * RED_WAVES), 0, (hipStream_t)stream,
-                       partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf,
-                       (const float*)(adam->params + (p_pf - A)), A, grads, info, d, workspace, (unsigned)adam->step_count,
-                       adam->device_state, xr ? 1 : 0, xr ? *xr : none, only_net);
+  // the Gaussian's logstd tail; the other heads have none: wave 3 folds the entropy column (SD: and the second scalar block)
+  const float* logstd = HEADS[head].logstd_tail ? adam->params + (p_pf - A) : nullptr;
+  const unsigned epoch = (unsigned)adam->step_count;
+  with_head(head, [&](auto hd) {
+    auto launch = [&](auto loop) {
+      hipLaunchKernelGGL((ppo_reduce_adam_kernel<decltype(loop)::value, decltype(hd)::value>), dim3(grid), dim3(64 * RED_WAVES), 0,
+                         (hipStream_t)stream, partial, scal_partial, n_wg, n_pf, ps, p_pf, p_vf, logstd, A, grads, info, d,
+                         workspace, epoch, adam->device_state, xr ? 1 : 0, xr ? *xr : none, only_net);
+    };
+    if (grid == jobs) launch(std::false_type{}); else launch(std::true_type{});
+    return 0;
+  });
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
@@ -1719,11 +1625,6 @@ extern "C" int trl_ppo_reduce_adam_net_f32(const float* partial, const double* s
 
 // The categorical head's folds (rows of trl_ppo_cat_minibatch_grad_f32; same row fold order, norm rendezvous and Adam
 // arithmetic; optimiser groups [policy without logstd | value]).  The cross-rank variants do not exist for this head.
-extern "C" int trl_ppo_cat_reduce_adam_workspace(int D, int H, int A) {
-  const int ps = trl_ppo_cat_partial_stride(D, H, A);
-  if (ps < 0) return ps;
-  return 16 + 4 * trl_ceil_div(ps, RED_CHUNK);
-}
 extern "C" int trl_ppo_cat_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
                                            int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
                                            float* workspace, void* stream) {
@@ -1739,11 +1640,6 @@ extern "C" int trl_ppo_cat_reduce_adam_net_f32(const float* partial, const doubl
 // The state-dependent-std head's folds (rows of trl_ppo_sd_minibatch_grad_f32; same row fold order, norm rendezvous and Adam
 // arithmetic; optimiser groups [policy with 2A head rows, no logstd | value]).  The `_net` fold of a policy-only launch reads
 // the second scalar block behind THAT launch's n_wg x 8.  The cross-rank variants do not exist for this head.
-extern "C" int trl_ppo_sd_reduce_adam_workspace(int D, int H, int A) {
-  const int ps = trl_ppo_sd_partial_stride(D, H, A);
-  if (ps < 0) return ps;
-  return 16 + 4 * trl_ceil_div(ps, RED_CHUNK);
-}
 extern "C" int trl_ppo_sd_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf,
                                           int D, int H, int A, float* grads, double* info, const trl_adam_t* adam,
                                           float* workspace, void* stream) {

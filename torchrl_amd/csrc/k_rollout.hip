@@ -32,6 +32,7 @@
 #include <algorithm>
 #include "trl_common.h"
 #include "trl_mlp.h"
+#include "trl_head.h"
 #include "trl_philox.h"
 
 #define RO_THREADS 256
@@ -133,25 +134,25 @@ __device__ __forceinline__ void stage_block(const f32x4* __restrict__ src, unsig
 // (torchrl/collector/on_policy.py:90-155 and torchrl/networks/base.py:8-44 are shape-generic).  D = 32 (WIDE, a.D in
 // [18, 32] -- Ant's 27 observations): features 16..31 are a second k group of the first layer and a second row block of
 // the env GEMM instead of the single 17th feature that rides on the VALU.
-// CAT = true: a categorical head (policies.CategoricalDisPolicy) over Ar = 2..8 actions.  The head's A outputs are the
+// HEAD_CAT: a categorical head (policies.CategoricalDisPolicy) over Ar = 2..8 actions.  The head's A outputs are the
 // logits; after the head exchange every lane holds all of its env's logits (they are 8 LDS words away), so the softmax is
 // the per-thread ascending-k loop of cat_act_kernel (k_categorical.hip) -- same max, same prefix sums, no cross-lane
 // step -- against the uniform of (cat_seed, global step, global env index), drawn 16 steps at a time like the Gaussian
 // noise (one (step, env) per thread).  The env takes the one-hot row of the drawn index: lane group g feeds action
 // dims g and 4 + g to the env GEMM as before, now 1.0 where the index matches -- a row selection of env_B, no one-hot row
 // in memory.  The ring's `acts` is (N, 1): the index as a float.  The parameter block has no logstd tail.
-// SD = true: a state-dependent-std Gaussian head (policies.GuassianContPolicy) over Ar = 1..8 action dims.  The head's
+// HEAD_SD: a state-dependent-std Gaussian head (policies.GuassianContPolicy) over Ar = 1..8 action dims.  The head's
 // 2 Ar <= 16 outputs are [mean | raw log_std] -- the whole 16-row head tile, which the other heads compute and half discard:
 // W3 is (2 Ar, H), b3 (2 Ar), no logstd tail; all four lane groups publish their partial head rows (headp [4][16][16]),
 // and after the exchange a lane reads the mean of its action dim o at row o and the raw log_std at row Ar + o.  The clamp
 // to [-20, 2], std = exp(ls) and 1 / std^2 = exp(-2 ls) are then PER STEP (gauss_sd_explore_kernel's forms, k_gauss_sd.hip)
 // instead of once per launch; noise, env step, bookkeeping and the value pass are the Gaussian head's, unchanged.
-template <int D, int H, int A, int ACT, bool NORM, bool RT = false, bool CAT = false, bool SD = false>
+template <int D, int H, int A, int ACT, bool NORM, bool RT = false, int HEAD = HEAD_GAUSS>
 __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
-  using S = RoShape<D, H, A, SD ? 16 : 8>;
-  constexpr bool WIDE = D > 17;
+  using S = RoShape<D, H, A, HEAD == HEAD_SD ? 16 : 8>;
+  constexpr bool WIDE = D > 17, CAT = HEAD == HEAD_CAT, SD = HEAD == HEAD_SD;
   static_assert(!CAT || RT, "the categorical head exists as a runtime-dims instantiation only");
-  static_assert(!SD || (RT && !NORM && !CAT), "the state-dependent-std head exists as a runtime-dims instantiation only");
+  static_assert(!SD || (RT && !NORM), "the state-dependent-std head exists as a runtime-dims instantiation only");
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!(RT && NORM), "the cooperative (normalised) rollout is instantiated for the benchmark shape");
   const int Dr = RT ? a.D : D, Ar = RT ? a.A : A;   // actual dims (row strides of obs / acts, parameter offsets)
@@ -840,14 +841,14 @@ static int rollout_norm_capacity() {
   return cus * per_cu * RO_ENVS;
 }
 
-template <int D, int H, int A, int ACT, bool RT = false, bool CAT = false, bool SD = false>
+template <int D, int H, int A, int ACT, bool RT = false, int HEAD = HEAD_GAUSS>
 static int launch_rollout(const RolloutDev& d, hipStream_t s, hipEvent_t value_wait = nullptr) {
   const int n_wg = trl_ceil_div(d.N, RO_ENVS);
   if constexpr (RT) {
     if (d.norm_state) { trl_set_error("rollout: the normalised rollout is instantiated for the benchmark shape only"); return TRL_EUNSUPPORTED; }
     RolloutDev e = d;
     e.n_ro_wg = n_wg;
-    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true, CAT, SD>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
+    hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false, true, HEAD>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
   } else if (d.norm_state) {
     const int cap = rollout_norm_capacity<D, H, A, ACT>();
     if (d.norm_update && d.N > cap) {
@@ -895,28 +896,18 @@ extern "C" int trl_stage_h2d_f32(const float* host_src, float* dev_dst, int64_t 
   return TRL_OK;
 }
 
-// Shapes the persistent rollout carries without a normaliser: the benchmark shape (compile-time instantiation) and any
-// 64-wide two-layer pair with 2..32 inputs and 1..8 actions (runtime-dims instantiations) -- what the fused update
-// kernels carry (trl_ppo_partial_stride), so such a task is 1 rollout launch + 2 launches per minibatch.
-extern "C" int trl_rollout_supported(int D, int H, int A, int act) {
-  return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
-}
+// Shapes the persistent rollout carries without a normaliser: the benchmark shape (compile-time instantiation, Gaussian
+// head) and any 64-wide two-layer pair with 2..32 inputs and the head's range of actions (HEADS, trl_head.h; runtime-dims
+// instantiations) -- what the fused update kernels carry (trl_ppo_partial_stride), so such a task is 1 rollout launch +
+// 2 launches per minibatch.  A categorical head's outputs are the logits; a state-dependent-std head has 2 A <= 16 rows, one
+// MFMA head tile.  Neither runs with a running observation normaliser.
+extern "C" int trl_rollout_supported(int D, int H, int A, int act) { return head_supported(HEAD_GAUSS, D, H, A, act); }
+extern "C" int trl_rollout_cat_supported(int D, int H, int A, int act) { return head_supported(HEAD_CAT, D, H, A, act); }
+extern "C" int trl_rollout_sd_supported(int D, int H, int A, int act) { return head_supported(HEAD_SD, D, H, A, act); }
 
-// Categorical heads on the persistent rollout: the 64-wide two-layer pairs of the runtime-dims instantiations with 2..8
-// actions (the head's outputs are the logits; no running observation normaliser).
-extern "C" int trl_rollout_cat_supported(int D, int H, int A, int act) {
-  return H == 64 && D >= 2 && D <= 32 && A >= 2 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
-}
-
-// State-dependent-std Gaussian heads on the persistent rollout: the 64-wide two-layer pairs of the runtime-dims
-// instantiations with 1..8 action dims -- a head of 2 A <= 16 rows, one MFMA head tile (no running observation normaliser).
-extern "C" int trl_rollout_sd_supported(int D, int H, int A, int act) {
-  return H == 64 && D >= 2 && D <= 32 && A >= 1 && A <= 8 && (act == TRL_ACT_TANH || act == TRL_ACT_RELU);
-}
-
-// cat: the categorical entry point (trl_rollout_synth_cat_f32) with its draw's key and first global env index
-// sd: the state-dependent-std entry point (trl_rollout_synth_sd_f32); p->A is the number of action dims
-static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t cat_seed, int64_t cat_env0, bool sd = false) {
+// head: which entry point (trl_rollout_synth_f32 / _cat_f32 / _sd_f32); cat_seed, cat_env0: the categorical draw's key and
+// first global env index; p->A is the number of actions (HEAD_CAT) or of action dims
+static int rollout_synth(const trl_rollout_t* p, void* stream, int head, int64_t cat_seed = 0, int64_t cat_env0 = 0) {
   if (!p) { trl_set_error("rollout: null descriptor"); return TRL_EINVAL; }
   TRL_REQUIRE(p->pf_params && p->vf_params && p->env_A && p->env_B, "null network / env pointer");
   TRL_REQUIRE(p->cur_obs && p->t_env && p->cur_step && p->episode_idx && p->ep_return, "null env state pointer");
@@ -928,24 +919,20 @@ static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t
   TRL_REQUIRE(p->top >= 0 && p->top < p->rows, "top outside ring");
   TRL_REQUIRE(no_ring || p->n_steps <= p->rows, "n_steps exceeds ring rows");
   TRL_REQUIRE(p->horizon > 0 && p->max_episode_frames > 0, "horizon / max_episode_frames must be positive");
-  if (cat) {
+  if (head == HEAD_CAT) {
     TRL_REQUIRE(cat_env0 >= 0, "categorical: negative env offset");
     TRL_REQUIRE(!p->noise && !p->noise_flag && !p->stage_n,
                 "categorical: actions are drawn from the device Philox stream only (no host noise block, nothing staged)");
     TRL_REQUIRE(!p->norm_state, "categorical: no running observation normaliser in the persistent rollout");
-    if (!trl_rollout_cat_supported(p->D, p->H, p->A, p->act)) {
-      trl_set_error("rollout: categorical shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
-      return TRL_EUNSUPPORTED;
-    }
   }
-  if (sd) {
+  if (head == HEAD_SD) {
     TRL_REQUIRE(!p->norm_state, "state-dependent std: no running observation normaliser in the persistent rollout");
     TRL_REQUIRE(!p->noise_flag && !p->stage_n,
                 "state-dependent std: the noise block is stream-ordered in front of the launch (no noise gate, nothing staged)");
-    if (!trl_rollout_sd_supported(p->D, p->H, p->A, p->act)) {
-      trl_set_error("rollout: state-dependent-std shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
-      return TRL_EUNSUPPORTED;
-    }
+  }
+  if (head != HEAD_GAUSS && !head_supported(head, p->D, p->H, p->A, p->act)) {
+    trl_set_error("rollout: %s shape D=%d H=%d A=%d act=%d not instantiated", HEADS[head].name, p->D, p->H, p->A, p->act);
+    return TRL_EUNSUPPORTED;
   }
   if (p->n_steps == 0) return TRL_OK;
   RolloutDev d;
@@ -984,47 +971,27 @@ static int rollout_synth(const trl_rollout_t* p, void* stream, bool cat, int64_t
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t vw = (hipEvent_t)p->value_wait_event;
   d.D = p->D; d.A = p->A;
-  if (cat) {
-    if (p->D <= 17) {
-      if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 8, TRL_ACT_TANH, true, true>(d, s, vw);
-      return launch_rollout<17, 64, 8, TRL_ACT_RELU, true, true>(d, s, vw);
-    }
-    if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true, true>(d, s, vw);
-    return launch_rollout<32, 64, 8, TRL_ACT_RELU, true, true>(d, s, vw);
-  }
-  if (sd) {
-    if (p->D <= 17) {
-      if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 8, TRL_ACT_TANH, true, false, true>(d, s, vw);
-      return launch_rollout<17, 64, 8, TRL_ACT_RELU, true, false, true>(d, s, vw);
-    }
-    if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true, false, true>(d, s, vw);
-    return launch_rollout<32, 64, 8, TRL_ACT_RELU, true, false, true>(d, s, vw);
-  }
-  if (p->D == 17 && p->H == 64 && p->A == 6) {
+  if (head == HEAD_GAUSS && p->D == 17 && p->H == 64 && p->A == 6) {               // the benchmark shape, with or without a normaliser
     if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 6, TRL_ACT_TANH>(d, s, vw);
     if (p->act == TRL_ACT_RELU) return launch_rollout<17, 64, 6, TRL_ACT_RELU>(d, s, vw);
   }
-  if (trl_rollout_supported(p->D, p->H, p->A, p->act) && !p->norm_state) {        // runtime-dims instantiations
-    if (p->D <= 17) {
-      if (p->act == TRL_ACT_TANH) return launch_rollout<17, 64, 8, TRL_ACT_TANH, true>(d, s, vw);
-      return launch_rollout<17, 64, 8, TRL_ACT_RELU, true>(d, s, vw);
-    }
-    if (p->act == TRL_ACT_TANH) return launch_rollout<32, 64, 8, TRL_ACT_TANH, true>(d, s, vw);
-    return launch_rollout<32, 64, 8, TRL_ACT_RELU, true>(d, s, vw);
-  }
+  if (head_supported(head, p->D, p->H, p->A, p->act) && !p->norm_state)            // runtime-dims instantiations
+    return with_head(head, [&](auto hd) {
+      return with_tile_act(p->D, p->act, [&](auto tile, auto act) {
+        return launch_rollout<decltype(tile)::value, 64, 8, decltype(act)::value, true, decltype(hd)::value>(d, s, vw);
+      });
+    });
   trl_set_error("rollout: shape D=%d H=%d A=%d act=%d not instantiated", p->D, p->H, p->A, p->act);
   return TRL_EUNSUPPORTED;
 }
 
-extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) { return rollout_synth(p, stream, false, 0, 0); }
+extern "C" int trl_rollout_synth_f32(const trl_rollout_t* p, void* stream) { return rollout_synth(p, stream, HEAD_GAUSS); }
 
 extern "C" int trl_rollout_synth_cat_f32(const trl_rollout_t* p, int64_t noise_seed, int64_t env_offset, void* stream) {
-  return rollout_synth(p, stream, true, noise_seed, env_offset);
+  return rollout_synth(p, stream, HEAD_CAT, noise_seed, env_offset);
 }
 
-extern "C" int trl_rollout_synth_sd_f32(const trl_rollout_t* p, void* stream) {
-  return rollout_synth(p, stream, false, 0, 0, true);
-}
+extern "C" int trl_rollout_synth_sd_f32(const trl_rollout_t* p, void* stream) { return rollout_synth(p, stream, HEAD_SD); }
 
 extern "C" int trl_rollout_norm_workspace(int N) {
   if (N <= 0) { trl_set_error("trl_rollout_norm_workspace: N must be positive"); return TRL_EINVAL; }

@@ -91,6 +91,27 @@ def is_state_std(pf):
     return int(ops.linear_layers(pf)[-1][0].shape[0]) % 2 == 0
 
 
+# The policy heads of the on-policy kernels (csrc/trl_head.h): a diagonal Gaussian with a free `logstd`
+# (GuassianContPolicyBasicBias), a categorical head (CategoricalDisPolicy) and a state-dependent-std Gaussian (GuassianContPolicy)
+HEAD_GAUSS, HEAD_CAT, HEAD_SD = 0, 1, 2
+HEAD_TAG = ("", "cat_", "sd_")                        # in the entry points' names: trl_ppo_<tag>..., trl_rollout_<tag>supported
+HEAD_NAME = ("Gaussian", "categorical", "state-dependent-std")
+
+
+def head_kind(pf, refuse=None):
+    """Which head `pf` has -- the one place the collector, the PPO / A2C engines, TRPO and V-MPO ask.  A network with none of
+    them (a value network, a deterministic or a Q policy): TrlError(`refuse`) when the caller refuses it, None otherwise."""
+    if getattr(pf, "continuous", True) is False and hasattr(pf, "logits"):
+        return HEAD_CAT
+    if is_state_std(pf):
+        return HEAD_SD
+    if hasattr(pf, "logstd"):
+        return HEAD_GAUSS
+    if refuse is not None:
+        raise _C.TrlError(refuse)
+    return None
+
+
 class GuassianContPolicy(networks.Net, GuassianContPolicyBase):
     """State-dependent std (SAC): head emits [mean | log_std] (continuous_policy.py:156-170)."""
 
