@@ -721,6 +721,29 @@ int trl_sac_losses_f32(const float* q1, const float* q2, const float* tq1, const
                        float* dq1, float* dq2, float* dq1n, float* dq2n, double* sums,
                        float* alpha_state, float* alpha_out, float target_entropy, float lr, float beta1,
                        float beta2, float eps, const double* mom_part, int A, double* mom_out, void* stream);
+/* --- SAC / TwinSAC with a value network (torchrl/algo/off_policy/sac.py:74-208, twin_sac.py:82-229) ---
+ * The ONE policy sample of an update and both critic inputs in one launch: (new_a, logp) from head = pf(obs) with eps
+ * (the arithmetic of trl_tanh_gauss_rsample_fwd_f32), x_sa = [obs | acts], x_new = [obs | new_a] (each (B, D + A)).
+ * step_state NULL: eps (B, A) is read.  step_state given: update u (u = step_state[0], the device-resident count of
+ * optimiser steps taken) draws trl_philox_normal_f32's values for (seed, u + 1) inside the launch and leaves them in eps
+ * for the sampler's backward pass.  mom_part (nullable): as in trl_sac_samples_f32, folded by trl_sacv_losses_f32. */
+int trl_sacv_samples_f32(const float* head, float* eps, const double* step_state, int64_t seed, const float* obs,
+                         const float* acts, float* new_a, float* logp, float* x_sa, float* x_new, int B, int D, int A,
+                         int tanh_action, double* mom_part, void* stream);
+/* The losses of that update and their output gradients in one launch; every tensor (B), n the GLOBAL batch size:
+ *   q_target = r + (1 - d) gamma tv   (tv = target_vf(next_obs));   dq_i = 2 (q_i - q_target) / n
+ *   qn = min(q1n, q2n)   (q_in = qf_i([obs | new_a]));   v_target = qn - alpha logp;   dv = 2 (v - v_target) / n
+ *   policy loss mean(alpha logp - qn):  dq1n = -(q1n < q2n ? 1 : q1n == q2n ? .5 : 0) / n, dq2n likewise
+ * q2 / q2n / dq2 / dq2n all NULL: one critic (SAC), qn = q1n and dq1n = -1 / n.
+ * sums (5 doubles): qf1 loss sum, qf2 loss sum (0 with one critic), vf loss sum, sum(alpha logp - qn), sum(rewards).
+ * alpha: device scalar, or the temperature step rides along (alpha_state / alpha_out) exactly as in trl_sac_losses_f32;
+ * mom_part / A / mom_out: the fold of trl_sacv_samples_f32's partial moments, as there.  One workgroup, fixed summation
+ * order.  B <= 0, n < B, a NULL required pointer or q2 without q2n: a negative code, nothing is launched. */
+int trl_sacv_losses_f32(const float* q1, const float* q2, const float* tv, const float* rew, const float* term,
+                        const float* v, const float* q1n, const float* q2n, const float* logp, const float* alpha,
+                        float gamma, int B, int n, float* dq1, float* dq2, float* dv, float* dq1n, float* dq2n,
+                        double* sums, float* alpha_state, float* alpha_out, float target_entropy, float lr, float beta1,
+                        float beta2, float eps, const double* mom_part, int A, double* mom_out, void* stream);
 /* DDPG / TD3 (torchrl/algo/off_policy/ddpg.py:42-110, td3.py:57-154): TD target with Q' = tq1 or
  * min(tq1, tq2) (tq2 NULL: single critic), MSE of one or two critics + output gradients; with qn also the
  * policy loss -mean(Q(s, pi(s))) and dqn = -1/B.  sums (4 doubles): q1 loss sum, q2 loss sum, sum(-qn), sum(r) */

@@ -227,6 +227,10 @@ SIGNATURES = {
     "trl_moments_multi_f64": (C.c_int, [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "trl_sac_losses_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_float, C.c_int] + [C.c_void_p] * 7 + [C.c_float] * 5 +
                            [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "trl_sacv_samples_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 6 + [C.c_int] * 4 +
+                             [C.c_void_p, C.c_void_p]),
+    "trl_sacv_losses_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_float] * 5 +
+                            [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "trl_synth_collect_step_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 6 +
                                    [C.c_float, C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p] +
                                    [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
@@ -1436,6 +1440,51 @@ def sac_losses(q1, q2, tq1, tq2, logp_next, rew, term, q1n, q2n, logp, alpha, ga
                                    dev_ptr(mom_out, torch.float64, "mom_out", allow_none=True),
                                    stream_ptr(q1.device)), "trl_sac_losses_f32")
     return outs
+
+
+def sacv_samples(head, eps, obs, acts, tanh_action=True, philox=None, mom_part=None):
+    """(new_a, logp, x_sa, x_new) of one SAC / TwinSAC update in one launch (include/trl_hip.h trl_sacv_samples_f32).
+    philox = (step_state, seed): the draw is made inside the launch from the device-resident update count and `eps`
+    RECEIVES it.  mom_part (ceil(B / 64), 12) float64: the per-wave partial moments `sacv_losses(..., fold=)` folds."""
+    B, A, D = int(eps.shape[0]), int(eps.shape[1]), int(obs.shape[1])
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=head.device)
+    new_a, logp, x_sa, x_new = f(B, A), f(B), f(B, D + A), f(B, D + A)
+    if mom_part is not None and mom_part.numel() < 12 * ((B + 63) // 64):
+        raise TrlError("sacv_samples: mom_part holds fewer than ceil(B / 64) rows of 12")
+    state, seed = philox if philox is not None else (None, 0)
+    check(lib().trl_sacv_samples_f32(dev_ptr(head, name="head"), dev_ptr(eps, name="eps"),
+                                     dev_ptr(state, torch.float64, "step_state", allow_none=True), int(seed),
+                                     dev_ptr(obs, name="obs"), dev_ptr(acts, name="acts"),
+                                     *[dev_ptr(t, name="out") for t in (new_a, logp, x_sa, x_new)], B, D, A,
+                                     int(bool(tanh_action)), dev_ptr(mom_part, torch.float64, "mom_part", allow_none=True),
+                                     stream_ptr(head.device)), "trl_sacv_samples_f32")
+    return new_a, logp, x_sa, x_new
+
+
+def sacv_losses(q1, q2, tv, rew, term, v, q1n, q2n, logp, alpha, gamma, sums, n=None, alpha_step=None, fold=None):
+    """(dq1, dq2, dv, dq1n, dq2n) and the five loss sums of one SAC / TwinSAC update (include/trl_hip.h
+    trl_sacv_losses_f32); q2 = q2n = None: one critic (dq2, dq2n are then None).  n: the global batch size (default B).
+    alpha_step / fold: as in `sac_losses`."""
+    dev_ptr(q1, name="in0")                                            # (a TrlError, before its size is asked for)
+    B = int(q1.numel())
+    twin = q2 is not None
+    new = lambda: torch.empty((B, 1), dtype=torch.float32, device=q1.device)
+    dq1, dq2, dv, dq1n, dq2n = new(), new() if twin else None, new(), new(), new() if twin else None
+    ent, lr, state, aout = alpha_step if alpha_step is not None else (0.0, 0.0, None, None)
+    part, A, mom_out = fold if fold is not None else (None, 0, None)
+    ins = [(q1, False), (q2, True), (tv, False), (rew, False), (term, False), (v, False), (q1n, False), (q2n, True),
+           (logp, False)]
+    outs = [(dq1, False), (dq2, True), (dv, False), (dq1n, False), (dq2n, True)]
+    check(lib().trl_sacv_losses_f32(*[dev_ptr(t, name="in%d" % i, allow_none=opt) for i, (t, opt) in enumerate(ins)],
+                                    dev_ptr(alpha, name="alpha", allow_none=alpha_step is not None), float(gamma), B,
+                                    B if n is None else int(n),
+                                    *[dev_ptr(t, name="out%d" % i, allow_none=opt) for i, (t, opt) in enumerate(outs)],
+                                    dev_ptr(sums, torch.float64, "sums"), dev_ptr(state, name="alpha_state", allow_none=True),
+                                    dev_ptr(aout, name="alpha_out", allow_none=True), float(ent), float(lr),
+                                    0.9, 0.999, 1e-8, dev_ptr(part, torch.float64, "mom_part", allow_none=True), int(A),
+                                    dev_ptr(mom_out, torch.float64, "mom_out", allow_none=True),
+                                    stream_ptr(q1.device)), "trl_sacv_losses_f32")
+    return dq1, dq2, dv, dq1n, dq2n
 
 
 def slice_add(x1, x2, off, A):

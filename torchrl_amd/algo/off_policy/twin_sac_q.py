@@ -30,7 +30,48 @@ from ._deferred import IndexSlab, StatRing
 from .off_rl_algo import OffRLAlgo
 
 
-class TwinSACQ(OffRLAlgo):
+class _EngineSurface:
+    """What the soft actor-critics offer over their fused engine (`_engine_class`, built on first use): `update` and its
+    deferred forms, `static_batch`, and `log_alpha` read from the engine's device-resident temperature state."""
+    _engine_class = None
+
+    @property
+    def log_alpha(self):
+        return self.engine().alpha_state[0:1]
+
+    def engine(self):
+        if self._engine is None:
+            if self.optimizer_class is not optim.Adam:
+                raise _C.TrlError("the fused SAC step implements torch.optim.Adam only")
+            self._engine = self._engine_class(self)
+        return self._engine
+
+    def static_batch(self):
+        return self.engine().static_batch(self.batch_size)
+
+    def update(self, batch):
+        self.training_update_num += 1
+        return self.engine().update(batch)
+
+    def update_deferred(self, batch):
+        """`update` without its read-back: OffRLAlgo.update_per_epoch enqueues all `opt_times` updates of an epoch and
+        resolves their info dicts with one D2H (`resolve_updates`)."""
+        self.training_update_num += 1
+        return self.engine().enqueue(batch)
+
+    def update_epoch_deferred(self, count):
+        """All `count` {uniform sample -> update} pairs of an epoch as one replayed graph (None when the engine's
+        conditions for it do not hold: the caller then samples and enqueues one by one)."""
+        handles = self.engine().enqueue_epoch(count)
+        if handles is not None:
+            self.training_update_num += count
+        return handles
+
+    def resolve_updates(self, handles):
+        return self.engine().resolve(handles)
+
+
+class TwinSACQ(_EngineSurface, OffRLAlgo):
     def __init__(self, pf, qf1, qf2, plr, qlr, optimizer_class=optim.Adam, policy_std_reg_weight=1e-3,
                  policy_mean_reg_weight=1e-3, reparameterization=True, automatic_entropy_tuning=True,
                  target_entropy=None, noise_mode="host", **kwargs):
@@ -71,58 +112,37 @@ class TwinSACQ(OffRLAlgo):
     def target_networks(self):
         return [(self.qf1, self.target_qf1), (self.qf2, self.target_qf2)]
 
-    @property
-    def log_alpha(self):
-        return self.engine().alpha_state[0:1]
-
-    def engine(self):
-        if self._engine is None:
-            if self.optimizer_class is not optim.Adam:
-                raise _C.TrlError("the fused SAC step implements torch.optim.Adam only")
-            self._engine = _FusedSAC(self)
-        return self._engine
-
-    def static_batch(self):
-        return self.engine().static_batch(self.batch_size)
-
-    def update(self, batch):
-        self.training_update_num += 1
-        return self.engine().update(batch)
-
-    def update_deferred(self, batch):
-        """`update` without its read-back: OffRLAlgo.update_per_epoch enqueues all `opt_times` updates of an epoch and
-        resolves their info dicts with one D2H (`resolve_updates`)."""
-        self.training_update_num += 1
-        return self.engine().enqueue(batch)
-
-    def update_epoch_deferred(self, count):
-        """All `count` {uniform sample -> update} pairs of an epoch as one replayed graph (None when the engine's
-        conditions for it do not hold: the caller then samples and enqueues one by one)."""
-        handles = self.engine().enqueue_epoch(count)
-        if handles is not None:
-            self.training_update_num += count
-        return handles
-
-    def resolve_updates(self, handles):
-        return self.engine().resolve(handles)
-
 
 class _FusedSAC:
+    """The engine of TwinSACQ.  What a soft actor-critic of another make-up changes (sac_v.py: a value network beside
+    the critics) are the two class attributes, `_roles`, `_info` and the loss half of `_sequence`; the flat buffers, the
+    optimiser tail, the graph cache, the statistics ring and the epoch builder are these."""
+    N_SUMS = 4                                                          # doubles the loss launch leaves at the top of the statistics block
+    NOISE = ("eps1", "eps2")                                            # static-batch slots of the N(0,1) draws of one update, in draw order
+
+    def _roles(self, algo):
+        """(trained networks, their optimisers, target networks): the flat parameter buffer is the trained networks back
+        to back, and the targets track the LAST len(targets) of them."""
+        return ((algo.pf, algo.qf1, algo.qf2), (algo.pf_optimizer, algo.qf1_optimizer, algo.qf2_optimizer),
+                (algo.target_qf1, algo.target_qf2))
+
     def __init__(self, algo):
         self.algo = algo
-        nets = (algo.pf, algo.qf1, algo.qf2)
+        nets, self.optimizers, targets = self._roles(algo)
         self.dev = next(algo.pf.parameters()).device
         if self.dev.type != "cuda":
-            raise _C.TrlError("TwinSACQ networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
+            raise _C.TrlError("%s networks live on %s: the HIP path needs a GPU (no CPU path exists)"
+                              % (type(algo).__name__, self.dev))
         self.act = ops.act_code(algo.pf)
         if any(ops.act_code(n) != self.act for n in nets[1:]):
-            raise _C.TrlError("pf / qf1 / qf2 must use the same activation")
+            raise _C.TrlError("the policy and the critics must use the same activation")
         self.layers = [ops.linear_layers(n) for n in nets]
         plists = [[t for wb in ls for t in wb] for ls in self.layers]
         self.sizes = [sum(p.numel() for p in pl) for pl in plists]
-        self.flat = flatten_into(plists[0] + plists[1] + plists[2])       # [pf | qf1 | qf2]; parameters become views
-        self.tlayers = [ops.linear_layers(n) for n in (algo.target_qf1, algo.target_qf2)]
+        self.flat = flatten_into([p for pl in plists for p in pl])      # [pf | qf1 | qf2]; parameters become views
+        self.tlayers = [ops.linear_layers(n) for n in targets]
         self.tflat = flatten_into([t for ls in self.tlayers for wb in ls for t in wb])
+        self.target_off = sum(self.sizes[:len(nets) - len(targets)])    # the targets' sources: flat[target_off:]
         self.grads = torch.zeros_like(self.flat)
         self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         self.gviews, off = [], 0
@@ -134,7 +154,7 @@ class _FusedSAC:
                 views.append((gw, gb))
             self.gviews.append(views)
         off = 0
-        for opt, pl in zip((algo.pf_optimizer, algo.qf1_optimizer, algo.qf2_optimizer), plists):
+        for opt, pl in zip(self.optimizers, plists):
             for p in pl:
                 n = p.numel()
                 opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
@@ -142,12 +162,14 @@ class _FusedSAC:
                 off += n
         self.step_count = 0
         self.alpha_state = torch.zeros(4, device=self.dev)               # log_alpha, exp_avg, exp_avg_sq, step
-        self._raw = torch.zeros(160, dtype=torch.uint8, device=self.dev)  # every logged statistic, one D2H per update
-        self.sums = self._raw[:32].view(torch.float64)
-        self.mom = self._raw[32:128].view(torch.float64).view(3, 4)
-        self.alpha_out = self._raw[128:136].view(torch.float32)         # alpha, alpha_loss
+        # every logged statistic in one block, one D2H per update: loss sums | 3 x 4 moments | alpha, alpha_loss | norms
+        o = self._cuts = [0, 8 * self.N_SUMS, 8 * self.N_SUMS + 96, 8 * self.N_SUMS + 104, 8 * self.N_SUMS + 104 + 4 * len(nets)]
+        self._raw = torch.zeros(max(160, (o[4] + 7) // 8 * 8), dtype=torch.uint8, device=self.dev)
+        self.sums = self._raw[o[0]:o[1]].view(torch.float64)
+        self.mom = self._raw[o[1]:o[2]].view(torch.float64).view(3, 4)
+        self.alpha_out = self._raw[o[2]:o[3]].view(torch.float32)       # alpha, alpha_loss
         self.alpha_out.fill_(1.0)
-        self.norms = self._raw[136:148].view(torch.float32)
+        self.norms = self._raw[o[3]:o[4]].view(torch.float32)
         self.workspace = None
         self.D = int(self.layers[0][0][0].shape[1])
         self.A = int(self.layers[0][-1][0].shape[0]) // 2
@@ -178,7 +200,8 @@ class _FusedSAC:
         if st is None:
             f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.dev)
             st = {"obs": f(B, self.D), "next_obs": f(B, self.D), "acts": f(B, self.A), "rewards": f(B, 1),
-                  "terminals": f(B, 1), "eps1": f(B, self.A), "eps2": f(B, self.A)}
+                  "terminals": f(B, 1)}
+            st.update({k: f(B, self.A) for k in self.NOISE})
             self._static[B] = st
         return st
 
@@ -228,29 +251,45 @@ class _FusedSAC:
         # The first critic layer's input gradient is only needed in its A action columns, summed over the twins and pushed
         # through the sampler's backward: one streaming launch (sac_policy_grad) instead of a (B x 256) . (256 x (D + A)) GEMM
         # per critic and the sampler launch behind it.
-        first, pol_dz = [], None
+        first = []
         dx1, dx2, _, _ = ops.mlp_backward_group([tape_q1n, tape_q2n, tape_q1, tape_q2], [dq1n, dq2n, dq1, dq2],
                                                 grads_list=[None, None, self.gviews[1], self.gviews[2]],
                                                 need_input=[True, True, False, False], plan=plan,
                                                 input_sink=(lambda *a: first.append(a)) if self._pg_fused else None)
+        self._policy_backward(first, (dx1, dx2), head, eps1, new_a, tape_pf, alpha, plan)
+        self._tail(plan, soft, ride, head, logp)
+
+    def _policy_backward(self, first, dxs, head, eps, new_a, tape_pf, alpha, plan):
+        """The policy loss's way from the critics on [obs | new_a] into the policy's weight gradients.  `first`: what
+        mlp_backward_group's input_sink received at the critics' first layer (empty: `dxs`, one or two, are that layer's
+        input gradients already)."""
+        algo, A, D, pf_l = self.algo, self.A, self.D, self.layers[0]
+        B, tanh_action = int(head.shape[0]), bool(algo.pf.tanh_action)
+        pol_dz = None
         if first:
             dys, ys, gate_act, w0 = first[0]
             if _C.sac_policy_grad_ok(dys, w0, A):
                 # ... and the policy's own head backward rides along: dZ2 = (d_head W3) * act'(H2) leaves the same launch
                 # already gated (a 2A-deep input-gradient GEMM launch less; the layer below reads one operand, not two)
                 hl = (pf_l[-1][0], tape_pf.outs[-2], self.act) if len(pf_l) >= 2 and len(tape_pf.outs) >= 2 else None
-                d_head = _C.sac_policy_grad(head, eps1, new_a, dys, ys, gate_act, w0, D, alpha, 1.0 / B,
+                d_head = _C.sac_policy_grad(head, eps, new_a, dys, ys, gate_act, w0, D, alpha, 1.0 / B,
                                             algo.policy_std_reg_weight, algo.policy_mean_reg_weight, tanh_action,
                                             head_layer=hl)
                 if hl is not None:
                     d_head, pol_dz = d_head
             else:                                                         # shapes outside the streaming kernel: the layer GEMM
-                dx1, dx2 = _C.linear_bwd_input_group(dys, ys, gate_act, w0)
+                dxs = _C.linear_bwd_input_group(dys, ys, gate_act, w0)
                 first = []
         if not first:
-            d_head = _C.rsample_bwd_cols(head, eps1, new_a, dx1, dx2, D, alpha, 1.0 / B, algo.policy_std_reg_weight,
+            dx1, dx2 = dxs if len(dxs) == 2 else (dxs[0], None)
+            d_head = _C.rsample_bwd_cols(head, eps, new_a, dx1, dx2, D, alpha, 1.0 / B, algo.policy_std_reg_weight,
                                          algo.policy_mean_reg_weight, tanh_action)    # d_act = (dx1 + dx2)[:, D:]
         ops.mlp_backward(tape_pf, d_head, grads=self.gviews[0], plan=plan, head_dx=pol_dz)
+
+    def _tail(self, plan, soft, ride, head, logp):
+        """The second half of an update, behind the backward passes that filled `plan`: fold, clip and Adam per network,
+        the target update, and the filing of the logged statistics."""
+        algo, dev, A = self.algo, self.dev, self.A
         # one process, soft target updates: the folds, the clip, the Adam steps, the Polyak step and the filing of the
         # statistics are ONE launch (FoldPlan.run_fused); otherwise fold here, (all-reduce,) clip + Adam (+ Polyak) below
         fused_tail = soft and self._fused_tail and dist.world_size() == 1 and plan.tiles(self.grads)
@@ -260,9 +299,9 @@ class _FusedSAC:
         a = _C.AdamArgs()
         a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
                                                       self.m.data_ptr(), self.v.data_ptr())
-        a.n_groups = 3
-        for k in range(3):
-            a.group_sizes[k] = self.sizes[k]
+        a.n_groups = len(self.sizes)
+        for k, size in enumerate(self.sizes):
+            a.group_sizes[k] = size
         for k, lr in enumerate(self._lrs()):
             a.group_lr[k] = lr
         a.max_norm = float(algo.grad_clip) if algo.grad_clip else 0.0
@@ -274,10 +313,10 @@ class _FusedSAC:
         if fused_tail:
             if self._tail_ws is None:
                 self._tail_ws = _C.fold_clip_adam_polyak_workspace(dev)
-            plan.run_fused(a, self.grads, self.tflat, self.sizes[0], algo.tau, self._tail_ws,
+            plan.run_fused(a, self.grads, self.tflat, self.target_off, algo.tau, self._tail_ws,
                            file=(self._raw, self._ring.t) if ride else None)
         elif soft:                                                       # Adam, then Polyak (which also advances the step state)
-            _C.clip_adam_polyak(a, self.tflat, self.flat[self.sizes[0]:], algo.tau, dev,
+            _C.clip_adam_polyak(a, self.tflat, self.flat[self.target_off:], algo.tau, dev,
                                 file=(self._raw, self._ring.t) if ride else None)
         else:
             _C.clip_adam(a, dev)
@@ -299,12 +338,13 @@ class _FusedSAC:
 
     def _inline_noise(self):
         """Device Philox noise on a single rank whose every update so far drew its noise on the device: draw u's counters
-        (2u + 1, 2u + 2) follow from the optimiser step count, so the sampling launch makes them itself."""
-        return self.algo.noise_mode == "device" and dist.world_size() == 1 and self.noise_ctr == 2 * self.step_count
+        (2u + 1, 2u + 2 with two draws per update) follow from the optimiser step count, so the sampling launch makes them
+        itself."""
+        return self.algo.noise_mode == "device" and dist.world_size() == 1 and \
+            self.noise_ctr == len(self.NOISE) * self.step_count
 
     def _lrs(self):
-        algo = self.algo
-        return tuple(float(o.param_groups[0]['lr']) for o in (algo.pf_optimizer, algo.qf1_optimizer, algo.qf2_optimizer))
+        return tuple(float(o.param_groups[0]['lr']) for o in self.optimizers)
 
     def _run(self, st, soft):
         """Eager on the first visit of a configuration, captured into a HIP graph on the second, replayed
@@ -341,7 +381,7 @@ class _FusedSAC:
         n_env = int(algo.replay_buffer.env_nums) if getattr(algo, "replay_buffer", None) is not None else B
         rows = B // n_env if B % n_env == 0 else 1                       # batch = sampled time rows x this rank's envs
         inline = self._inline_noise()
-        for k in ("eps1", "eps2"):                                       # distribution.py:67-70: two draws, in this order
+        for k in self.NOISE:                                             # distribution.py:67-70: the draws, in this order
             if inline:
                 continue
             if algo.noise_mode == "host":
@@ -356,10 +396,10 @@ class _FusedSAC:
         self._ring.make_room(1)
         self._run(st, bool(algo.use_soft_update))
         if inline:
-            self.noise_ctr += 2                                          # the two draws the sampling launch made
+            self.noise_ctr += len(self.NOISE)                            # the draws the sampling launch made
         self.step_count += 1
         if not algo.use_soft_update and algo.training_update_num % algo.target_hard_update_period == 0:
-            _C.polyak(self.tflat, self.flat[self.sizes[0]:], 1.0)
+            _C.polyak(self.tflat, self.flat[self.target_off:], 1.0)
         return self._handles(1, B)[0]
 
     def _handles(self, count, B):
@@ -407,31 +447,37 @@ class _FusedSAC:
             graph, _ = _C.capture_graph(lambda: launches(count))
             self._graphs[key] = graph
             graph.replay()
-        self.noise_ctr += 2 * count
+        self.noise_ctr += len(self.NOISE) * count
         self.step_count += count
         return self._handles(count, B)
 
     def resolve(self, handles):
         """Info dicts of enqueued updates, in order: one D2H per ring (normally one per call), the only host sync."""
         raw = self._ring.read([(ref, row) for ref, row, _ in handles])   # (n, 160) bytes -> nested lists of Python floats:
-        parts = (raw[:, :32].view(np.float64).tolist(), raw[:, 32:128].view(np.float64).tolist(),   # one conversion, not
-                 raw[:, 128:136].view(np.float32).tolist(), raw[:, 136:148].view(np.float32).tolist())  # views per update
+        o = self._cuts
+        parts = (raw[:, o[0]:o[1]].view(np.float64).tolist(), raw[:, o[1]:o[2]].view(np.float64).tolist(),   # one conversion, not
+                 raw[:, o[2]:o[3]].view(np.float32).tolist(), raw[:, o[3]:o[4]].view(np.float32).tolist())   # views per update
         return [self._info(part, h[2]) for part, h in zip(zip(*parts), handles)]
 
     def update(self, batch):
         return self.resolve([self.enqueue(batch)])[0]
 
+    def _reg_terms(self, mom, Bg):
+        """w_std mean(log_std^2) + w_mean mean(mean^2) of the policy loss, from the logged moments over Bg rows."""
+        algo, A = self.algo, self.A
+        w_std, w_mean = algo.policy_std_reg_weight, algo.policy_mean_reg_weight
+        if not (w_std or w_mean):
+            return 0.0
+        n = Bg * A - 1
+        ms_ls = mom[1] ** 2 * n / (n + 1) + mom[0] ** 2                               # E[x^2] from mean / unbiased std
+        ms_mu = mom[9] ** 2 * n / (n + 1) + mom[8] ** 2
+        return w_std * ms_ls + w_mean * ms_mu
+
     def _info(self, raw, B):
         algo, A = self.algo, self.A
         Bg = B * dist.world_size()                                       # the sums were reduced over all ranks
         sums, mom, aout, norms = raw                                     # 4 sums, 3 x (mean, std, max, min), (alpha, loss), 3 norms
-        w_std, w_mean = algo.policy_std_reg_weight, algo.policy_mean_reg_weight
-        reg = 0.0
-        if w_std or w_mean:
-            n = Bg * A - 1
-            ms_ls = mom[1] ** 2 * n / (n + 1) + mom[0] ** 2                           # E[x^2] from mean / unbiased std
-            ms_mu = mom[9] ** 2 * n / (n + 1) + mom[8] ** 2
-            reg = w_std * ms_ls + w_mean * ms_mu
+        reg = self._reg_terms(mom, Bg)
         info = {'Reward_Mean': sums[3] / Bg}
         if algo.automatic_entropy_tuning:
             info["Alpha"], info["Alpha_loss"] = aout
@@ -443,3 +489,6 @@ class _FusedSAC:
         for k, key in enumerate(("log_std", "log_probs", "mean")):
             info[key + '/mean'], info[key + '/std'], info[key + '/max'], info[key + '/min'] = mom[4 * k:4 * k + 4]
         return info
+
+
+TwinSACQ._engine_class = _FusedSAC

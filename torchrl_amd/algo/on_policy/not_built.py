@@ -10,7 +10,7 @@ class _NotBuilt:
 
     def __init__(self, *args, **kwargs):
         raise _C.TrlError("%s is not built in torchrl_amd (reference: %s): the HIP path covers PPO, A2C, TRPO, VMPO, TwinSACQ, "
-                          "DQN, QRDQN, DDPG and TD3" % (type(self).__name__, self._what))
+                          "SAC, TwinSAC, DQN, QRDQN, DDPG and TD3" % (type(self).__name__, self._what))
 
 
 class Reinforce(_NotBuilt):

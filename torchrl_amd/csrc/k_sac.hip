@@ -114,6 +114,30 @@ __device__ __forceinline__ void philox_noise_row(int64_t seed, int64_t ctr, int6
   }
 }
 
+// The logged moments of the policy head on obs -- clamped log_std, mean -- and of log_prob (twin_sac_q.py:190-207) as
+// per-wave partials {sum, sum of squares, max, -min} x {log_std, log_prob, mean}: row b >> 6 of mom_part (12 doubles),
+// written by a WHOLE wave (rows past the batch contribute nothing); the loss launches fold them (the separate
+// trl_moments_multi_f64 launch re-read head and logp for this).
+__device__ __forceinline__ void policy_moment_partials(const float* __restrict__ head, float lp0, int b, int A, bool live,
+                                                       double* __restrict__ mom_part) {
+  double ps[3] = {0, 0, 0}, pq[3] = {0, 0, 0}, pm[3] = {-INFINITY, -INFINITY, -INFINITY}, pn[3] = {-INFINITY, -INFINITY, -INFINITY};
+  if (live) {
+    for (int k = 0; k < A; ++k) {
+      const double mu = (double)head[(size_t)b * 2 * A + k];
+      const double ls = (double)fminf(fmaxf(head[(size_t)b * 2 * A + A + k], -20.0f), 2.0f);
+      ps[0] += ls; pq[0] += ls * ls; pm[0] = fmax(pm[0], ls); pn[0] = fmax(pn[0], -ls);
+      ps[2] += mu; pq[2] += mu * mu; pm[2] = fmax(pm[2], mu); pn[2] = fmax(pn[2], -mu);
+    }
+    ps[1] = (double)lp0; pq[1] = (double)lp0 * lp0; pm[1] = (double)lp0; pn[1] = -(double)lp0;
+  }
+  double* row = mom_part + (size_t)(b >> 6) * 12;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double a0 = wave_sum(ps[j]), a1 = wave_sum(pq[j]), a2 = wave_max(pm[j]), a3 = wave_max(pn[j]);
+    if ((threadIdx.x & 63) == 0) { row[4 * j] = a0; row[4 * j + 1] = a1; row[4 * j + 2] = a2; row[4 * j + 3] = a3; }
+  }
+}
+
 // Both policy samples of one SAC update and the three critic inputs in one launch (twin_sac_q.py:93-106, :125-131,
 // :146-151): new_a / logp from head(obs) with eps1, next_a / next_logp from head(next_obs) with eps2, and
 // x_sa = [obs | acts], x_next = [next_obs | next_a], x_new = [obs | new_a].  One thread per batch row -- the whole
@@ -168,27 +192,7 @@ __global__ __launch_bounds__(SAC_THREADS) void sac_samples_kernel(const float* _
       for (int k = 0; k < A; ++k) x_next[(size_t)b * F + D + k] = xa[k];
     }
   }
-  if (stats) {
-    // the logged moments of the policy head on obs -- clamped log_std, mean -- and of log_prob (twin_sac_q.py:190-207) as
-    // per-wave partials {sum, sum of squares, max, -min} x {log_std, log_prob, mean}: row b >> 6 of mom_part (12 doubles);
-    // trl_sac_losses_f32 folds them (the separate trl_moments_multi_f64 launch re-read head and logp for this)
-    double ps[3] = {0, 0, 0}, pq[3] = {0, 0, 0}, pm[3] = {-INFINITY, -INFINITY, -INFINITY}, pn[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if (live) {
-      for (int k = 0; k < A; ++k) {
-        const double mu = (double)head[(size_t)b * 2 * A + k];
-        const double ls = (double)fminf(fmaxf(head[(size_t)b * 2 * A + A + k], -20.0f), 2.0f);
-        ps[0] += ls; pq[0] += ls * ls; pm[0] = fmax(pm[0], ls); pn[0] = fmax(pn[0], -ls);
-        ps[2] += mu; pq[2] += mu * mu; pm[2] = fmax(pm[2], mu); pn[2] = fmax(pn[2], -mu);
-      }
-      ps[1] = (double)lp0; pq[1] = (double)lp0 * lp0; pm[1] = (double)lp0; pn[1] = -(double)lp0;
-    }
-    double* row = mom_part + (size_t)(b >> 6) * 12;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double a0 = wave_sum(ps[j]), a1 = wave_sum(pq[j]), a2 = wave_max(pm[j]), a3 = wave_max(pn[j]);
-      if ((threadIdx.x & 63) == 0) { row[4 * j] = a0; row[4 * j + 1] = a1; row[4 * j + 2] = a2; row[4 * j + 3] = a3; }
-    }
-  }
+  if (stats) policy_moment_partials(head, lp0, b, A, live, mom_part);
 }
 static int sac_samples_impl(const float* head, const float* head2, const float* eps1, const float* eps2,
                             const float* obs, const float* acts, const float* next_obs, float* new_a, float* logp,
@@ -589,6 +593,38 @@ __device__ __forceinline__ float alpha_adam_step(double logp_sum, int B, const L
   x.alpha_out[0] = alpha;
   return alpha;
 }
+// The fold of the sampling launch's per-wave partial moments, by the LAST wave of a one-workgroup loss kernel:
+// `moment_fold_request` at kernel entry (the first 64 partial rows, one per lane, travel with the kernel's first loads),
+// `moment_fold_finish` at its end ({mean, unbiased std, max, min} x {log_std, log_prob, mean} -> x.mom_out).
+__device__ __forceinline__ void moment_fold_request(const LossExtras& x, double (&mp)[3][4]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { mp[j][0] = 0; mp[j][1] = 0; mp[j][2] = -INFINITY; mp[j][3] = -INFINITY; }
+  if (x.mom_part && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1 && (int)(threadIdx.x & 63) < x.parts) {
+    const double* row = x.mom_part + (size_t)(threadIdx.x & 63) * 12;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { mp[j][0] = row[4 * j]; mp[j][1] = row[4 * j + 1]; mp[j][2] = row[4 * j + 2]; mp[j][3] = row[4 * j + 3]; }
+  }
+}
+__device__ __forceinline__ void moment_fold_finish(const LossExtras& x, const double (&mp)[3][4], int B) {
+  if (x.mom_part && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1) {
+    const int lane = threadIdx.x & 63;
+    for (int j = 0; j < 3; ++j) {
+      double a = mp[j][0], c = mp[j][1], mx = mp[j][2], nmn = mp[j][3];
+      for (int p = lane + 64; p < x.parts; p += 64) {
+        const double* row = x.mom_part + (size_t)p * 12 + 4 * j;
+        a += row[0]; c += row[1]; mx = fmax(mx, row[2]); nmn = fmax(nmn, row[3]);
+      }
+      a = wave_sum(a); c = wave_sum(c); mx = wave_max(mx); nmn = wave_max(nmn);
+      if (lane == 0) {
+        const double cnt = (double)B * (j == 1 ? 1 : x.A), mean = a / cnt;
+        double* o = x.mom_out + 4 * j;
+        o[0] = mean;
+        o[1] = cnt > 1 ? sqrt(fmax((c - a * mean) / (cnt - 1), 0.0)) : NAN;
+        o[2] = mx; o[3] = -nmn;
+      }
+    }
+  }
+}
 __global__ __launch_bounds__(SAC_WIDE) void sac_losses_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                                                                  const float* __restrict__ tq1, const float* __restrict__ tq2,
                                                                  const float* __restrict__ logp_next,
@@ -617,13 +653,8 @@ __global__ __launch_bounds__(SAC_WIDE) void sac_losses_kernel(const float* __res
     }
   };
   request(threadIdx.x);
-  // the moment fold's first 64 partial rows (one per lane of the last wave) travel with the first group of loads
-  double mp[3][4] = {{0, 0, -INFINITY, -INFINITY}, {0, 0, -INFINITY, -INFINITY}, {0, 0, -INFINITY, -INFINITY}};
-  if (x.mom_part && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1 && (int)(threadIdx.x & 63) < x.parts) {
-    const double* row = x.mom_part + (size_t)(threadIdx.x & 63) * 12;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { mp[j][0] = row[4 * j]; mp[j][1] = row[4 * j + 1]; mp[j][2] = row[4 * j + 2]; mp[j][3] = row[4 * j + 3]; }
-  }
+  double mp[3][4];                                                     // (the moment fold's first rows: with the first loads)
+  moment_fold_request(x, mp);
   float alpha;
   if (x.alpha_state) {                                                 // (one workgroup: the launcher's contract)
     double s = 0.0;
@@ -668,24 +699,7 @@ __global__ __launch_bounds__(SAC_WIDE) void sac_losses_kernel(const float* __res
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += red4[w][threadIdx.x];
     sums[threadIdx.x] = r;
   }
-  if (x.mom_part && (threadIdx.x >> 6) == (blockDim.x >> 6) - 1) {     // the last wave folds the partial moments (values it
-    const int lane = threadIdx.x & 63;                                 // requested at kernel entry: mp[])
-    for (int j = 0; j < 3; ++j) {
-      double a = mp[j][0], c = mp[j][1], mx = mp[j][2], nmn = mp[j][3];
-      for (int p = lane + 64; p < x.parts; p += 64) {
-        const double* row = x.mom_part + (size_t)p * 12 + 4 * j;
-        a += row[0]; c += row[1]; mx = fmax(mx, row[2]); nmn = fmax(nmn, row[3]);
-      }
-      a = wave_sum(a); c = wave_sum(c); mx = wave_max(mx); nmn = wave_max(nmn);
-      if (lane == 0) {
-        const double cnt = (double)B * (j == 1 ? 1 : x.A), mean = a / cnt;
-        double* o = x.mom_out + 4 * j;
-        o[0] = mean;
-        o[1] = cnt > 1 ? sqrt(fmax((c - a * mean) / (cnt - 1), 0.0)) : NAN;
-        o[2] = mx; o[3] = -nmn;
-      }
-    }
-  }
+  moment_fold_finish(x, mp, B);
 }
 extern "C" int trl_sac_losses_f32(const float* q1, const float* q2, const float* tq1, const float* tq2,
                                        const float* logp_next, const float* rew, const float* term, const float* q1n,
@@ -702,6 +716,172 @@ extern "C" int trl_sac_losses_f32(const float* q1, const float* q2, const float*
   LossExtras x = {alpha_state, alpha_out, target_entropy, lr, beta1, beta2, eps, mom_part, trl_ceil_div(B, 64), A, mom_out};
   hipLaunchKernelGGL(sac_losses_kernel, dim3(1), dim3(SAC_WIDE), 0, (hipStream_t)stream, q1, q2, tq1, tq2, logp_next, rew,
                      term, q1n, q2n, logp, alpha, gamma, B, dq1, dq2, dq1n, dq2n, sums, x);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
+}
+
+// ---------------------------------------------------------------- SAC / TwinSAC with a value network (sac.py, twin_sac.py)
+// The one policy sample of an update and both critic inputs in one launch (sac.py:92-101, :128; twin_sac.py:99-109,
+// :138-140): new_a / logp from head(obs) with eps (rsample_row: the arithmetic of rsample_fwd_kernel), x_sa = [obs | acts],
+// x_new = [obs | new_a].  One thread per batch row, one wave per workgroup.  step_state given: update u (the
+// device-resident count of optimiser steps taken) draws trl_philox_normal_f32's values for (seed, u + 1) in place and
+// leaves them in eps for the sampler's backward pass.  mom_part: the per-wave partial moments, as in sac_samples_kernel.
+__global__ __launch_bounds__(64) void sacv_samples_kernel(const float* __restrict__ head, float* __restrict__ eps,
+                                                          const float* __restrict__ obs, const float* __restrict__ acts,
+                                                          float* __restrict__ new_a, float* __restrict__ logp,
+                                                          float* __restrict__ x_sa, float* __restrict__ x_new, int B, int D,
+                                                          int A, int tanh_action, const double* __restrict__ step_state,
+                                                          int64_t seed, double* __restrict__ mom_part) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  const bool live = b < B;
+  if (!live && !mom_part) return;                                     // (a statistics wave stays whole for its reductions)
+  float lp0 = 0.0f;
+  if (live) {
+    const int F = D + A;
+    float e[8];
+    if (step_state) {
+      philox_noise_row(seed, (int64_t)step_state[0] + 1, b, A, e);
+      for (int k = 0; k < A; ++k) eps[(size_t)b * A + k] = e[k];
+    } else {
+      for (int k = 0; k < A; ++k) e[k] = eps[(size_t)b * A + k];
+    }
+    float* na = new_a + (size_t)b * A;
+    lp0 = rsample_row(head + (size_t)b * 2 * A, e, na, A, tanh_action);
+    logp[b] = lp0;
+    for (int k = 0; k < D; ++k) {
+      const float o = obs[(size_t)b * D + k];
+      x_sa[(size_t)b * F + k] = o; x_new[(size_t)b * F + k] = o;
+    }
+    for (int k = 0; k < A; ++k) {
+      x_sa[(size_t)b * F + D + k] = acts[(size_t)b * A + k];
+      x_new[(size_t)b * F + D + k] = na[k];
+    }
+  }
+  if (mom_part) policy_moment_partials(head, lp0, b, A, live, mom_part);
+}
+extern "C" int trl_sacv_samples_f32(const float* head, float* eps, const double* step_state, int64_t seed, const float* obs,
+                                    const float* acts, float* new_a, float* logp, float* x_sa, float* x_new, int B, int D,
+                                    int A, int tanh_action, double* mom_part, void* stream) {
+  TRL_REQUIRE(B >= 0 && A > 0 && A <= 8 && D > 0, "bad sizes (A <= 8)");
+  if (B == 0) return TRL_OK;
+  TRL_REQUIRE(head && eps && obs && acts, "null input");
+  TRL_REQUIRE(new_a && logp && x_sa && x_new, "null output");
+  hipLaunchKernelGGL(sacv_samples_kernel, dim3(trl_ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, head, eps, obs, acts,
+                     new_a, logp, x_sa, x_new, B, D, A, tanh_action, step_state, seed, mom_part);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
+}
+
+// TD target from the target V, the critic regression(s), the V regression and the policy-loss gradients (sac.py:117-144,
+// twin_sac.py:125-156); q2 / q2n / dq2 / dq2n NULL: the single-critic SAC.  n: the global batch size (B on one rank).
+//   q_target = r + (1 - d) gamma tv                    qf_i loss = mean((q_i - q_target)^2), dq_i = 2 (q_i - q_target) / n
+//   qn = min(q1n, q2n) (or q1n)     v_target = qn - alpha logp       vf loss = mean((v - v_target)^2), dv = 2 (v - v_target) / n
+//   policy_loss = mean(alpha logp - qn); torch.min ties split the gradient: dq1n = -(q1n < q2n ? 1 : q1n == q2n ? .5 : 0) / n
+// sums (double[5]): qf1 loss sum, qf2 loss sum (0 without q2), vf loss sum, sum(alpha logp - qn), sum rewards.
+// The two riders of sac_losses_kernel (temperature step at the top, fold of the partial moments by the last wave) are the
+// same code; one workgroup, partial sums folded in a fixed order.
+__global__ __launch_bounds__(SAC_WIDE) void sacv_losses_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
+                                                               const float* __restrict__ tv, const float* __restrict__ rew,
+                                                               const float* __restrict__ term, const float* __restrict__ v,
+                                                               const float* __restrict__ q1n, const float* __restrict__ q2n,
+                                                               const float* __restrict__ logp, const float* __restrict__ alpha_ptr,
+                                                               float gamma, int B, int n, float* __restrict__ dq1,
+                                                               float* __restrict__ dq2, float* __restrict__ dv,
+                                                               float* __restrict__ dq1n, float* __restrict__ dq2n,
+                                                               double* __restrict__ sums, LossExtras x) {
+  __shared__ double smem[SAC_WIDE / 64];
+  __shared__ float s_alpha;
+  const bool twin = q2 != nullptr;
+  // rows four per thread (b, b + 1024, ...), the first group requested BEFORE the temperature step, as in sac_losses_kernel
+  constexpr int R = 4;
+  float in[R][9];
+  auto request = [&](int b0) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int b = b0 + j * SAC_WIDE;
+      if (b < B) {
+        in[j][0] = tv[b]; in[j][1] = rew[b]; in[j][2] = term[b]; in[j][3] = q1[b]; in[j][4] = v[b]; in[j][5] = q1n[b];
+        in[j][6] = logp[b];
+        if (twin) { in[j][7] = q2[b]; in[j][8] = q2n[b]; }
+      }
+    }
+  };
+  request(threadIdx.x);
+  double mp[3][4];
+  moment_fold_request(x, mp);
+  float alpha;
+  if (x.alpha_state) {                                                 // (one workgroup: the launcher's contract)
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) if ((int)threadIdx.x + j * SAC_WIDE < B) s += (double)in[j][6];
+    for (int b = threadIdx.x + R * SAC_WIDE; b < B; b += SAC_WIDE) s += (double)logp[b];
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) s_alpha = alpha_adam_step(s, B, x);
+    __syncthreads();
+    alpha = s_alpha;
+  } else {
+    alpha = *alpha_ptr;
+  }
+  const float nf = (float)n, inv_n = 1.0f / nf;
+  double s1 = 0, s2 = 0, sv = 0, sp = 0, sr = 0;
+  for (int b0 = threadIdx.x; b0 < B; b0 += R * SAC_WIDE) {
+    if (b0 != (int)threadIdx.x) request(b0);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int b = b0 + j * SAC_WIDE;
+      if (b >= B) break;
+      const float qt = in[j][1] + (1.0f - in[j][2]) * gamma * in[j][0];
+      const float e1 = in[j][3] - qt;
+      dq1[b] = 2.0f * e1 / nf;
+      s1 += (double)e1 * e1;
+      float qn = in[j][5];
+      if (twin) {
+        const float e2 = in[j][7] - qt;
+        dq2[b] = 2.0f * e2 / nf;
+        s2 += (double)e2 * e2;
+        const float a = in[j][5], c = in[j][8];
+        dq1n[b] = -(a < c ? 1.0f : (a == c ? 0.5f : 0.0f)) * inv_n;
+        dq2n[b] = -(c < a ? 1.0f : (a == c ? 0.5f : 0.0f)) * inv_n;
+        qn = fminf(a, c);
+      } else {
+        dq1n[b] = -inv_n;
+      }
+      const float al = alpha * in[j][6];
+      const float ev = in[j][4] - (qn - al);
+      dv[b] = 2.0f * ev / nf;
+      sv += (double)ev * ev; sp += (double)(al - qn); sr += (double)in[j][1];
+    }
+  }
+  // the five sums: one exchange (wave sums side by side, one barrier, threads 0..4 add the waves in block_sum's order)
+  __shared__ double red5[SAC_WIDE / 64][5];
+  {
+    const double w1 = wave_sum(s1), w2 = wave_sum(s2), wv = wave_sum(sv), wp = wave_sum(sp), wr = wave_sum(sr);
+    if ((threadIdx.x & 63) == 0) { double* r = red5[threadIdx.x >> 6]; r[0] = w1; r[1] = w2; r[2] = wv; r[3] = wp; r[4] = wr; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    double r = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += red5[w][threadIdx.x];
+    sums[threadIdx.x] = r;
+  }
+  moment_fold_finish(x, mp, B);
+}
+extern "C" int trl_sacv_losses_f32(const float* q1, const float* q2, const float* tv, const float* rew, const float* term,
+                                   const float* v, const float* q1n, const float* q2n, const float* logp, const float* alpha,
+                                   float gamma, int B, int n, float* dq1, float* dq2, float* dv, float* dq1n, float* dq2n,
+                                   double* sums, float* alpha_state, float* alpha_out, float target_entropy, float lr,
+                                   float beta1, float beta2, float eps, const double* mom_part, int A, double* mom_out,
+                                   void* stream) {
+  TRL_REQUIRE(B > 0 && n >= B, "empty batch, or a global batch smaller than the local one");
+  TRL_REQUIRE(q1 && tv && rew && term && v && q1n && logp, "null input");
+  TRL_REQUIRE(dq1 && dv && dq1n && sums, "null output");
+  TRL_REQUIRE((q2 != nullptr) == (q2n != nullptr), "q2 and q2n come together (both NULL: one critic)");
+  TRL_REQUIRE((q2 != nullptr) == (dq2 != nullptr) && (q2 != nullptr) == (dq2n != nullptr), "dq2 / dq2n go with q2 / q2n");
+  TRL_REQUIRE((alpha_state && alpha_out) || (!alpha_state && alpha), "alpha: a step state + output, or a value");
+  TRL_REQUIRE(!mom_part || (mom_out && A > 0), "moments fold: null output / bad A");
+  LossExtras x = {alpha_state, alpha_out, target_entropy, lr, beta1, beta2, eps, mom_part, trl_ceil_div(B, 64), A, mom_out};
+  hipLaunchKernelGGL(sacv_losses_kernel, dim3(1), dim3(SAC_WIDE), 0, (hipStream_t)stream, q1, q2, tv, rew, term, v, q1n, q2n,
+                     logp, alpha, gamma, B, n, dq1, dq2, dv, dq1n, dq2n, sums, x);
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
