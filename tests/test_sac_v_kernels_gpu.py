@@ -28,7 +28,7 @@ import _sac_v_ref as R                                                        # 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 U = R.U
-LOSS_B = (1, 64, 65, 1023, 1025, 4096)
+LOSS_B = (1, 64, 65, 1023, 1025, 4096, 4097, 8200)
 KEYS = ("q1", "q2", "tv", "rew", "term", "v", "q1n", "q2n", "logp")
 
 

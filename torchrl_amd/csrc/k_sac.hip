@@ -1038,45 +1038,45 @@ extern "C" int trl_polyak_f32(float* target, const float* source, int64_t n, flo
 __device__ __forceinline__ void moments_block(const float* __restrict__ x, int64_t n, int ld, int off,
                                               int width, float lo, float hi_, double* __restrict__ out,
                                               double* __restrict__ out2 = nullptr) {
-  // x viewed as rows of `ld` floats; statistics over columns [off, off+width) of every row.  One workgroup of 16
-  // waves (fixed summation order); each thread walks (row, column) incrementally -- no division in the loop.
-  __shared__ double smem[4][MOM_THREADS / 64];
-  double s = 0, sq = 0, mx = -INFINITY, nmn = -INFINITY;
+  // x viewed as rows of `ld` floats; statistics over columns [off, off+width) of every row.  One workgroup of 16 waves.
+  // The sums are added in the order of the loss launches' moment fold (policy_moment_partials + moment_fold_finish), so
+  // that the two give the same bits: a thread adds the columns of ONE row in turn, a wave adds 64 consecutive rows by
+  // butterfly (one "partial row" of the fold), partial p goes to slot p % 64 in ascending p, and one wave adds the 64
+  // slots by butterfly.  Wave w takes partials w, w + 16, ...: slots w, w + 16, w + 32, w + 48 are its own.
+  __shared__ double smem[4][64];
+  double mx = -INFINITY, nmn = -INFINITY;
   const int64_t rows = n / ld;
-  // four independent element streams per thread (elements tid + j * 1024, then strides of 4096): their loads are in flight
-  // together -- one stream per thread was a chain of dependent round trips, 24 of them at B = 4096 x 6 columns
-  int64_t r[4];
-  int c[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int e = threadIdx.x + j * MOM_THREADS;
-    r[j] = e / width;
-    c[j] = e - (int)r[j] * width;
-  }
-  const int dr = 4 * MOM_THREADS / width, dc = 4 * MOM_THREADS - dr * width;
-  while (r[0] < rows) {                                                // (stream 0 is the one that runs out last)
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = r[j] < rows ? x[r[j] * ld + off + c[j]] : 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (r[j] < rows) {
-        const double d = (double)fminf(fmaxf(v[j], lo), hi_);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double as[4] = {0, 0, 0, 0}, aq[4] = {0, 0, 0, 0};
+  const int64_t parts = (rows + 63) / 64;
+  for (int64_t p = wave; p < parts; p += MOM_THREADS / 64) {           // (wave-uniform)
+    const int64_t r = p * 64 + lane;
+    double s = 0, sq = 0;
+    if (r < rows) {
+      const float* __restrict__ row = x + r * ld + off;
+#pragma unroll 4
+      for (int k = 0; k < width; ++k) {
+        const double d = (double)fminf(fmaxf(row[k], lo), hi_);
         s += d; sq += d * d; mx = fmax(mx, d); nmn = fmax(nmn, -d);
       }
-      r[j] += dr; c[j] += dc;
-      if (c[j] >= width) { c[j] -= width; ++r[j]; }
     }
+    s = wave_sum(s); sq = wave_sum(sq);
+    const int slot = (int)((p >> 4) & 3);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (slot == j) { as[j] += s; aq[j] += sq; }
   }
-  s = wave_sum(s); sq = wave_sum(sq); mx = wave_max(mx); nmn = wave_max(nmn);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { smem[0][wave] = s; smem[1][wave] = sq; smem[2][wave] = mx; smem[3][wave] = nmn; }
+  mx = wave_max(mx); nmn = wave_max(nmn);
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { smem[0][wave + 16 * j] = as[j]; smem[1][wave + 16 * j] = aq[j]; }
+    smem[2][wave] = mx; smem[3][wave] = nmn;
+  }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    s = 0; sq = 0; mx = -INFINITY; nmn = -INFINITY;
-    for (int w = 0; w < MOM_THREADS / 64; ++w) {
-      s += smem[0][w]; sq += smem[1][w]; mx = fmax(mx, smem[2][w]); nmn = fmax(nmn, smem[3][w]);
-    }
+  if (wave == 0) {
+    double s = wave_sum(smem[0][lane]), sq = wave_sum(smem[1][lane]);
+    mx = wave_max(lane < MOM_THREADS / 64 ? smem[2][lane] : -INFINITY);
+    nmn = wave_max(lane < MOM_THREADS / 64 ? smem[3][lane] : -INFINITY);
+    if (lane != 0) return;
     const double cnt = (double)(rows * width), mean = s / cnt;
     const double sd = cnt > 1 ? sqrt(fmax((sq - s * mean) / (cnt - 1), 0.0)) : NAN;
     out[0] = mean; out[1] = sd; out[2] = mx; out[3] = -nmn;
