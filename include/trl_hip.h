@@ -1053,16 +1053,21 @@ int trl_act2_bwd_f32(const float* d, const float* t1, const float* t2, float* dz
 
 /* --- K18: running observation normaliser (torchrl/env/base_wrapper.py:44-121) --------------
  * state = {mean[D], var[D], count} fp64 on the device (Normalizer._mean/_var/_count; a fresh
- * normaliser is mean 0, var 1, count 1e-4, :64-69).  sums = {sum x [D], sum x^2 [D], n}.
- *   update_filt   one vector step in one launch: batch moments over the N rows, Chan merge
- *                 (update_mean_var_count, :44-60) when update != 0, then
+ * normaliser is mean 0, var 1, count 1e-4, :64-69).
+ *   update_filt   one vector step in one launch: batch moments over the N rows (two passes: sum x, then
+ *                 sum (x - batch mean)^2), Chan merge (update_mean_var_count, :44-60) when update != 0, then
  *                 out = clip((x - mean) / (sqrt(var) + 1e-4), +-clip) (filt, :86-89); out may be NULL
- *   batch_moments / merge / filt   the same three steps separately, so that env shards on several
- *                 GPUs can all-reduce (SUM) the batch moments between the first two.  D <= 64. */
+ *   batch_moments / merge / filt   the same three steps separately, one process:
+ *                 sums = {sum x [D], sum (x - batch mean)^2 [D], n}
+ *   shard_moments / shard_merge    for env shards on several GPUs: sums = {sum (x - c) [D], sum (x - c)^2 [D], n}, c the
+ *                 mean in `state` (identical on every rank), which the ranks all-reduce (SUM) between the two; shard_merge
+ *                 is given the same, still unmerged state.  D <= 64. */
 int trl_norm_update_filt_f32(const float* x, double* state, float* out, int N, int D, float clip,
                              int update, void* stream);
 int trl_norm_batch_moments_f64(const float* x, int N, int D, double* sums, void* stream);
 int trl_norm_merge_f64(double* state, const double* sums, int D, void* stream);
+int trl_norm_shard_moments_f64(const float* x, const double* state, int N, int D, double* sums, void* stream);
+int trl_norm_shard_merge_f64(double* state, const double* sums, int D, void* stream);
 int trl_norm_filt_f32(const float* x, const double* state, float* out, int N, int D, float clip,
                       void* stream);
 

@@ -91,7 +91,8 @@ def _worker(rank, world, port, out_dir):
 
         # observation normaliser: SUM of the shards' batch moments {sum x, sum x^2, n}, then the
         # same Chan merge on every rank == the single-process update on the full batch (what
-        # torchrl_amd.env.base_wrapper.Normalizer does between trl_norm_batch_moments_f64 and trl_norm_merge_f64)
+        # torchrl_amd.env.base_wrapper.Normalizer does between trl_norm_shard_moments_f64 and trl_norm_shard_merge_f64,
+        # whose sums are taken about the running mean, which every rank holds identically)
         from oracle.normalizer import NormalizerOracle, update_mean_var_count
         rs2 = np.random.RandomState(7)
         state = (np.zeros(D), np.ones(D), 1e-4)

@@ -173,6 +173,8 @@ SIGNATURES = {
     "trl_select_on_mask_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "trl_norm_update_filt_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "trl_norm_batch_moments_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "trl_norm_shard_moments_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "trl_norm_shard_merge_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "trl_norm_merge_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "trl_norm_filt_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "trl_ppo_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1966,10 +1968,26 @@ def norm_update_filt(x, state, out, clip, update):
 
 
 def norm_batch_moments(x, sums):
+    """sums = {sum x, sum (x - batch mean)^2, n}: one process (norm_merge takes them)."""
     N, D = int(x.shape[0]), int(x.shape[1])
     check(lib().trl_norm_batch_moments_f64(dev_ptr(x, name="x"), N, D, dev_ptr(sums, torch.float64, "sums"),
                                            stream_ptr(x.device)), "trl_norm_batch_moments_f64")
     return sums
+
+
+def norm_shard_moments(x, state, sums):
+    """sums = {sum (x - c), sum (x - c)^2, n} about the mean c held in `state`: what env shards all-reduce (SUM) before
+    norm_shard_merge, which is given the same state."""
+    N, D = int(x.shape[0]), int(x.shape[1])
+    check(lib().trl_norm_shard_moments_f64(dev_ptr(x, name="x"), dev_ptr(state, torch.float64, "state"), N, D,
+                                           dev_ptr(sums, torch.float64, "sums"), stream_ptr(x.device)),
+          "trl_norm_shard_moments_f64")
+    return sums
+
+
+def norm_shard_merge(state, sums, D):
+    check(lib().trl_norm_shard_merge_f64(dev_ptr(state, torch.float64, "state"), dev_ptr(sums, torch.float64, "sums"), int(D),
+                                         stream_ptr(state.device)), "trl_norm_shard_merge_f64")
 
 
 def norm_merge(state, sums, D):

@@ -86,9 +86,9 @@ class Normalizer:
             out = torch.empty_like(x)
         update = bool(update and self.should_estimate)
         if update and dist.collectives_active():               # sharded envs: global batch statistics
-            _C.norm_batch_moments(x, self._sums)
+            _C.norm_shard_moments(x, self.state, self._sums)
             dist.all_reduce_sum_(self._sums)
-            _C.norm_merge(self.state, self._sums, self.shape[0])
+            _C.norm_shard_merge(self.state, self._sums, self.shape[0])
             return _C.norm_filt(x, self.state, out, self.clip)
         return _C.norm_update_filt(x, self.state, out, self.clip, update)
 
@@ -97,9 +97,9 @@ class Normalizer:
             return
         x = self._as_batch(data)
         if dist.collectives_active():
-            _C.norm_batch_moments(x, self._sums)
+            _C.norm_shard_moments(x, self.state, self._sums)
             dist.all_reduce_sum_(self._sums)
-            _C.norm_merge(self.state, self._sums, self.shape[0])
+            _C.norm_shard_merge(self.state, self._sums, self.shape[0])
         else:
             _C.norm_update_filt(x, self.state, None, self.clip, True)
 
