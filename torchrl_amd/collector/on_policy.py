@@ -686,7 +686,14 @@ class VecOnPolicyCollector(VecCollector):
             return self._rollout_per_step(n_steps)                           # per-step launch sequence
         if hasattr(self.env, "_obs_normalizer"):
             nz = self.env._obs_normalizer
-            if not self._fused_norm_ok(self.env, self.env.training and nz.should_estimate):
+            update = bool(self.env.training and nz.should_estimate)
+            if not self._fused_norm_ok(self.env, update):
+                return self._rollout_per_step(n_steps)
+            # Frozen statistics: the kernel's workgroups do not meet, and "raw observations for ALL envs once ANY env was
+            # reset" (base_wrapper.py:23-26) needs a flag over all of them -- the kernel then has its own tile's only.  With
+            # normalize_partial_reset the two agree (an env that was not reset is filtered to what it had); otherwise the
+            # per-step route collects.  (Evaluation is not affected: its envs are reset together, in the launch's last step.)
+            if not update and not getattr(self.env, "normalize_partial_reset", False):
                 return self._rollout_per_step(n_steps)
             ob = torch.as_tensor(self.current_ob).to(device=self.env.device, dtype=torch.float32).contiguous().clone()
             noise = self._host_noise(n_steps, self.env) if self.noise_mode == "host" else None

@@ -75,14 +75,21 @@ struct RolloutDev {
 // stamps its slot of the epoch table with the (launch-unique, monotone) step number; readers poll the
 // stamps.  Everything travels through agent-scope relaxed atomics; the poll is capped so a scheduling
 // accident raises the error word (ws header [2]) instead of hanging the GPU.
-__device__ __forceinline__ float ro_row_sum16(float v) {          // sum over the 16 env lanes of a lane group
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false));
+template <int CTRL> __device__ __forceinline__ double ro_dpp_f64(double v) {       // both halves take the same DPP move
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u & 0xFFFFFFFFull), CTRL, 0xF, 0xF, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, false);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double ro_row_sum16(double v) {        // sum over the 16 env lanes of a lane group (row rotations)
+  v += ro_dpp_f64<0x128>(v);
+  v += ro_dpp_f64<0x124>(v);
+  v += ro_dpp_f64<0x122>(v);
+  v += ro_dpp_f64<0x121>(v);
   return v;
 }
-#define NORM_SLOT 40                                 // doubles per workgroup partial: sum x [D] | sum x^2 [D] | any flag | .. | stamp
+// doubles per workgroup partial: sum d [D] | sum d^2 [D] | any flag | .. | stamp, d = x - the running mean of the step's start
+#define NORM_SLOT 40
 
 // HC: head capacity, the rows of the 16-row head tile that are exchanged through LDS -- 8 (the A <= 8 means or logits), or
 // 16 for the state-dependent-std head [mean | log_std] of up to 2 x 8 rows.
@@ -498,13 +505,16 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
         double* part = a.norm_ws + 2 + (size_t)((t & 1) * gridDim.x + blockIdx.x) * NORM_SLOT;
         if (mo == 0) {                                        // every wave holds the same 16 envs: wave 0 publishes
 #pragma unroll
+          // Sums about the running mean the step starts with (the same in every workgroup: each folds the same partials
+          // in the same order), in double from the first addition: about zero, or added in float32, observations far
+          // from zero lose the batch variance to cancellation (profiles/NOTES_rollout_kernel_tests.md).
           for (int q = 0; q < 5; ++q) {
-            const float v = (valid && (q < 4 || g == 0)) ? nx[q] : 0.0f;
-            const float s1 = ro_row_sum16(v), s2 = ro_row_sum16(v * v);
             const int f = q < 4 ? 4 * g + q : 16;
+            const double d = (valid && (q < 4 || g == 0)) ? (double)nx[q] - s_mean[f] : 0.0;
+            const double s1 = ro_row_sum16(d), s2 = ro_row_sum16(d * d);
             if (j == 0 && (q < 4 || g == 0)) {
-              __hip_atomic_store(part + f, (double)s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              __hip_atomic_store(part + D + f, (double)s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              __hip_atomic_store(part + f, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              __hip_atomic_store(part + D + f, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
           }
           const bool fl = __ballot(valid && (done || surpass)) != 0ull;
@@ -543,8 +553,8 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
         __syncthreads();
         if (tid < D) {                                        // Chan merge (update_mean_var_count, :44-60), same in every workgroup
           const double bn = (double)a.N, cnt = s_cnt;
-          const double bmean = s_sum[tid] / bn, bvar = fmax(s_sum[D + tid] / bn - bmean * bmean, 0.0);
-          const double delta = bmean - s_mean[tid], tot = cnt + bn;
+          const double delta = s_sum[tid] / bn, bvar = fmax(s_sum[D + tid] / bn - delta * delta, 0.0);   // (sums about s_mean)
+          const double tot = cnt + bn;
           const double m2 = s_var[tid] * cnt + bvar * bn + delta * delta * cnt * bn / tot;
           s_mean[tid] += delta * bn / tot;
           s_var[tid] = m2 / tot;
@@ -552,6 +562,14 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
         __syncthreads();
         if (tid == 0) s_cnt += (double)a.N;
         any_reset = s_sum[2 * D] != 0.0;
+      } else {
+        // Frozen statistics: the workgroups do not meet, so the flag is the tile's own (every wave holds the same 16 envs).
+        // An env that was reset then starts its episode from its reset observation and not from the filtered last
+        // observation of the episode before; with normalize_partial_reset that is the reference's result for every env
+        // (the filter of an env that was not reset gives nxn again), without it the envs of OTHER tiles keep their
+        // normalised observation where the reference hands out raw ones -- the collector sends that case to the per-step
+        // route (collector/on_policy.py).
+        any_reset = __ballot(valid && (done || surpass)) != 0ull;
       }
 #pragma unroll
       for (int q = 0; q < 5; ++q) {
