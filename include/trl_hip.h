@@ -388,7 +388,8 @@ typedef struct trl_adam_t {
   float beta1, beta2, eps;
   int step_count;
   float grad_scale;           /* grads are multiplied by this first (1/world_size) */
-  float* norms_out;           /* (n_groups) pre-clip global norms */
+  float* norms_out;           /* (n_groups) pre-clip global norms of the scaled gradients; max_norm <= 0: the norm pass
+                                 is skipped and 0 is written (no caller reads the norms without clipping) */
   int device_state;           /* trl_ppo_reduce_adam_f32 only: 1 = take the step count and the two learning
                                  rates from its workspace header instead of step_count / group_lr
                                  (ws[1]: steps taken so far, uint32; ws[2], ws[3]: lr; ws[4..7]: two doubles

@@ -278,16 +278,22 @@ def loss_error_ratios(got, want, B, n_global):
     w = want["d_logstd"].double()
     bound = 1e-4 * B / ng + 1e-4 * want["dls_terms"].abs().sum(0)
     out["d_logstd"] = float(((got["d_logstd"].double() - w).abs() / bound).max())
+    out["info"] = info_error_ratio(got["info"], want["info"], B)
+    return out
+
+
+def info_error_ratio(got, want, B):
+    """Worst err / bound over the 24 info slots: rel 1e-4, abs 1e-5 (times B on slots that hold sums); NaN and sentinel slots
+    must be equal."""
     worst = 0.0
     for k in range(24):
-        g, w = float(got["info"][k]), float(want["info"][k])
+        g, w = float(got[k]), float(want[k])
         if math.isnan(w) or w == SENTINEL:
             ok = (math.isnan(g) and math.isnan(w)) or g == w
             worst = max(worst, 0.0 if ok else float("inf"))
         else:
             worst = max(worst, abs(g - w) / ((1e-5 * B if k in SUM_SLOTS else 1e-5) + 1e-4 * abs(w)))
-    out["info"] = worst
-    return out
+    return worst
 
 
 def value_tie_case(clip=0.25):
