@@ -948,6 +948,40 @@ int trl_dqn_act_f32(const float* h, const float* w, const float* bias, int N, in
                     const int64_t* rand_act, float epsilon, float* q_out, int64_t* action, int64_t* ring_row, int n_rows,
                     void* stream);     /* ring_row (nullable): ring_row[0] = (ring_row[0] + 1) % n_rows rides along, see
                                           trl_synth_frames_collect_u8 */
+/* --- K19: Bootstrapped DQN (torchrl/algo/off_policy/bootstrapped_dqn.py:73-90, policies/discrete_policies.py:92-121),
+ * k_bootdqn.hip.  The Q values of all K heads are one dense head-major stack (K, rows, A): head k's block is a dense
+ * (rows, A) tensor.  Every entry point refuses outside 1 <= K <= 64 and 1 <= A <= 64 (TRL_EINVAL).
+ *
+ * Actions for N envs.  head (N, nullable) non-NULL: action[n] = argmax_a q[head[n]][n][a], a stored head outside [0, K)
+ * clamped, never used as an index.  head NULL: argmax_a of the ensemble vote sum_k q[k][n][a], summed in ascending k in
+ * fp32 (the sums are compared, not the means).  Ties go to the lowest index.  q_sel (N, A, nullable): the active head's
+ * row, or the vote sum times 1 / K; onehot (N, A, nullable): the indicator of the action. */
+int trl_boot_act_i64(const float* q, const int64_t* head, int K, int N, int A, int64_t* action, float* q_sel,
+                     float* onehot, void* stream);
+/* The head an env plays, drawn in place: where reset_mask[n] != 0 (everywhere when reset_mask is NULL)
+ * head[n] = (uint64(x) * K) >> 32, x the Philox word of (seed, counter, global env index g = env_offset + n) under the
+ * head tag -- element g & 3 of block g >> 2, counter words (lo32(counter), hi32(counter)); other entries stay as they are. */
+int trl_boot_heads_i64(int64_t* head, const uint8_t* reset_mask, int N, int K, int64_t seed, int64_t counter,
+                       int64_t env_offset, void* stream);
+/* The Bernoulli(p) masks of one vector step: out (N, K), out[n][k] = 1 if (x >> 8) * 2^-24 + 2^-25 < p else 0, x the
+ * Philox word of flat index i = (env_offset + n) K + k under the mask tag (element i & 3 of block i >> 2). */
+int trl_boot_masks_f32(float* out, int N, int K, float p, int64_t seed, int64_t counter, int64_t env_offset,
+                       void* stream);
+/* The TD loss over K heads: q, q_next, dq (K, B, A); masks (B, K); rewards, terminals (B); acts / acts_f as in K14
+ * (exactly one non-NULL, the same clamp).  Per (b, k): e = q[k][b][a_b] - (r_b + gamma (1 - d_b) max_a' q_next[k][b][a']);
+ * dq = 2 masks[b][k] e / (K B) at the taken action, exactly 0 elsewhere (and exactly 0 where the mask is 0).
+ * sums (3 doubles): sum_b sum_k masks e^2 / K, sum masks, sum_b r_b; ring / slots / update_count as in K14.
+ * Deterministic: up to 256 workgroups (a function of K B alone) with a fixed item -> thread map; the workgroup that arrives
+ * last adds the workgroups' partial sums in workgroup order (an integer arrival counter, no float atomics, nobody waits).
+ * workspace: trl_boot_td_loss_workspace() bytes, 16-byte aligned, ZEROED ONCE before the first call and then left alone
+ * (the counter lives there and is back at zero when a launch ends); calls sharing a workspace must be stream-ordered. */
+int64_t trl_boot_td_loss_workspace(void);
+int trl_boot_td_loss_f32(const float* q, const float* q_next, const int64_t* acts, const float* acts_f,
+                         const float* rewards, const float* terminals, const float* masks, float gamma, int K, int B,
+                         int A, float* dq, double* sums, double* ring, int slots, const double* update_count,
+                         void* workspace, void* stream);
+/* The K heads' gradients at the trunk feature folded into one: src (K, n) -> dst (n), ascending k, fp32. */
+int trl_boot_fold_f32(const float* src, float* dst, int K, int64_t n, void* stream);
 /* synthetic Atari-shaped env: (N, C, HW) uint8 frame stacks, Philox frames (see k_dqn.hip) */
 int trl_synth_frames_step_u8(uint8_t* frames, const int64_t* acts, int32_t* t_env, int64_t env_seed_base,
                              int horizon, int A, uint8_t* next_obs, float* rewards, float* dones,

@@ -271,6 +271,14 @@ SIGNATURES = {
                          [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trl_quantile_huber_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 +
                                [C.c_int, C.c_void_p, C.c_void_p]),
+    "trl_boot_act_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "trl_boot_heads_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_boot_masks_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_boot_td_loss_workspace": (C.c_int64, []),
+    "trl_boot_td_loss_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "trl_boot_fold_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "trl_dqn_act_supported": (C.c_int, [C.c_int, C.c_int]),
     "trl_dqn_act_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1065,13 +1073,35 @@ def _ptrs(tensors, name, allow_none=False):
     return (C.c_void_p * len(tensors))(*[dev_ptr(t, name=name, allow_none=allow_none) for t in tensors])
 
 
-def linear_fwd_group(xs, ws, biases, act):
-    """[act(x_g @ w_g.T + b_g)] for G same-shaped layers in one launch (twin critics, targets, several inputs)."""
+GROUP_MAX = 12                  # problems per grouped dense-layer launch (k_gemm.hip GEMM_MAX_GROUPS)
+
+
+def _group_chunks(G):
+    """[(lo, hi)] cutting G problems into grouped launches of at most GROUP_MAX (Bootstrapped DQN: up to 64 heads)."""
+    return [(lo, min(lo + GROUP_MAX, G)) for lo in range(0, G, GROUP_MAX)]
+
+
+def _cut(ts, lo, hi):
+    return None if ts is None else ts[lo:hi]
+
+
+def linear_fwd_group(xs, ws, biases, act, ys=None):
+    """[act(x_g @ w_g.T + b_g)] for G same-shaped layers in one launch (twin critics, targets, several inputs); more than
+    GROUP_MAX problems run as ceil(G / GROUP_MAX) launches.
+    ys: the G (M, N) outputs to write (e.g. the consecutive blocks of one (G, M, N) stack); None: fresh tensors."""
     G = len(xs)
+    if G > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(G):
+            out += linear_fwd_group(xs[lo:hi], ws[lo:hi], _cut(biases, lo, hi), act, _cut(ys, lo, hi))
+        return out
     M, K, N = int(xs[0].shape[0]), int(xs[0].shape[1]), int(ws[0].shape[0])
     if any(tuple(x.shape) != (M, K) for x in xs) or any(tuple(w.shape) != (N, K) for w in ws):
         raise TrlError("linear_fwd_group: the layers of a group must have identical shapes")
-    ys = [torch.empty((M, N), dtype=torch.float32, device=xs[0].device) for _ in range(G)]
+    if ys is None:
+        ys = [torch.empty((M, N), dtype=torch.float32, device=xs[0].device) for _ in range(G)]
+    elif len(ys) != G or any(tuple(y.shape) != (M, N) for y in ys):
+        raise TrlError("linear_fwd_group: ys must be %d tensors of shape %s" % (G, (M, N)))
     need = lib().trl_linear_fwd_workspace(M, K, N)
     if need > 0:                                                         # few rows, long reduction: split-K + fold, grouped
         wsp = torch.empty((G * need,), dtype=torch.float32, device=xs[0].device)
@@ -1085,7 +1115,13 @@ def linear_fwd_group(xs, ws, biases, act):
 
 
 def outer_gate_group(dqs, ws, hs, act):
-    """[dq_g w_g^T * act'(h_g)]: the gated input gradient of G one-output layers in one streaming launch."""
+    """[dq_g w_g^T * act'(h_g)]: the gated input gradient of G one-output layers in one streaming launch (more than
+    GROUP_MAX: ceil(G / GROUP_MAX) launches)."""
+    if len(hs) > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(len(hs)):
+            out += outer_gate_group(dqs[lo:hi], ws[lo:hi], hs[lo:hi], act)
+        return out
     M, N = int(hs[0].shape[0]), int(hs[0].shape[1])
     outs = [torch.empty((M, N), dtype=torch.float32, device=hs[0].device) for _ in hs]
     check(lib().trl_outer_gate_group_f32(len(hs), _ptrs(dqs, "dq"), _ptrs(ws, "w"), _ptrs(hs, "h"), _ptrs(outs, "out"),
@@ -1118,10 +1154,20 @@ def mlp3_forward_group(layers_list, xs, act, last_act, keep):
     return list(zip(h1s, h2s, ys))
 
 
-def linear_bwd_input_group(dys, y_gates, gate_act, ws):
+def linear_bwd_input_group(dys, y_gates, gate_act, ws, dxs=None):
+    """dxs: the G (M, K) outputs to write (e.g. the blocks of one (G, M, K) stack); None: fresh tensors.  More than
+    GROUP_MAX problems run as ceil(G / GROUP_MAX) launches."""
     G = len(dys)
+    if G > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(G):
+            out += linear_bwd_input_group(dys[lo:hi], _cut(y_gates, lo, hi), gate_act, ws[lo:hi], _cut(dxs, lo, hi))
+        return out
     M, N, K = int(dys[0].shape[0]), int(dys[0].shape[1]), int(ws[0].shape[1])
-    dxs = [torch.empty((M, K), dtype=torch.float32, device=dys[0].device) for _ in range(G)]
+    if dxs is None:
+        dxs = [torch.empty((M, K), dtype=torch.float32, device=dys[0].device) for _ in range(G)]
+    elif len(dxs) != G or any(tuple(d.shape) != (M, K) for d in dxs):
+        raise TrlError("linear_bwd_input_group: dxs must be %d tensors of shape %s" % (G, (M, K)))
     check(lib().trl_linear_bwd_input_group_f32(G, _ptrs(dys, "dy"), _ptrs(y_gates, "y_gate", True), gate_act,
                                                _ptrs(ws, "w"), _ptrs(dxs, "dx"), M, K, N, stream_ptr(dys[0].device)),
           "trl_linear_bwd_input_group_f32")
@@ -1129,7 +1175,13 @@ def linear_bwd_input_group(dys, y_gates, gate_act, ws):
 
 
 def linear_bwd_weight_group(dys, y_gates, gate_act, xs, dws, dbs, workspace=None):
+    """More than GROUP_MAX problems run as ceil(G / GROUP_MAX) launches that use the workspace one after the other."""
     G = len(dys)
+    if G > GROUP_MAX:
+        for lo, hi in _group_chunks(G):
+            linear_bwd_weight_group(dys[lo:hi], _cut(y_gates, lo, hi), gate_act, xs[lo:hi], dws[lo:hi], _cut(dbs, lo, hi),
+                                    workspace=workspace)
+        return
     M, N, K = int(dys[0].shape[0]), int(dys[0].shape[1]), int(xs[0].shape[1])
     need = G * lib().trl_linear_bwd_weight_workspace(M, K, N)
     if workspace is None or workspace.numel() < need:
@@ -1852,6 +1904,101 @@ def eps_greedy(q, A, Q, u, rand_act, epsilon, ring_row=None, n_rows=0):
                                    dev_ptr(ring_row, torch.int64, "ring_row", allow_none=True), int(n_rows),
                                    stream_ptr(q.device)), "trl_eps_greedy_i64")
     return action
+
+
+# ---- Bootstrapped DQN (k_bootdqn.hip): Q values of all heads as one head-major (K, rows, A) stack ----
+def boot_stack(q, what="q"):
+    """The (K, rows, A) stack itself, or the list of its K consecutive (rows, A) blocks -> (stack, K, rows, A)."""
+    if isinstance(q, (list, tuple)):
+        K = len(q)
+        if K == 0 or any(t.dim() != 2 or t.shape != q[0].shape or not t.is_contiguous() for t in q):
+            raise TrlError("%s: a list of K same-shaped contiguous (rows, A) blocks" % what)
+        rows, A = int(q[0].shape[0]), int(q[0].shape[1])
+        base = q[0]
+        if any(t.data_ptr() != base.data_ptr() + 4 * k * rows * A or t.dtype != torch.float32 for k, t in enumerate(q)):
+            raise TrlError("%s: the K blocks must be consecutive slices of ONE (K, rows, A) float32 allocation" % what)
+        dev_ptr(base, name=what)
+        return base, K, rows, A
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise TrlError("%s: a (K, rows, A) stack" % what)
+    return q, int(q.shape[0]), int(q.shape[1]), int(q.shape[2])
+
+
+def boot_act(q, head=None, want_q=False, onehot=None):
+    """(action (N,) int64, q_sel (N, A) or None): each env's arg-max under its head, or (head None) of the ensemble vote."""
+    q, K, N, A = boot_stack(q)
+    action = torch.empty(N, dtype=torch.int64, device=q.device)
+    q_sel = torch.empty((N, A), dtype=torch.float32, device=q.device) if want_q else None
+    if head is not None and int(head.numel()) != N:
+        raise TrlError("boot_act: head holds one index per env (%d), got %d" % (N, head.numel()))
+    if onehot is not None and tuple(onehot.shape) != (N, A):
+        raise TrlError("boot_act: onehot is (N, A) = %s" % ((N, A),))
+    check(lib().trl_boot_act_i64(dev_ptr(q, name="q"), dev_ptr(head, torch.int64, "head", allow_none=True), K, N, A,
+                                 dev_ptr(action, torch.int64, "action"), dev_ptr(q_sel, name="q_sel", allow_none=True),
+                                 dev_ptr(onehot, name="onehot", allow_none=True), stream_ptr(q.device)), "trl_boot_act_i64")
+    return action, q_sel
+
+
+def boot_heads(head, K, seed, counter, env_offset=0, reset_mask=None):
+    """Draw head[n] in [0, K) in place where reset_mask[n] != 0 (everywhere when None)."""
+    N = int(head.numel())
+    if reset_mask is not None and int(reset_mask.numel()) != N:
+        raise TrlError("boot_heads: reset_mask holds one byte per env")
+    check(lib().trl_boot_heads_i64(dev_ptr(head, torch.int64, "head"), dev_ptr(reset_mask, torch.uint8, "reset_mask", True),
+                                   N, int(K), int(seed), int(counter), int(env_offset), stream_ptr(head.device)),
+          "trl_boot_heads_i64")
+    return head
+
+
+def boot_masks(out, p, seed, counter, env_offset=0):
+    """out (N, K) <- the Bernoulli(p) masks of (seed, counter, global env index)."""
+    if out.dim() != 2:
+        raise TrlError("boot_masks: out is (N, K)")
+    check(lib().trl_boot_masks_f32(dev_ptr(out, name="out"), int(out.shape[0]), int(out.shape[1]), float(p), int(seed),
+                                   int(counter), int(env_offset), stream_ptr(out.device)), "trl_boot_masks_f32")
+    return out
+
+
+def boot_td_loss_workspace(device):
+    """Zeroed workspace of `boot_td_loss` (keep it: it carries the kernel's arrival counter from launch to launch)."""
+    return torch.zeros(int(lib().trl_boot_td_loss_workspace()), dtype=torch.uint8, device=device)
+
+
+def boot_td_loss(q, q_next, acts, rew, term, masks, gamma, sums, ring=None, workspace=None):
+    """dq (K, B, A) of the masked K-head TD loss; `sums` (3 doubles) and the optional `ring` row as `dqn_td_loss`.
+    workspace: `boot_td_loss_workspace(device)`, kept by the caller (None: a fresh one for this call)."""
+    q, K, B, A = boot_stack(q)
+    qn, Kn, Bn, An = boot_stack(q_next, "q_next")
+    if (Kn, Bn, An) != (K, B, A) or tuple(masks.shape) != (B, K) or int(rew.numel()) != B or int(term.numel()) != B or \
+            int(acts.numel()) != B:
+        raise TrlError("boot_td_loss: q, q_next (K, B, A), masks (B, K), acts / rew / term (B)")
+    dq = torch.empty((K, B, A), dtype=torch.float32, device=q.device)
+    ai, af = _acts_ptrs(acts)
+    rp, slots, cp = _ring_args(ring)
+    q_ptr = dev_ptr(q, name="q")                                         # (a CPU tensor is refused before anything is allocated)
+    if workspace is None:
+        workspace = boot_td_loss_workspace(q.device)
+    if int(workspace.numel()) < int(lib().trl_boot_td_loss_workspace()):
+        raise TrlError("boot_td_loss: the workspace holds %d bytes, needs %d"
+                       % (workspace.numel(), lib().trl_boot_td_loss_workspace()))
+    check(lib().trl_boot_td_loss_f32(q_ptr, dev_ptr(qn, name="q_next"), ai, af, dev_ptr(rew, name="rew"),
+                                     dev_ptr(term, name="term"), dev_ptr(masks, name="masks"), float(gamma), K, B, A,
+                                     dev_ptr(dq, name="dq"), dev_ptr(sums, torch.float64, "sums"), rp, slots, cp,
+                                     dev_ptr(workspace, torch.uint8, "workspace"), stream_ptr(q.device)),
+          "trl_boot_td_loss_f32")
+    return dq
+
+
+def boot_fold(src, out=None):
+    """(K, ...) -> (...): the sum over the leading axis in ascending k, fp32."""
+    K = int(src.shape[0])
+    if out is None:
+        out = torch.empty(tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    if out.numel() * K != src.numel():
+        raise TrlError("boot_fold: out holds one block of src")
+    check(lib().trl_boot_fold_f32(dev_ptr(src, name="src"), dev_ptr(out, name="out"), K, int(out.numel()),
+                                  stream_ptr(src.device)), "trl_boot_fold_f32")
+    return out
 
 
 def dqn_act_ok(h, w):

@@ -1,0 +1,175 @@
+"""Bootstrapped DQN on the HIP path (torchrl/algo/off_policy/bootstrapped_dqn.py:7-104).
+
+K Q heads on one MLP trunk (`networks.BootstrappedNet`); every stored transition carries a Bernoulli(p) mask per head
+(drawn by the collector, trl_boot_masks_f32) and head k learns from the transitions whose mask k is set:
+
+    loss = mean_b sum_k masks[b, k] (Q_k(s_b)[a_b] - (r_b + gamma (1 - d_b) max_a' Q'_k(s'_b)[a']))^2 / K
+
+`update(batch)`: the trunk once per network, all K heads as ONE grouped launch per head level (online on obs, target on
+next_obs) writing head-major (K, B, A) stacks, trl_boot_td_loss_f32 for the loss sums and dL/dQ, the heads' backward
+pass as one grouped weight- and one grouped input-gradient launch per level, trl_boot_fold_f32 to sum the K gradients at
+the trunk feature, the trunk's backward pass, then Adam (+ Polyak) over ONE flat buffer of trunk and heads, as DQN does.
+The launch count does not grow with K up to 12 heads, the most problems one grouped dense-layer launch carries
+(_C.GROUP_MAX); beyond, each grouped launch of the heads becomes ceil(K / 12) launches.  The reference does not detach the target; that only reaches the target net's
+unused gradients.
+
+Scope: MLP trunks, one rank, Adam; 1 <= K <= 64 heads and 1 <= A <= 64 actions.  Everything else raises _C.TrlError.
+"""
+import torch
+import torch.optim as optim
+
+from ... import _C, dist, ops
+from ...networks import flatten_into
+from .dqn import DQN, _FusedDQN
+
+
+class BootstrappedDQN(DQN):
+    sample_key = ("obs", "next_obs", "acts", "rewards", "terminals", "masks")
+
+    def __init__(self, head_num=10, bernoulli_p=0.5, **kwargs):
+        super().__init__(**kwargs)
+        self.head_num = int(head_num)
+        self.bernoulli_p = float(bernoulli_p)
+        if not 0.0 <= self.bernoulli_p <= 1.0:
+            raise _C.TrlError("BootstrappedDQN: bernoulli_p is a probability, got %s" % (bernoulli_p,))
+        qf_heads = getattr(self.qf, "head_num", None)
+        if qf_heads != self.head_num or getattr(self.pf, "head_num", None) != self.head_num:
+            raise _C.TrlError("BootstrappedDQN(head_num=%d) needs a BootstrappedNet and a BootstrappedDQNDiscretePolicy with "
+                              "the same number of heads (network: %s, policy: %s)"
+                              % (self.head_num, qf_heads, getattr(self.pf, "head_num", None)))
+        self.pf.bernoulli_p = self.bernoulli_p                          # the collector draws the masks with it
+
+    def engine(self):
+        if self._engine is None:
+            if self.optimizer_class is not optim.Adam:
+                raise _C.TrlError("the fused Bootstrapped DQN step implements torch.optim.Adam only (got %s)"
+                                  % getattr(self.optimizer_class, "__name__", self.optimizer_class))
+            if dist.world_size() != 1:
+                raise _C.TrlError("Bootstrapped DQN runs on one rank (got a world of %d): several ranks are not built"
+                                  % dist.world_size())
+            self._engine = _FusedBootDQN(self)
+        return self._engine
+
+
+class _FusedBootDQN(_FusedDQN):
+    """`_FusedDQN`'s protocol (static inputs, eager -> captured -> replayed launch sequence, loss sums through a StatRing,
+    whole epochs as one graph) for a BootstrappedNet."""
+    KEYS = ("obs", "next_obs", "acts", "rewards", "terminals", "masks")
+
+    def __init__(self, algo):
+        from ...networks.base import MLPBase
+        self.algo = algo
+        qf = algo.qf
+        self.dev = next(qf.parameters()).device
+        if self.dev.type != "cuda":
+            raise _C.TrlError("Bootstrapped DQN networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
+        if not isinstance(qf.base, MLPBase) or qf.add_ln:
+            raise _C.TrlError("Bootstrapped DQN runs MLP trunks without LayerNorm only")
+        self.is_mlp = True
+        self.K, self.A = int(algo.head_num), int(algo.env.action_space.n)
+        if not 1 <= self.K <= 64 or not 1 <= self.A <= 64 or int(qf.out_dim) != self.A:
+            raise _C.TrlError("Bootstrapped DQN: 1..64 heads and 1..64 actions, the heads as wide as the env's action set "
+                              "(K=%d, A=%d, heads emit %d)" % (self.K, self.A, int(qf.out_dim)))
+        self.act = ops.act_code(qf)
+        self._init_run_state()                                           # (ring, slab, static inputs, graphs, step state)
+        self._loss_ws = _C.boot_td_loss_workspace(self.dev)              # (the loss launch's arrival counter lives there)
+        self._home()
+
+    def _home(self):
+        """One flat parameter / gradient / Adam buffer over trunk and all heads (module order), the networks' parameters
+        views of it and `qf_optimizer.state` bound to the moments."""
+        algo, qf, tqf = self.algo, self.algo.qf, self.algo.target_qf
+        K = self.K
+        self.trunk, self.ttrunk = qf.trunk_layers(), tqf.trunk_layers()
+        self.heads = [qf.head_layers(k) for k in range(K)]
+        self.theads = [tqf.head_layers(k) for k in range(K)]
+        plist, tlist = qf.param_list(), tqf.param_list()
+        self.flat, self.tflat = flatten_into(plist), flatten_into(tlist)
+        old_m, old_v = getattr(self, "m", None), getattr(self, "v", None)
+        self.grads = torch.zeros_like(self.flat)
+        keep = old_m is not None and old_m.numel() == self.flat.numel()
+        self.m = old_m.to(self.dev) if keep else torch.zeros_like(self.flat)
+        self.v = old_v.to(self.dev) if keep else torch.zeros_like(self.flat)
+        views, off = [], 0
+        for p in plist:
+            n = p.numel()
+            views.append(self.grads[off:off + n].view(p.shape))
+            algo.qf_optimizer.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
+                                          "exp_avg_sq": self.v[off:off + n].view(p.shape)}
+            off += n
+        pairs = [(views[i], views[i + 1]) for i in range(0, len(views), 2)]
+        nt, nh = len(self.trunk), len(self.heads[0])
+        self.trunk_gviews = pairs[:nt]
+        self.head_gviews = [pairs[nt + k * nh:nt + (k + 1) * nh] for k in range(K)]
+        self._homed = (plist[0].data_ptr(), plist[-1].data_ptr(), tlist[0].data_ptr(), tlist[-1].data_ptr())
+        self._graphs, self._seen = {}, set()
+
+    def _check_home(self):
+        """A `.to()` or an assignment that replaced parameter storage (a checkpoint load copies in place and needs nothing):
+        re-home the flat buffers and drop the captured graphs, which carry the old addresses."""
+        p, t = self.algo.qf.param_list(), self.algo.target_qf.param_list()
+        if (p[0].data_ptr(), p[-1].data_ptr(), t[0].data_ptr(), t[-1].data_ptr()) != self._homed:
+            self._home()
+
+    def _extra_static(self, B):
+        return {"masks": torch.zeros((B, self.K), dtype=torch.float32, device=self.dev)}
+
+    def resolve(self, handles):
+        rows = self._ring.read([(h[0], h[1]) for h in handles]).tolist()
+        return [{'Reward_Mean': s[2] / B, 'Training/qf_loss': s[0] / B} for s, (_, _, B) in zip(rows, handles)]
+
+    def _handles(self, count, B):
+        return [(ref, row, B) for ref, row in self._ring.handles(self.step_count - count, count)]
+
+    def enqueue(self, batch):
+        self._check_home()
+        return super().enqueue(batch)
+
+    def enqueue_epoch(self, count):
+        self._check_home()
+        return super().enqueue_epoch(count)
+
+    def _sequence(self, st, soft):
+        """The fixed launch sequence of one update on the static inputs (eager, or under graph capture)."""
+        algo, dev, K, A, act = self.algo, self.dev, self.K, self.A, self.act
+        obs, nobs = st["obs"], st["next_obs"]
+        B, F = int(obs.shape[0]), int(self.trunk[-1][0].shape[0])
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        # trunks: online on obs (kept for the backward pass), target on next_obs
+        feat, trunk_tape = ops.mlp_forward(self.trunk, obs, act, last_act=act)
+        tfeat, _ = ops.mlp_forward(self.ttrunk, nobs, act, last_act=act, keep=False)
+        # all K heads: one grouped launch per head level, the last one writing the head-major (K, B, A) stack
+        q, qn = f(K, B, A), f(K, B, A)
+        _, tapes = ops.mlp_forward_group(self.heads, [feat] * K, act, out=list(q.unbind(0)))
+        ops.mlp_forward_group(self.theads, [tfeat] * K, act, keep=[False] * K, out=list(qn.unbind(0)))
+        dq = _C.boot_td_loss(q, qn, st["acts"].view(-1), st["rewards"].view(-1), st["terminals"].view(-1), st["masks"],
+                             algo.discount, self.sums, ring=(self._ring.t, self.step_state), workspace=self._loss_ws)
+        wsz = _C.lib().trl_linear_bwd_weight_workspace
+        need = max([wsz(B, int(w.shape[1]), int(w.shape[0])) for w, _ in self.trunk] +
+                   [K * wsz(B, int(w.shape[1]), int(w.shape[0])) for w, _ in self.heads[0]])
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(max(need, 4), device=dev)
+        # heads backwards: per level one grouped weight-gradient and one grouped input-gradient launch; the K gradients at
+        # the trunk feature land in one (K, B, F) stack and are folded in ascending k by one launch
+        dfeat_k = f(K, B, F)
+
+        def sink(dys, gates, gate_act, ws):
+            _C.linear_bwd_input_group(dys, gates, gate_act, ws, dxs=list(dfeat_k.unbind(0)))
+        ops.mlp_backward_group(tapes, list(dq.unbind(0)), self.head_gviews, need_input=True, workspace=self.workspace,
+                               input_sink=sink)
+        dfeat = _C.boot_fold(dfeat_k)
+        ops.mlp_backward(trunk_tape, dfeat, grads=self.trunk_gviews, workspace=self.workspace)
+        a = _C.AdamArgs()
+        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
+                                                      self.m.data_ptr(), self.v.data_ptr())
+        a.n_groups = 1
+        a.group_sizes[0] = self.flat.numel()
+        a.group_lr[0] = algo.qf_optimizer.param_groups[0]['lr']
+        a.max_norm, a.beta1, a.beta2 = 0.0, 0.9, 0.999
+        a.eps = float(algo.optimizer_info.get("eps", 1e-8))
+        a.grad_scale, a.norms_out = 1.0, None
+        a.step_count, a.step_state = 0, self.step_state.data_ptr()       # the step count lives on the device
+        if soft:                                                         # Adam, then Polyak (which also advances the step state)
+            _C.clip_adam_polyak(a, self.tflat, self.flat, algo.tau, dev)
+        else:
+            _C.clip_adam(a, dev)

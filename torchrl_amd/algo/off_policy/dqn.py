@@ -84,6 +84,8 @@ class QRDQN(DQN):
 
 
 class _FusedDQN:
+    KEYS = ("obs", "next_obs", "acts", "rewards", "terminals")       # the sampled keys = the static input tensors
+
     def __init__(self, algo):
         self.algo = algo
         self.dev = next(algo.qf.parameters()).device
@@ -114,9 +116,15 @@ class _FusedDQN:
             algo.qf_optimizer.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
                                           "exp_avg_sq": self.v[off:off + n].view(p.shape)}
             off += n
+        self.A = int(algo.env.action_space.n)
+        self._init_run_state()
+
+    def _init_run_state(self):
+        """What `enqueue` / `enqueue_epoch` / `resolve` / `_run` keep between updates, whatever the network is (the
+        Bootstrapped DQN engine builds its own parameter buffers and calls this too)."""
+        algo = self.algo
         self.step_count = 0
         self.sums = torch.zeros(3, dtype=torch.float64, device=self.dev)
-        self.A = int(algo.env.action_space.n)
         self.workspace = None
         # update u's three sums are filed into ring row u % slots by its loss launch (one rank), or copied there
         self._ring = StatRing(max(64, int(getattr(algo, "opt_times", 1))), 3, torch.float64, self.dev)
@@ -152,14 +160,18 @@ class _FusedDQN:
             f = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
             st = {"obs": torch.zeros(shape, dtype=want, device=dev), "next_obs": torch.zeros(shape, dtype=want, device=dev),
                   "acts": f(B, 1), "rewards": f(B, 1), "terminals": f(B, 1)}
+            st.update(self._extra_static(B))
             self._static, self._graphs, self._seen = st, {}, set()
-        for k in ("obs", "next_obs", "acts", "rewards", "terminals"):
+        for k in self.KEYS:
             src = batch[k]
             if src is st[k]:
                 continue
             src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
             st[k].copy_(src.to(device=dev, dtype=st[k].dtype).reshape(st[k].shape), non_blocking=True)
         return st, B
+
+    def _extra_static(self, B):
+        return {}
 
     def _sequence(self, st, soft):
         """The fixed launch sequence of one update on the static inputs (eager, or under graph capture)."""
@@ -277,7 +289,7 @@ class _FusedDQN:
                 dist.collectives_active() or os.environ.get("TRL_NO_GRAPH") == "1" or not hasattr(buf, "gather_sources") or \
                 int(st["obs"].shape[0]) != B or (not soft and any((done + j) % period == 0 for j in range(1, count + 1))):
             return None
-        keys = ("obs", "next_obs", "acts", "rewards", "terminals")
+        keys = self.KEYS
         srcs = buf.gather_sources(keys)
         nrows = buf._rows_per_batch(B)
         if srcs is None or any(s.dtype != st[k].dtype or s[0].numel() * nrows != st[k].numel() for s, k in zip(srcs, keys)):

@@ -133,6 +133,11 @@ class VecCollector(_CollectorBase):
     partial reset.  `epoch_frames // env_nums` vector steps per epoch (base.py:179); nothing is read
     back until the epoch ends.  Exploration noise: CPU `torch.randn(N, A)` per step (reference
     stream, its Q5) or the device Philox stream (`noise_mode="device"`).
+
+    A Bootstrapped DQN policy (`pf.head_num`): every stored step also files its Bernoulli(p) masks into ring key `masks`
+    (N, K) (trl_boot_masks_f32, keyed by the global step and env index), the envs whose episode just ended draw a fresh
+    head, and a device env with one-hot actions steps on the one-hot rows the action launch wrote.  Evaluation draws
+    nothing and leaves the heads and the step count alone.
     """
     EP_LOG_CAP = 1 << 16
 
@@ -255,6 +260,14 @@ class VecCollector(_CollectorBase):
         from .. import ops
         pf = self.pf
         ob = env.cur_obs if ob is None else ob
+        if not self.continuous and hasattr(pf, "head_num"):
+            # Bootstrapped DQN: each env's arg-max under the head it plays, or (evaluation) the ensemble vote -- one
+            # launch behind the Q network; on a device env with one-hot actions that launch writes the one-hot rows too
+            onehot = None
+            if getattr(env, "discrete", False) and not getattr(env, "is_host_env", False):
+                onehot = torch.empty(env.env_nums, env.act_dim, device=env.device)
+            self._boot_onehot = onehot
+            return pf.act_on(ob, greedy_vote=deterministic, want_q=False, onehot=onehot)[1]
         if not self.continuous:                                             # epsilon-greedy over a Q network
             if deterministic:
                 return torch.as_tensor(pf.eval_act(ob)).to(env.device).reshape(-1).contiguous()
@@ -292,10 +305,20 @@ class VecCollector(_CollectorBase):
         if self._one_launch_step(env, nz):
             return self._step_one_launch(env, store, deterministic, max_frames)
         act = self._policy_action(env, deterministic, pol_in)
+        boot = not self.continuous and hasattr(self.pf, "head_num")          # Bootstrapped DQN (see below)
+        act_env = act
+        if boot:
+            a_dim = 1                                                        # the stored action is the index
+            if self._boot_onehot is not None:
+                act_env = self._boot_onehot                                  # the device env steps on one-hot rows
         if store:
             row = buf._top
             buf._ensure_key("obs", (n, d))[row].copy_(pol_in)                # before the env advances in place
             buf._ensure_key("acts", (n, a_dim))[row].copy_(act if self.continuous else act.reshape(n, 1))
+            if boot:
+                # this step's Bernoulli(p) masks, one per (env, head): a function of (seed, global step, global env index)
+                _C.boot_masks(buf._ensure_key("masks", (n, int(self.pf.head_num)))[row], self.pf.bernoulli_p, self.pf.seed,
+                              self.global_step, int(getattr(env, "index_offset", 0)))
             nxt = buf._ensure_key("next_obs", (n, d))[row]
             rew = buf._ensure_key("rewards", (n, 1))[row]
             done = buf._ensure_key("terminals", (n, 1))[row]
@@ -304,13 +327,16 @@ class VecCollector(_CollectorBase):
             rew = torch.empty(n, 1, device=env.device)
             done = torch.empty(n, 1, device=env.device)
         raw_next = nxt if nz is None else torch.empty(n, d, device=env.device)
-        self._env_advance(env, act, raw_next, rew, done, buf._ensure_key("time_limits", (n, 1))[row] if store else None)
+        self._env_advance(env, act_env, raw_next, rew, done, buf._ensure_key("time_limits", (n, 1))[row] if store else None)
         if nz is not None:
             nz.update_filt(raw_next, update=env.training, out=nxt)           # NormObs.observation on env.step's return
         _C.collector_bookkeep(rew, done, env.cur_step, env.ep_return,
                               self.max_episode_frames if max_frames is None else max_frames, self._mask,
                               self._epoch_reward, self._ep_count, self._ep_log, self.global_step - self._log_step0)
         self._env_reset_masked(env, nxt if (store and nz is None) else None)
+        if boot and store:
+            # an env plays one head per episode (the reference's start_episode): fresh heads where an episode just ended
+            self.pf.sample_head(self._mask, counter=self.global_step, env_offset=int(getattr(env, "index_offset", 0)))
         if store:
             buf._advance()
         self.global_step += 1
@@ -610,6 +636,7 @@ class VecCollector(_CollectorBase):
             env._obs_normalizer = copy.deepcopy(self.env._obs_normalizer)
         env.eval()
         rews, lens = [], []
+        step0 = self.global_step
         for _ in range(self.eval_episodes):
             ob = env.reset()
             self._clear_header()
@@ -623,6 +650,10 @@ class VecCollector(_CollectorBase):
                 first.setdefault(int(idx), (ret, int(step) + 1))   # steps are logged relative to the clear
             rews += [np.float32(first[i][0]) for i in sorted(first)]
             lens += [first[i][1] for i in sorted(first)]
+        if hasattr(self.pf, "head_num"):
+            # Bootstrapped DQN keys its mask and head draws by the training step count: evaluation steps must not shift
+            # them (the same data is collected whatever the eval interval); the next rollout re-bases the episode log
+            self.global_step = self._log_step0 = step0
         return {"eval_rewards": rews, "eval_traj_length": float(np.mean(lens)) if lens else 0.0}
 
 

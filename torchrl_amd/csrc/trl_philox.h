@@ -9,6 +9,11 @@
 #define TRL_TAG_NOISE 0x4E4F4953u
 #define TRL_TAG_CATEGORICAL 0x43415447u   // one uniform per (seed, step counter, global env index): trl_cat_uniform
 
+// Bootstrapped DQN (k_bootdqn.hip): one word per (seed, step counter, global env index) for the head an env plays, one per
+// (seed, step counter, (global env index) K + k) for the Bernoulli mask of head k
+#define TRL_TAG_BOOT_HEAD 0x42484541u     // "BHEA"
+#define TRL_TAG_BOOT_MASK 0x424D534Bu     // "BMSK"
+
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t out[4]) {
 #pragma unroll

@@ -12,6 +12,9 @@ layer by layer on the dense-layer kernels, `add_ln=True` ones with their
 LayerNorm layers on k_layernorm.hip in between (ops.net_plan).  With autograd
 enabled (algorithms outside this repo's hot-path scope) it is the plain
 nn.Module graph.
+
+`BootstrappedNet` / `FlattenBootstrappedNet` (nets.py:71-127): K heads on one MLP trunk for Bootstrapped DQN; on the
+GPU the trunk runs once and the requested heads as grouped launches into one head-major stack.
 """
 import torch
 import torch.nn as nn
@@ -186,6 +189,101 @@ class QNet(Net):
         assert len(input) == 2, "Q Net only get observation and action"
         state, action = input
         return super().forward(torch.cat([state, action], dim=-1))
+
+
+class BootstrappedNet(nn.Module):
+    """K Q heads on one trunk (torchrl/networks/nets.py:71-121, Bootstrapped DQN).  Module names, construction order
+    (trunk, then heads 0..K-1, hidden layers before the last layer inside a head) and initialisation are the
+    reference's, so state dicts interchange and a seeded construction gives the same parameters: `base.*`, then
+    `head{k}` = nn.Sequential([Linear, act] * len(append_hidden_shapes) + [Linear]).
+
+    `forward(x, head_idxs)` returns the list of the requested heads' (..., A) outputs.  On the GPU under no_grad the trunk
+    runs ONCE on the dense-layer kernels and all requested heads as one grouped launch per head level, written into one
+    head-major (len(head_idxs), rows, A) stack (`forward_stack`) whose blocks are the returned tensors.
+
+    Limits (each a loud _C.TrlError): MLP trunks only (a CNNBase trunk, the reference's Atari config, is not built), no
+    LayerNorm (`add_ln=True`), 1 <= head_num <= 64 and 1 <= output_shape <= 64 (the sizes k_bootdqn.hip carries)."""
+
+    def __init__(self, output_shape, base_type, head_num=10, append_hidden_shapes=[],
+                 append_hidden_init_func=init.basic_init, net_last_init_func=init.uniform_init,
+                 activation_func=nn.ReLU, add_ln=False, **kwargs):
+        super().__init__()
+        import functools
+        trunk_cls = base_type.func if isinstance(base_type, functools.partial) else base_type
+        if not (isinstance(trunk_cls, type) and issubclass(trunk_cls, MLPBase)):
+            raise _C.TrlError("BootstrappedNet over a %s trunk is not built: the Bootstrapped DQN path runs MLP trunks "
+                              "(networks.MLPBase) only, conv trunks are outside it" % getattr(trunk_cls, "__name__", trunk_cls))
+        if add_ln:
+            raise _C.TrlError("BootstrappedNet(add_ln=True) is not built: the grouped head launches carry no LayerNorm")
+        if not 1 <= int(head_num) <= 64:
+            raise _C.TrlError("BootstrappedNet: the Bootstrapped DQN kernels carry 1..64 heads, got head_num=%s" % (head_num,))
+        if not 1 <= int(output_shape) <= 64:
+            raise _C.TrlError("BootstrappedNet: the Bootstrapped DQN kernels carry 1..64 actions, got output_shape=%s"
+                              % (output_shape,))
+        self.base = base_type(activation_func=activation_func, add_ln=add_ln, **kwargs)
+        self.add_ln = add_ln
+        self.activation_func = activation_func
+        self.head_num = int(head_num)
+        self.out_dim = int(output_shape)
+        self.bootstrapped_heads = []
+        for idx in range(self.head_num):
+            width = self.base.output_shape
+            layers = []
+            for nxt in append_hidden_shapes:
+                fc = nn.Linear(width, nxt)
+                append_hidden_init_func(fc)
+                layers += [fc, activation_func()]
+                width = nxt
+            last = nn.Linear(width, output_shape)
+            net_last_init_func(last)
+            layers.append(last)
+            head = nn.Sequential(*layers)
+            setattr(self, "head{}".format(idx), head)
+            self.bootstrapped_heads.append(head)
+
+    def trunk_layers(self):
+        return [(m.weight, m.bias) for m in self.base.seq_fcs if isinstance(m, nn.Linear)]
+
+    def head_layers(self, idx):
+        return [(m.weight, m.bias) for m in self.bootstrapped_heads[idx] if isinstance(m, nn.Linear)]
+
+    def param_list(self):
+        """Trunk, then heads 0..K-1: W, b per layer -- the order of the engine's flat buffer (and of `parameters()`)."""
+        out = []
+        for w, b in self.trunk_layers() + [wb for k in range(self.head_num) for wb in self.head_layers(k)]:
+            out += [w, b]
+        return out
+
+    def forward_stack(self, x, head_idxs=None):
+        """The heads' Q values as one head-major (len(head_idxs), rows, A) stack, on the kernels (no autograd):
+        one trunk pass, one grouped launch per head level."""
+        from .. import ops
+        idxs = list(range(self.head_num)) if head_idxs is None else [int(i) for i in head_idxs]
+        if not idxs or any(not 0 <= i < self.head_num for i in idxs):
+            raise _C.TrlError("BootstrappedNet: head indices must lie in [0, %d), got %s" % (self.head_num, idxs))
+        act = ops.act_code(self)
+        trunk = [(w.detach(), b.detach()) for w, b in self.trunk_layers()]
+        x2 = x.reshape(-1, int(trunk[0][0].shape[1])).float().contiguous()
+        feat, _ = ops.mlp_forward(trunk, x2, act, last_act=act, keep=False)
+        stack = torch.empty((len(idxs), int(x2.shape[0]), self.out_dim), dtype=torch.float32, device=x.device)
+        heads = [[(w.detach(), b.detach()) for w, b in self.head_layers(i)] for i in idxs]
+        ops.mlp_forward_group(heads, [feat] * len(idxs), act, keep=[False] * len(idxs), out=list(stack.unbind(0)))
+        return stack
+
+    def forward(self, x, head_idxs):
+        needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if x.is_cuda and not needs_graph:
+            lead = tuple(x.shape[:-1])
+            return [q.reshape(lead + (self.out_dim,)) for q in self.forward_stack(x, head_idxs).unbind(0)]
+        if x.is_cuda:
+            _C.note_eager(type(self).__name__ + ".forward", "autograd is on")
+        feature = self.base(x)
+        return [self.bootstrapped_heads[idx](feature) for idx in head_idxs]
+
+
+class FlattenBootstrappedNet(BootstrappedNet):
+    def forward(self, input, head_idxs):
+        return super().forward(torch.cat(input, dim=-1), head_idxs)
 
 
 class ZeroNet(nn.Module):

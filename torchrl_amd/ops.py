@@ -210,15 +210,17 @@ def mlp_backward(tape, d_out, grads=None, need_input=False, workspace=None, plan
     return d if need_input else None
 
 
-def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None):
+def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None, out=None):
     """G same-shaped MLPs (or one MLP listed several times) on G inputs, one launch per layer instead of G:
     returns ([out_g], [tape_g]); every tape works with `mlp_backward` / `mlp_backward_group`.
     keep[g] = False: network g's hidden activations are not needed (no backward pass, e.g. target networks); networks
-    of the shape D -> 256 -> 256 -> O then run through ONE fused launch that leaves their hidden layers on chip."""
+    of the shape D -> 256 -> 256 -> O then run through ONE fused launch that leaves their hidden layers on chip.
+    out: the G tensors the LAST layer writes (the blocks of one (G, M, O) stack, Bootstrapped DQN's heads); the layers
+    then run one grouped launch each."""
     G = len(layers_list)
     code_last = _C.ACT_NONE if last_act is None else last_act
     ls0 = layers_list[0]
-    if len(ls0) == 3 and _C.mlp3_forward_ok(ls0[0][0].shape[1], ls0[0][0].shape[0], ls0[1][0].shape[0], ls0[2][0].shape[0]) and \
+    if out is None and len(ls0) == 3 and _C.mlp3_forward_ok(ls0[0][0].shape[1], ls0[0][0].shape[0], ls0[1][0].shape[0], ls0[2][0].shape[0]) and \
             all(b is not None for ls in layers_list for _, b in ls[:2]):
         keep = [True] * G if keep is None else list(keep)
         res = _C.mlp3_forward_group(layers_list, xs, act, code_last, keep)
@@ -240,7 +242,8 @@ def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None):
     n = len(layers_list[0])
     for k in range(n):
         code = tapes[0].last_act if k == n - 1 else act
-        hs = _C.linear_fwd_group(hs, [ls[k][0] for ls in layers_list], [ls[k][1] for ls in layers_list], code)
+        hs = _C.linear_fwd_group(hs, [ls[k][0] for ls in layers_list], [ls[k][1] for ls in layers_list], code,
+                                 ys=out if k == n - 1 else None)
         for t, h in zip(tapes, hs):
             t.outs.append(h)
     return hs, tapes

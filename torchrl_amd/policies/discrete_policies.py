@@ -7,6 +7,9 @@ seeded runs replay the reference's exploration decisions) -- but the Q network r
 dense HIP kernels and the argmax + mask is one kernel (trl_eps_greedy_i64).  Unlike the
 reference's QR-DQN policy (single env, `.item()`, its Q16) both policies are vectorised over N
 envs; actions are returned as (N, 1) int64.
+
+`BootstrappedDQNDiscretePolicy` (:92-121): every env plays one of K heads (trl_boot_act_i64 behind one shared trunk pass),
+evaluation takes the ensemble vote; heads are device Philox draws (trl_boot_heads_i64), not host numpy draws.
 """
 import numpy as np
 import torch
@@ -94,6 +97,90 @@ class EpsilonGreedyQRDQNDiscretePolicy(EpsilonGreedyDQNDiscretePolicy):
     def __init__(self, quantile_num, **kwargs):
         super().__init__(**kwargs)
         self.quantile_num = quantile_num
+
+
+class BootstrappedDQNDiscretePolicy:
+    """Wrapper over a `networks.BootstrappedNet` (torchrl/policies/discrete_policies.py:92-121), vectorised over N envs:
+    the reference plays ONE env with `.item()` and a host `np.random.randint` head; here every env plays a head of its own.
+
+    `idx` is an (N,) int64 device tensor -- allocated at the first `explore` for N envs and drawn for all of them --
+    `explore` returns each env's arg-max under its head ((N, 1) int64) with that head's Q row, `eval_act` the arg-max of
+    the ensemble vote (the reference's `eval_act` on a (1, D) input).  All K heads share one trunk pass; the selection is
+    one launch (trl_boot_act_i64).  Heads are Philox draws of (`seed`, counter, global env index) (trl_boot_heads_i64), not
+    host numpy draws: those would interleave with the replay index stream, and the reference has no vector-env
+    behaviour to match.  `bernoulli_p` is set by the algorithm (the collector draws the masks with it)."""
+    seed = 0xB007D
+    bernoulli_p = 0.5
+
+    def __init__(self, qf, head_num, action_shape):
+        if not 1 <= int(head_num) <= 64 or not 1 <= int(action_shape) <= 64:
+            raise _C.TrlError("BootstrappedDQNDiscretePolicy: the kernels carry 1..64 heads and 1..64 actions, got "
+                              "head_num=%s, action_shape=%s" % (head_num, action_shape))
+        self.qf = qf
+        self.head_num = int(head_num)
+        self.action_shape = action_shape
+        self.idx = None
+        self._pending_head = None
+        self.continuous = False
+
+    def _ensure_idx(self, n, device):
+        if self.idx is None or int(self.idx.numel()) != n or self.idx.device != device:
+            self.idx = torch.zeros(n, dtype=torch.int64, device=device)
+            self.sample_head(counter=-1)                             # (the draw "before step 0": steps count from 0)
+
+    def sample_head(self, mask=None, counter=0, env_offset=0):
+        """Fresh heads where `mask` (N bytes) is set, everywhere when it is None: the Philox word of
+        (seed, counter, env_offset + n) scaled to [0, K)."""
+        if self.idx is None:
+            return                                                   # (no envs seen yet: the first explore draws)
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=self.idx.device, dtype=torch.uint8).reshape(-1).contiguous()
+        _C.boot_heads(self.idx, self.head_num, self.seed, counter, env_offset, mask)
+
+    def set_head(self, idx):
+        """One head for every env (an int; before the envs are known it is applied at the first explore), or an (N,) tensor."""
+        if isinstance(idx, torch.Tensor):
+            dev = next(self.qf.parameters()).device
+            self.idx = idx.to(device=dev, dtype=torch.int64).reshape(-1).contiguous().clone()
+        elif self.idx is None:
+            self._pending_head = int(idx)
+        else:
+            self.idx.fill_(int(idx))
+
+    def _rows(self, x):
+        if x.dim() == 3 and x.shape[0] == 1:                         # the collector's unsqueeze(0)
+            x = x.squeeze(0)
+        return x.reshape(-1, x.shape[-1])
+
+    def act_on(self, x, greedy_vote=False, want_q=True, onehot=None):
+        """(q_sel or None, action (N,) int64) for a batch of observations: under each env's head, or the ensemble vote."""
+        x = self._rows(x)
+        if not x.is_cuda:
+            raise _C.TrlError("BootstrappedDQNDiscretePolicy: observations live on %s, the HIP path needs a GPU" % x.device)
+        n = int(x.shape[0])
+        if not greedy_vote:
+            had = self.idx is not None and int(self.idx.numel()) == n and self.idx.device == x.device
+            self._ensure_idx(n, x.device)
+            if not had and getattr(self, "_pending_head", None) is not None:
+                self.idx.fill_(self._pending_head)
+            self._pending_head = None
+        with torch.no_grad():
+            stack = self.qf.forward_stack(x)
+        act, q = _C.boot_act(stack, None if greedy_vote else self.idx, want_q=want_q, onehot=onehot)
+        return q, act
+
+    def explore(self, x):
+        q, act = self.act_on(x)
+        return {"q_value": q, "action": act.unsqueeze(-1)}
+
+    def eval_act(self, x):
+        return self.act_on(x, greedy_vote=True, want_q=False)[1].unsqueeze(-1).cpu().numpy()
+
+    def to(self, device):
+        self.qf.to(device)
+
+    def parameters(self):
+        return self.qf.parameters()
 
 
 class CategoricalDisPolicy(networks.Net):
