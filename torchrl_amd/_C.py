@@ -105,6 +105,20 @@ class AdamArgs(C.Structure):
     ]
 
 
+def adam_args(flat, grads, m, v, sizes, lrs, *, offset=0, max_norm=0.0, eps=1e-8, grad_scale=1.0, norms_out=None,
+              step_state=None, step_count=0):
+    """AdamArgs (beta 0.9 / 0.999) for the `sizes` groups that start `offset` elements into the four flat buffers;
+    `norms_out` and `step_state` (where the step count lives on the device) are addresses."""
+    a = AdamArgs()
+    a.params, a.grads, a.exp_avg, a.exp_avg_sq = (t.data_ptr() + int(offset) * t.element_size() for t in (flat, grads, m, v))
+    a.n_groups = len(sizes)
+    for k, (size, lr) in enumerate(zip(sizes, lrs)):
+        a.group_sizes[k], a.group_lr[k] = size, lr
+    a.max_norm, a.beta1, a.beta2, a.eps = max_norm, 0.9, 0.999, eps
+    a.step_count, a.grad_scale, a.norms_out, a.step_state = step_count, grad_scale, norms_out, step_state
+    return a
+
+
 class ConvRiders(C.Structure):          # include/trl_hip.h trl_conv_riders_t
     _fields_ = [("n_perm", C.c_int), ("perm_src", C.c_void_p * 4), ("perm_dst", C.c_void_p * 4), ("perm_cout", C.c_int * 4),
                 ("perm_c", C.c_int * 4), ("perm_khw", C.c_int * 4), ("n_dx", C.c_int), ("dx_w", C.c_void_p * 4),

@@ -1,0 +1,161 @@
+"""The host-side plumbing every fused off-policy engine shares (none of it is kernel code, all of it runs on CPU tensors):
+the eager -> captured -> replayed rule, the networks' home in one flat buffer, the copy of a sampled batch into the
+fixed-address inputs, the whole-epoch builder, and what an algorithm forwards to its engine."""
+import os
+from collections.abc import Mapping
+
+import numpy as np
+import torch
+
+from ... import _C, dist
+from ...networks import flatten_into
+
+
+class GraphCache(Mapping):
+    """Captured HIP graphs by key, at most `cap` of them and none ever evicted (a learning-rate schedule would mint a key
+    per value).  A launch sequence runs eagerly on the first visit of its key, is captured on the second and replayed
+    afterwards: the host then issues one call per update instead of ~45-90 and stays ahead of the device."""
+
+    def __init__(self, cap):
+        self.cap, self._graphs, self._seen = cap, {}, set()
+
+    def __getitem__(self, key):
+        return self._graphs[key]
+
+    def __iter__(self):
+        return iter(self._graphs)
+
+    def __len__(self):
+        return len(self._graphs)
+
+    def clear(self):
+        self._graphs.clear()
+        self._seen.clear()
+
+    def has_room(self, key):
+        return key in self._graphs or len(self._graphs) < self.cap
+
+    def run(self, key, launches):
+        graph = self._graphs.get(key)
+        if os.environ.get("TRL_NO_GRAPH") == "1" or dist.collectives_active() or \
+                (graph is None and len(self._graphs) >= self.cap):
+            launches()                                                   # eager, and the key stays unseen
+        elif graph is not None:
+            graph.replay()
+        elif key not in self._seen:
+            self._seen.add(key)
+            launches()
+        else:
+            self._graphs[key], _ = _C.capture_graph(launches)
+            self._graphs[key].replay()
+
+
+class FlatHome:
+    """`plists` (one parameter list per network, W and b alternating) back to back in one buffer `flat`, the parameters
+    views of it; `grads`, `m`, `v` beside it, with `views` the per-parameter gradient views and every
+    `optimizer.state[p]` bound to its slices of the moments.  `targets`: the target networks' parameters, homed in `tflat`
+    (allocated right behind `flat`, where it has always been).  `keep=(m, v)`: moments of an earlier home, reused when
+    the size still matches."""
+
+    def __init__(self, plists, optimizers, targets, keep=None):
+        self.sizes = [sum(p.numel() for p in pl) for pl in plists]
+        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(int)
+        self.flat, self.tflat = flatten_into([p for pl in plists for p in pl]), flatten_into(targets)
+        self.grads = torch.zeros_like(self.flat)
+        if keep is not None and keep[0].numel() == self.flat.numel():
+            self.m, self.v = keep[0].to(self.flat.device), keep[1].to(self.flat.device)
+        else:
+            self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.views, self._counts, off = [], [len(pl) for pl in plists], 0
+        for opt, pl in zip(optimizers, plists):
+            for p in pl:
+                n = p.numel()
+                self.views.append(self.grads[off:off + n].view(p.shape))
+                opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
+                                "exp_avg_sq": self.v[off:off + n].view(p.shape)}
+                off += n
+
+    def pairs(self):
+        """The gradient views as (gW, gb) pairs: one list per parameter list."""
+        firsts = np.concatenate([[0], np.cumsum(self._counts)])
+        return [[(self.views[i], self.views[i + 1]) for i in range(f, f + n, 2)] for f, n in zip(firsts, self._counts)]
+
+
+def load_static(st, batch, keys):
+    """Copy the sampled `batch` into the fixed-address inputs `st` (a replay gather that wrote there already is skipped)."""
+    for k in keys:
+        src = batch[k]
+        if src is st[k]:
+            continue
+        src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
+        st[k].copy_(src.to(dtype=st[k].dtype).reshape(st[k].shape), non_blocking=True)
+
+
+class _FusedOffPolicy:
+    """What the engines with a whole-epoch path share.  Theirs: `_graphs`, `_ring`, `_slab`, `step_count`, `step_state`,
+    `static_batch(B)`, `_sequence(st, soft)`, `_handles(count, B)`, `_epoch_declined(count)`, `_epoch_key(soft)`."""
+    KEYS = ("obs", "next_obs", "acts", "rewards", "terminals")           # the sampled keys = the static input tensors
+
+    def update(self, batch):
+        return self.resolve([self.enqueue(batch)])[0]
+
+    def enqueue_epoch(self, count):
+        """`count` x {uniform replay sample -> update} as ONE graph launch: the index sets are drawn on the host in the
+        order `count` random_batch calls would draw them and uploaded once; every update of the graph gathers the set the
+        device-resident update count selects (trl_gather_rows_multi with its update counter) and files its statistics
+        into its ring slot.  Returns the handles, or None when this path does not apply: TRL_NO_GRAPH=1, several ranks, a
+        replay buffer that does not store the sampled keys plainly, a full graph cache, the engine's own conditions."""
+        algo = self.algo
+        buf, B = getattr(algo, "replay_buffer", None), int(algo.batch_size)
+        if buf is None or count < 1 or count > self._ring.slots or dist.collectives_active() or \
+                os.environ.get("TRL_NO_GRAPH") == "1" or not hasattr(buf, "gather_sources") or self._epoch_declined(count):
+            return None
+        keys, soft = self.KEYS, bool(algo.use_soft_update)
+        srcs = buf.gather_sources(keys)
+        if srcs is None:
+            return None
+        st, nrows = self.static_batch(B), buf._rows_per_batch(B)
+        if any(s.dtype != st[k].dtype or s[0].numel() * nrows != st[k].numel() for s, k in zip(srcs, keys)):
+            return None
+        key = ("epoch", count, B, nrows, tuple(s.data_ptr() for s in srcs)) + self._epoch_key(soft)
+        if not self._graphs.has_room(key):                               # before anything below consumes the host's
+            return None                                                  # random stream or touches the ring
+        self._ring.make_room(count)
+        slab = self._slab.upload(self.step_count, buf.draw_indices(B, count))
+        dsts = [st[k] for k in keys]
+
+        def launches():
+            for _ in range(count):
+                _C.gather_rows_multi(srcs, slab, dsts, slab_counter=self.step_state, n_rows=nrows)
+                self._sequence(st, soft)
+        self._graphs.run(key, launches)
+        self.step_count += count
+        return self._handles(count, B)
+
+
+class _EngineSurface:
+    """What an algorithm offers over its fused engine (`engine()`): `update` and its deferred forms, `static_batch`."""
+
+    def static_batch(self):
+        return self.engine().static_batch(self.batch_size)
+
+    def update(self, batch):
+        self.training_update_num += 1
+        return self.engine().update(batch)
+
+    def update_deferred(self, batch):
+        """`update` without its read-back: OffRLAlgo.update_per_epoch enqueues all `opt_times` updates of an epoch and
+        resolves their info dicts with one D2H (`resolve_updates`)."""
+        self.training_update_num += 1
+        return self.engine().enqueue(batch)
+
+    def update_epoch_deferred(self, count):
+        """All `count` {uniform sample -> update} pairs of an epoch as one replayed graph (None when the engine's
+        conditions for it do not hold: the caller then samples and enqueues one by one)."""
+        handles = self.engine().enqueue_epoch(count)
+        if handles is not None:
+            self.training_update_num += count
+        return handles
+
+    def resolve_updates(self, handles):
+        return self.engine().resolve(handles)

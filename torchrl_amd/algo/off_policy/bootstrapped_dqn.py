@@ -19,7 +19,7 @@ import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
-from ...networks import flatten_into
+from ._engine import FlatHome
 from .dqn import DQN, _FusedDQN
 
 
@@ -84,25 +84,14 @@ class _FusedBootDQN(_FusedDQN):
         self.heads = [qf.head_layers(k) for k in range(K)]
         self.theads = [tqf.head_layers(k) for k in range(K)]
         plist, tlist = qf.param_list(), tqf.param_list()
-        self.flat, self.tflat = flatten_into(plist), flatten_into(tlist)
-        old_m, old_v = getattr(self, "m", None), getattr(self, "v", None)
-        self.grads = torch.zeros_like(self.flat)
-        keep = old_m is not None and old_m.numel() == self.flat.numel()
-        self.m = old_m.to(self.dev) if keep else torch.zeros_like(self.flat)
-        self.v = old_v.to(self.dev) if keep else torch.zeros_like(self.flat)
-        views, off = [], 0
-        for p in plist:
-            n = p.numel()
-            views.append(self.grads[off:off + n].view(p.shape))
-            algo.qf_optimizer.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
-                                          "exp_avg_sq": self.v[off:off + n].view(p.shape)}
-            off += n
-        pairs = [(views[i], views[i + 1]) for i in range(0, len(views), 2)]
+        home = FlatHome([plist], [algo.qf_optimizer], tlist, keep=(self.m, self.v) if hasattr(self, "m") else None)
+        self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
+        pairs = home.pairs()[0]
         nt, nh = len(self.trunk), len(self.heads[0])
         self.trunk_gviews = pairs[:nt]
         self.head_gviews = [pairs[nt + k * nh:nt + (k + 1) * nh] for k in range(K)]
         self._homed = (plist[0].data_ptr(), plist[-1].data_ptr(), tlist[0].data_ptr(), tlist[-1].data_ptr())
-        self._graphs, self._seen = {}, set()
+        self._graphs.clear()                                             # (they carry the old addresses)
 
     def _check_home(self):
         """A `.to()` or an assignment that replaced parameter storage (a checkpoint load copies in place and needs nothing):
@@ -159,17 +148,4 @@ class _FusedBootDQN(_FusedDQN):
                                input_sink=sink)
         dfeat = _C.boot_fold(dfeat_k)
         ops.mlp_backward(trunk_tape, dfeat, grads=self.trunk_gviews, workspace=self.workspace)
-        a = _C.AdamArgs()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                      self.m.data_ptr(), self.v.data_ptr())
-        a.n_groups = 1
-        a.group_sizes[0] = self.flat.numel()
-        a.group_lr[0] = algo.qf_optimizer.param_groups[0]['lr']
-        a.max_norm, a.beta1, a.beta2 = 0.0, 0.9, 0.999
-        a.eps = float(algo.optimizer_info.get("eps", 1e-8))
-        a.grad_scale, a.norms_out = 1.0, None
-        a.step_count, a.step_state = 0, self.step_state.data_ptr()       # the step count lives on the device
-        if soft:                                                         # Adam, then Polyak (which also advances the step state)
-            _C.clip_adam_polyak(a, self.tflat, self.flat, algo.tau, dev)
-        else:
-            _C.clip_adam(a, dev)
+        self._adam_polyak(soft, 1.0)

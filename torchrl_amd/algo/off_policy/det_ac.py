@@ -15,15 +15,13 @@ TD3's two N(0,1) draws per update come from the CPU torch generator (reference p
 Philox stream (`noise_mode="device"`).
 """
 import copy
-import os
 
-import numpy as np
 import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
-from ...networks import flatten_into
 from ._deferred import StatRing
+from ._engine import FlatHome, GraphCache, load_static
 from .off_rl_algo import OffRLAlgo
 
 
@@ -145,27 +143,9 @@ class _FusedDetAC:
         self.layers = [ops.linear_layers(n) for n in nets]
         self.tlayers = [ops.linear_layers(n) for n in targets]
         plists = [[t for wb in ls for t in wb] for ls in self.layers]
-        self.sizes = [sum(p.numel() for p in pl) for pl in plists]
-        self.flat = flatten_into([p for pl in plists for p in pl])
-        self.tflat = flatten_into([t for ls in self.tlayers for wb in ls for t in wb])
-        self.grads = torch.zeros_like(self.flat)
-        self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.gviews, off = [], 0
-        for ls in self.layers:
-            views = []
-            for w, b in ls:
-                gw = self.grads[off:off + w.numel()].view(w.shape); off += w.numel()
-                gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
-                views.append((gw, gb))
-            self.gviews.append(views)
-        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(int)
-        off = 0
-        for opt, pl in zip(optimizers, plists):
-            for p in pl:
-                n = p.numel()
-                opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
-                                "exp_avg_sq": self.v[off:off + n].view(p.shape)}
-                off += n
+        home = FlatHome(plists, optimizers, [t for ls in self.tlayers for wb in ls for t in wb])
+        self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
+        self.sizes, self.offsets, self.gviews = home.sizes, home.offsets, home.pairs()
         self.optimizers = optimizers
         self.steps = [0] * len(nets)                                       # per-network Adam step counts (TD3's policy lags)
         self._raw = torch.zeros(96 + 16, dtype=torch.uint8, device=self.dev)   # every logged statistic: one D2H per update
@@ -175,7 +155,7 @@ class _FusedDetAC:
         self.norms = self._raw[96:96 + 4 * len(nets)].view(torch.float32)
         # per-network Adam step state on the device {steps, beta1^steps, beta2^steps, 0}: a captured graph replays unchanged
         self.step_state = torch.tensor([[0.0, 1.0, 1.0, 0.0]] * len(nets), dtype=torch.float64, device=self.dev)
-        self._static, self._graphs, self._seen = {}, {}, set()
+        self._static, self._graphs = {}, GraphCache(8)
         self.workspace = None
         self.D = int(self.layers[0][0][0].shape[1])
         self.A = int(self.layers[0][-1][0].shape[0])
@@ -202,12 +182,7 @@ class _FusedDetAC:
     def _load(self, batch, noise_keys):
         B = int(batch['obs'].shape[0])
         st = self.static_batch(B)
-        for k in ("obs", "next_obs", "acts", "rewards", "terminals"):
-            src = batch[k]
-            if src is st[k]:
-                continue
-            src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
-            st[k].copy_(src.to(dtype=torch.float32).reshape(st[k].shape), non_blocking=True)
+        load_static(st, batch, ("obs", "next_obs", "acts", "rewards", "terminals"))
         buf = getattr(self.algo, "replay_buffer", None)
         n_env = int(buf.env_nums) if buf is not None and B % int(buf.env_nums) == 0 else B
         for k in noise_keys:                                               # this rank's block of the draw for all envs
@@ -223,22 +198,9 @@ class _FusedDetAC:
         return tuple(float(o.param_groups[0]['lr']) for o in self.optimizers)
 
     def _run(self, key, seq):
-        """Eager on the first visit of a configuration, captured into a HIP graph on the second, replayed afterwards
-        (TRL_NO_GRAPH=1 keeps everything eager)."""
+        """`seq` through the graph cache, under `key` and everything else a captured sequence has baked in."""
         algo = self.algo
-        key = key + (self._lrs(), algo.grad_clip, algo.tau, algo.discount)
-        if os.environ.get("TRL_NO_GRAPH") == "1" or dist.collectives_active() or \
-                (key not in self._graphs and len(self._graphs) >= 8):
-            seq()                                                            # (a learning-rate schedule would mint a key per value)
-        elif key in self._graphs:
-            self._graphs[key].replay()
-        elif key not in self._seen:
-            self._seen.add(key)
-            seq()
-        else:
-            graph, _ = _C.capture_graph(seq)
-            self._graphs[key] = graph
-            graph.replay()
+        self._graphs.run(key + (self._lrs(), algo.grad_clip, algo.tau, algo.discount), seq)
 
     def _adam(self, which):
         """clip_grad_norm_ + Adam for the networks in `which` (indices into the flat buffer), one launch each;
@@ -246,17 +208,10 @@ class _FusedDetAC:
         algo = self.algo
         for k in which:
             dist.all_reduce_sum_(self.grads[int(self.offsets[k]):int(self.offsets[k + 1])])   # C1: local means -> SUM / world
-            a = _C.AdamArgs()
-            o = int(self.offsets[k]) * 4
-            a.params, a.grads = self.flat.data_ptr() + o, self.grads.data_ptr() + o
-            a.exp_avg, a.exp_avg_sq = self.m.data_ptr() + o, self.v.data_ptr() + o
-            a.n_groups = 1
-            a.group_sizes[0] = self.sizes[k]
-            a.group_lr[0] = self.optimizers[k].param_groups[0]['lr']
-            a.max_norm = float(algo.grad_clip) if algo.grad_clip else 0.0
-            a.beta1, a.beta2, a.eps, a.grad_scale = 0.9, 0.999, 1e-8, 1.0 / dist.world_size()
-            a.step_count, a.norms_out = 0, self.norms.data_ptr() + 4 * k
-            a.step_state = self.step_state.data_ptr() + 32 * k
+            a = _C.adam_args(self.flat, self.grads, self.m, self.v, [self.sizes[k]], [self.optimizers[k].param_groups[0]['lr']],
+                             offset=self.offsets[k], max_norm=float(algo.grad_clip) if algo.grad_clip else 0.0,
+                             grad_scale=1.0 / dist.world_size(), norms_out=self.norms.data_ptr() + 4 * k,
+                             step_state=self.step_state.data_ptr() + 32 * k)
             _C.clip_adam(a, self.dev)
 
     def _hard_update_due(self):

@@ -8,19 +8,18 @@ Actions are read as (B,) or (B, 1) floats as the replay buffer stores them and c
 loss launch (the reference's two classes disagree on the shape, its Q16).
 """
 import copy
-import os
 
 import numpy as np
 import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
-from ...networks import flatten_into
 from ._deferred import IndexSlab, StatRing
+from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static
 from .off_rl_algo import OffRLAlgo
 
 
-class DQN(OffRLAlgo):
+class DQN(_EngineSurface, OffRLAlgo):
     quantile_num = 1
 
     def __init__(self, qf, pf, qlr, optimizer_class=optim.Adam, optimizer_info={}, **kwargs):
@@ -54,28 +53,6 @@ class DQN(OffRLAlgo):
             self._engine = _FusedDQN(self)
         return self._engine
 
-    def update(self, batch):
-        self.training_update_num += 1
-        return self.engine().update(batch)
-
-    def static_batch(self):
-        return self.engine().static_batch()
-
-    def update_deferred(self, batch):
-        """`update` without its read-back (see OffRLAlgo.update_per_epoch): returns a handle for `resolve_updates`."""
-        self.training_update_num += 1
-        return self.engine().enqueue(batch)
-
-    def update_epoch_deferred(self, count):
-        """All `count` {uniform sample -> update} pairs of an epoch as one replayed graph, or None (one by one then)."""
-        handles = self.engine().enqueue_epoch(count)
-        if handles is not None:
-            self.training_update_num += count
-        return handles
-
-    def resolve_updates(self, handles):
-        return self.engine().resolve(handles)
-
 
 class QRDQN(DQN):
     def __init__(self, quantile_num=100, **kwargs):
@@ -83,9 +60,7 @@ class QRDQN(DQN):
         self.quantile_num = quantile_num
 
 
-class _FusedDQN:
-    KEYS = ("obs", "next_obs", "acts", "rewards", "terminals")       # the sampled keys = the static input tensors
-
+class _FusedDQN(_FusedOffPolicy):
     def __init__(self, algo):
         self.algo = algo
         self.dev = next(algo.qf.parameters()).device
@@ -100,22 +75,9 @@ class _FusedDQN:
             tlist = [t for wb in self.tlayers for t in wb]
         else:
             plist, tlist = ops.cnn_param_list(algo.qf), ops.cnn_param_list(algo.target_qf)
-        self.flat = flatten_into(plist)
-        self.tflat = flatten_into(tlist)
-        self.grads = torch.zeros_like(self.flat)
-        self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.gviews, off = [], 0
-        for k in range(0, len(plist), 2):
-            w, b = plist[k], plist[k + 1]
-            gw = self.grads[off:off + w.numel()].view(w.shape); off += w.numel()
-            gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
-            self.gviews.append((gw, gb))
-        off = 0
-        for p in plist:
-            n = p.numel()
-            algo.qf_optimizer.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
-                                          "exp_avg_sq": self.v[off:off + n].view(p.shape)}
-            off += n
+        home = FlatHome([plist], [algo.qf_optimizer], tlist)
+        self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
+        self.gviews = home.pairs()[0]
         self.A = int(algo.env.action_space.n)
         self._init_run_state()
 
@@ -129,12 +91,9 @@ class _FusedDQN:
         # update u's three sums are filed into ring row u % slots by its loss launch (one rank), or copied there
         self._ring = StatRing(max(64, int(getattr(algo, "opt_times", 1))), 3, torch.float64, self.dev)
         self._slab = IndexSlab(self.dev)
-        self._static, self._graphs, self._seen = None, {}, set()
+        self._static, self._graphs = None, GraphCache(4)
         self.step_state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
         self._head_ws = None                                            # workspace of the one-launch head (conv nets, Q = 1)
-
-    def update(self, batch):
-        return self.resolve([self.enqueue(batch)])[0]
 
     def resolve(self, handles):
         """Info dicts of enqueued updates, in order, after one D2H per ring of loss sums (the only host sync)."""
@@ -142,9 +101,9 @@ class _FusedDQN:
         return [{'Reward_Mean': s[2] / B, 'Training/qf_loss': s[0] / denom, 'epsilon': eps, 'q_s_a': s[1] / (B * Q)}
                 for s, (_, _, B, denom, Q, eps) in zip(rows, handles)]
 
-    def static_batch(self):
-        """Fixed-address input tensors of an update (None until the first batch has shown the shapes): the replay gather
-        writes straight into them (`random_batch(..., out=)`) and the captured launch sequence reads them."""
+    def static_batch(self, B=None):
+        """Fixed-address input tensors of an update (None until the first batch has shown the shapes, whatever `B`): the
+        replay gather writes straight into them (`random_batch(..., out=)`) and the captured launch sequence reads them."""
         return self._static
 
     def _load(self, batch):
@@ -161,13 +120,9 @@ class _FusedDQN:
             st = {"obs": torch.zeros(shape, dtype=want, device=dev), "next_obs": torch.zeros(shape, dtype=want, device=dev),
                   "acts": f(B, 1), "rewards": f(B, 1), "terminals": f(B, 1)}
             st.update(self._extra_static(B))
-            self._static, self._graphs, self._seen = st, {}, set()
-        for k in self.KEYS:
-            src = batch[k]
-            if src is st[k]:
-                continue
-            src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
-            st[k].copy_(src.to(device=dev, dtype=st[k].dtype).reshape(st[k].shape), non_blocking=True)
+            self._static = st
+            self._graphs.clear()                                         # (they read the old tensors)
+        load_static(st, batch, self.KEYS)
         return st, B
 
     def _extra_static(self, B):
@@ -217,42 +172,26 @@ class _FusedDQN:
             ops.mlp_backward(tape, dq, grads=self.gviews, workspace=self.workspace)
         else:
             ops.cnn_backward(algo.qf, tape, dq, self.gviews, workspace=self.workspace)
-        a = _C.AdamArgs()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                      self.m.data_ptr(), self.v.data_ptr())
-        a.n_groups = 1
-        a.group_sizes[0] = self.flat.numel()
-        a.group_lr[0] = algo.qf_optimizer.param_groups[0]['lr']
-        a.max_norm, a.beta1, a.beta2 = 0.0, 0.9, 0.999
-        a.eps = float(algo.optimizer_info.get("eps", 1e-8))
         dist.all_reduce_sum_(self.grads)                                 # C1: local-mean gradients -> SUM / world
-        a.grad_scale, a.norms_out = 1.0 / dist.world_size(), None
-        a.step_count, a.step_state = 0, self.step_state.data_ptr()       # the step count lives on the device
-        if soft:                                                         # Adam, then Polyak (which also advances the step state)
-            _C.clip_adam_polyak(a, self.tflat, self.flat, algo.tau, dev)
-        else:
-            _C.clip_adam(a, dev)
+        self._adam_polyak(soft, 1.0 / dist.world_size())
         dist.all_reduce_sum_(self.sums)
 
-    def _run(self, st, soft):
-        """Eager on the first visit of a configuration, captured into a HIP graph on the second, replayed afterwards
-        (TRL_NO_GRAPH=1, or collectives between ranks: eager launches): the host then issues one call per update instead
-        of ~45 and stays ahead of the device."""
+    def _adam_polyak(self, soft, grad_scale):
+        """Adam over the whole flat buffer, then Polyak when `soft` (which also advances the step state)."""
         algo = self.algo
-        key = (int(st["obs"].shape[0]), soft, float(algo.qf_optimizer.param_groups[0]['lr']), float(algo.discount),
-               float(algo.tau), int(algo.quantile_num))
-        if os.environ.get("TRL_NO_GRAPH") == "1" or dist.collectives_active() or \
-                (key not in self._graphs and len(self._graphs) >= 4):
-            self._sequence(st, soft)
-        elif key in self._graphs:
-            self._graphs[key].replay()
-        elif key not in self._seen:
-            self._seen.add(key)
-            self._sequence(st, soft)
+        a = _C.adam_args(self.flat, self.grads, self.m, self.v, [self.flat.numel()], [algo.qf_optimizer.param_groups[0]['lr']],
+                         eps=float(algo.optimizer_info.get("eps", 1e-8)), grad_scale=grad_scale,
+                         step_state=self.step_state.data_ptr())
+        if soft:
+            _C.clip_adam_polyak(a, self.tflat, self.flat, algo.tau, self.dev)
         else:
-            graph, _ = _C.capture_graph(lambda: self._sequence(st, soft))
-            self._graphs[key] = graph
-            graph.replay()
+            _C.clip_adam(a, self.dev)
+
+    def _epoch_key(self, soft):
+        """What a captured launch sequence has baked in, beside its shapes."""
+        algo = self.algo
+        return (soft, float(algo.qf_optimizer.param_groups[0]['lr']), float(algo.discount), float(algo.tau),
+                int(algo.quantile_num))
 
     def enqueue(self, batch):
         """Launch one update without waiting for it; its loss sums wait in their ring row for `resolve`."""
@@ -260,7 +199,7 @@ class _FusedDQN:
         st, B = self._load(batch)
         soft = bool(algo.use_soft_update)
         self._ring.make_room(1)
-        self._run(st, soft)
+        self._graphs.run((B,) + self._epoch_key(soft), lambda: self._sequence(st, soft))
         self.step_count += 1
         if not soft and algo.training_update_num % algo.target_hard_update_period == 0:
             _C.polyak(self.tflat, self.flat, 1.0)
@@ -276,44 +215,9 @@ class _FusedDQN:
         return [(ref, row, B * world, denom, Q, algo.pf.epsilon)
                 for ref, row in self._ring.handles(self.step_count - count, count)]
 
-    def enqueue_epoch(self, count):
-        """`count` x {uniform replay sample -> update} as ONE graph launch (see _FusedSAC.enqueue_epoch): index sets drawn on
-        the host in the reference's order and uploaded once, each update of the graph gathering the set the device-resident
-        update count selects.  None when it does not apply: several ranks, a hard target copy due inside the epoch, a
-        replay buffer that stores the sampled keys differently (frame-dedup), no update seen yet, TRL_NO_GRAPH=1."""
-        algo = self.algo
-        buf, B, st = getattr(algo, "replay_buffer", None), int(algo.batch_size), self._static
-        soft = bool(algo.use_soft_update)
+    def _epoch_declined(self, count):
+        """Whole epochs need one rank, an update seen at this batch size and no hard target copy due inside the epoch."""
+        algo, st = self.algo, self._static
         period, done = int(algo.target_hard_update_period), int(algo.training_update_num)
-        if buf is None or st is None or count < 1 or count > self._ring.slots or dist.world_size() != 1 or \
-                dist.collectives_active() or os.environ.get("TRL_NO_GRAPH") == "1" or not hasattr(buf, "gather_sources") or \
-                int(st["obs"].shape[0]) != B or (not soft and any((done + j) % period == 0 for j in range(1, count + 1))):
-            return None
-        keys = self.KEYS
-        srcs = buf.gather_sources(keys)
-        nrows = buf._rows_per_batch(B)
-        if srcs is None or any(s.dtype != st[k].dtype or s[0].numel() * nrows != st[k].numel() for s, k in zip(srcs, keys)):
-            return None
-        key = ("epoch", count, B, nrows, tuple(s.data_ptr() for s in srcs), soft,
-               float(algo.qf_optimizer.param_groups[0]['lr']), float(algo.discount), float(algo.tau), int(algo.quantile_num))
-        if key not in self._graphs and len(self._graphs) >= 4:
-            return None
-        self._ring.make_room(count)
-        slab = self._slab.upload(self.step_count, buf.draw_indices(B, count))
-        dsts = [st[k] for k in keys]
-
-        def launches():
-            for _ in range(count):
-                _C.gather_rows_multi(srcs, slab, dsts, slab_counter=self.step_state, n_rows=nrows)
-                self._sequence(st, soft)
-        if key in self._graphs:
-            self._graphs[key].replay()
-        elif key not in self._seen:                                      # first visit eager, captured on the second
-            self._seen.add(key)
-            launches()
-        else:
-            graph, _ = _C.capture_graph(launches)
-            self._graphs[key] = graph
-            graph.replay()
-        self.step_count += count
-        return self._handles(count, B)
+        return st is None or dist.world_size() != 1 or int(st["obs"].shape[0]) != int(algo.batch_size) or \
+            (not algo.use_soft_update and any((done + j) % period == 0 for j in range(1, count + 1)))

@@ -25,10 +25,10 @@ import torch.optim as optim
 
 from ... import _C, dist, ops
 from .off_rl_algo import OffRLAlgo
-from .twin_sac_q import _EngineSurface, _FusedSAC
+from .twin_sac_q import _FusedSAC, _SoftSurface
 
 
-class _ValueSAC(_EngineSurface, OffRLAlgo):
+class _ValueSAC(_SoftSurface, OffRLAlgo):
     """What SAC and TwinSAC share: `_setup` behind their reference-shaped constructors."""
 
     def _setup(self, pf, vf, critics, plr, vlr, qlr, optimizer_class, policy_std_reg_weight, policy_mean_reg_weight,

@@ -18,21 +18,20 @@ The two N(0,1) draws per update come from the CPU torch generator (reference par
 device Philox stream (`noise_mode="device"`).
 """
 import copy
-import os
 
 import numpy as np
 import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
-from ...networks import flatten_into
 from ._deferred import IndexSlab, StatRing
+from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static
 from .off_rl_algo import OffRLAlgo
 
 
-class _EngineSurface:
-    """What the soft actor-critics offer over their fused engine (`_engine_class`, built on first use): `update` and its
-    deferred forms, `static_batch`, and `log_alpha` read from the engine's device-resident temperature state."""
+class _SoftSurface(_EngineSurface):
+    """The soft actor-critics over their fused engine (`_engine_class`, built on first use): `_EngineSurface`, and
+    `log_alpha` read from the engine's device-resident temperature state."""
     _engine_class = None
 
     @property
@@ -46,32 +45,8 @@ class _EngineSurface:
             self._engine = self._engine_class(self)
         return self._engine
 
-    def static_batch(self):
-        return self.engine().static_batch(self.batch_size)
 
-    def update(self, batch):
-        self.training_update_num += 1
-        return self.engine().update(batch)
-
-    def update_deferred(self, batch):
-        """`update` without its read-back: OffRLAlgo.update_per_epoch enqueues all `opt_times` updates of an epoch and
-        resolves their info dicts with one D2H (`resolve_updates`)."""
-        self.training_update_num += 1
-        return self.engine().enqueue(batch)
-
-    def update_epoch_deferred(self, count):
-        """All `count` {uniform sample -> update} pairs of an epoch as one replayed graph (None when the engine's
-        conditions for it do not hold: the caller then samples and enqueues one by one)."""
-        handles = self.engine().enqueue_epoch(count)
-        if handles is not None:
-            self.training_update_num += count
-        return handles
-
-    def resolve_updates(self, handles):
-        return self.engine().resolve(handles)
-
-
-class TwinSACQ(_EngineSurface, OffRLAlgo):
+class TwinSACQ(_SoftSurface, OffRLAlgo):
     def __init__(self, pf, qf1, qf2, plr, qlr, optimizer_class=optim.Adam, policy_std_reg_weight=1e-3,
                  policy_mean_reg_weight=1e-3, reparameterization=True, automatic_entropy_tuning=True,
                  target_entropy=None, noise_mode="host", **kwargs):
@@ -113,7 +88,7 @@ class TwinSACQ(_EngineSurface, OffRLAlgo):
         return [(self.qf1, self.target_qf1), (self.qf2, self.target_qf2)]
 
 
-class _FusedSAC:
+class _FusedSAC(_FusedOffPolicy):
     """The engine of TwinSACQ.  What a soft actor-critic of another make-up changes (sac_v.py: a value network beside
     the critics) are the two class attributes, `_roles`, `_info` and the loss half of `_sequence`; the flat buffers, the
     optimiser tail, the graph cache, the statistics ring and the epoch builder are these."""
@@ -138,28 +113,11 @@ class _FusedSAC:
             raise _C.TrlError("the policy and the critics must use the same activation")
         self.layers = [ops.linear_layers(n) for n in nets]
         plists = [[t for wb in ls for t in wb] for ls in self.layers]
-        self.sizes = [sum(p.numel() for p in pl) for pl in plists]
-        self.flat = flatten_into([p for pl in plists for p in pl])      # [pf | qf1 | qf2]; parameters become views
         self.tlayers = [ops.linear_layers(n) for n in targets]
-        self.tflat = flatten_into([t for ls in self.tlayers for wb in ls for t in wb])
+        home = FlatHome(plists, self.optimizers, [t for ls in self.tlayers for wb in ls for t in wb])
+        self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v   # [pf | qf1 | qf2]
+        self.sizes, self.gviews = home.sizes, home.pairs()
         self.target_off = sum(self.sizes[:len(nets) - len(targets)])    # the targets' sources: flat[target_off:]
-        self.grads = torch.zeros_like(self.flat)
-        self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.gviews, off = [], 0
-        for ls in self.layers:
-            views = []
-            for w, b in ls:
-                gw = self.grads[off:off + w.numel()].view(w.shape); off += w.numel()
-                gb = self.grads[off:off + b.numel()].view(b.shape); off += b.numel()
-                views.append((gw, gb))
-            self.gviews.append(views)
-        off = 0
-        for opt, pl in zip(self.optimizers, plists):
-            for p in pl:
-                n = p.numel()
-                opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
-                                "exp_avg_sq": self.v[off:off + n].view(p.shape)}
-                off += n
         self.step_count = 0
         self.alpha_state = torch.zeros(4, device=self.dev)               # log_alpha, exp_avg, exp_avg_sq, step
         # every logged statistic in one block, one D2H per update: loss sums | 3 x 4 moments | alpha, alpha_loss | norms
@@ -176,7 +134,7 @@ class _FusedSAC:
         self.noise_ctr = 0
         self.noise_seed = 0x5AC
         self.step_state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
-        self._static, self._graphs, self._seen = {}, {}, set()
+        self._static, self._graphs = {}, GraphCache(8)
         # the statistics block of update u is filed into ring row u % slots by the update's last launch
         self._ring = StatRing(max(64, int(getattr(algo, "opt_times", 1))), self._raw.numel(), torch.uint8, self.dev)
         self._slab = IndexSlab(self.dev)
@@ -296,20 +254,10 @@ class _FusedSAC:
         if not fused_tail:
             plan.run()
         # ---- optimiser steps (pf, qf1, qf2) and target update ----
-        a = _C.AdamArgs()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                      self.m.data_ptr(), self.v.data_ptr())
-        a.n_groups = len(self.sizes)
-        for k, size in enumerate(self.sizes):
-            a.group_sizes[k] = size
-        for k, lr in enumerate(self._lrs()):
-            a.group_lr[k] = lr
-        a.max_norm = float(algo.grad_clip) if algo.grad_clip else 0.0
-        a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-8
         dist.all_reduce_sum_(self.grads)                                 # C1: every loss is a local mean -> SUM / world
-        a.grad_scale = 1.0 / dist.world_size()
-        a.step_count, a.norms_out = 0, self.norms.data_ptr()
-        a.step_state = self.step_state.data_ptr()                        # the step count lives on the device
+        a = _C.adam_args(self.flat, self.grads, self.m, self.v, self.sizes, self._lrs(),
+                         max_norm=float(algo.grad_clip) if algo.grad_clip else 0.0, grad_scale=1.0 / dist.world_size(),
+                         norms_out=self.norms.data_ptr(), step_state=self.step_state.data_ptr())
         if fused_tail:
             if self._tail_ws is None:
                 self._tail_ws = _C.fold_clip_adam_polyak_workspace(dev)
@@ -346,38 +294,14 @@ class _FusedSAC:
     def _lrs(self):
         return tuple(float(o.param_groups[0]['lr']) for o in self.optimizers)
 
-    def _run(self, st, soft):
-        """Eager on the first visit of a configuration, captured into a HIP graph on the second, replayed
-        afterwards: ~90 dependent launches per update otherwise pay the eager launch latency each
-        (TRL_NO_GRAPH=1 keeps everything eager)."""
-        key = (int(st["obs"].shape[0]), soft, self._lrs(), self.algo.grad_clip, self.algo.tau, self.algo.discount,
-               bool(self.algo.automatic_entropy_tuning), self._inline_noise())
-        if os.environ.get("TRL_NO_GRAPH") == "1" or dist.collectives_active() or \
-                (key not in self._graphs and len(self._graphs) >= 8):     # collectives between ranks: eager launches
-            self._sequence(st, soft)                                     # (a learning-rate schedule would mint a key per value)
-        elif key in self._graphs:
-            self._graphs[key].replay()
-        elif key not in self._seen:
-            self._seen.add(key)
-            self._sequence(st, soft)
-        else:
-            graph, _ = _C.capture_graph(lambda: self._sequence(st, soft))
-            self._graphs[key] = graph
-            graph.replay()
-
     def enqueue(self, batch):
         """Launch one update without waiting for it; returns the handle `resolve` turns into the info dict.  The logged
         statistics of the update are copied (stream-ordered) into a slot of a device ring, so that an epoch's
         `opt_times` updates need ONE read-back instead of one host sync each."""
-        algo, dev, A, D = self.algo, self.dev, self.A, self.D
+        algo, dev, A = self.algo, self.dev, self.A
         B = int(batch['obs'].shape[0])
         st = self.static_batch(B)
-        for k in ("obs", "next_obs", "acts", "rewards", "terminals"):
-            src = batch[k]
-            if src is st[k]:
-                continue
-            src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
-            st[k].copy_(src.to(dtype=torch.float32).reshape(st[k].shape), non_blocking=True)
+        load_static(st, batch, self.KEYS)
         n_env = int(algo.replay_buffer.env_nums) if getattr(algo, "replay_buffer", None) is not None else B
         rows = B // n_env if B % n_env == 0 else 1                       # batch = sampled time rows x this rank's envs
         inline = self._inline_noise()
@@ -394,7 +318,10 @@ class _FusedSAC:
                 make = lambda m, f: _C.philox_normal(torch.empty(m, f, device=dev), self.noise_seed, self.noise_ctr)
             st[k].copy_(dist.shard_rows_of_global(make, rows, B // rows, A, dev), non_blocking=True)
         self._ring.make_room(1)
-        self._run(st, bool(algo.use_soft_update))
+        soft = bool(algo.use_soft_update)
+        # (collectives between ranks: eager launches; a learning-rate schedule would mint a key per value)
+        self._graphs.run((B, soft, self._lrs(), algo.grad_clip, algo.tau, algo.discount,
+                          bool(algo.automatic_entropy_tuning), self._inline_noise()), lambda: self._sequence(st, soft))
         if inline:
             self.noise_ctr += len(self.NOISE)                            # the draws the sampling launch made
         self.step_count += 1
@@ -407,49 +334,20 @@ class _FusedSAC:
         reads)."""
         return [(ref, row, B) for ref, row in self._ring.handles(self.step_count - count, count)]
 
-    def enqueue_epoch(self, count):
-        """`count` x {uniform replay sample -> update} as ONE graph launch: the index sets are drawn on the host in the
-        order `count` random_batch calls would draw them and uploaded once; every update of the graph gathers the set
-        the device-resident update count selects (trl_gather_rows_multi with its update counter), draws its own noise from that count and files
-        its statistics into its ring slot.  Returns the handles, or None when this path does not apply (host noise,
-        several ranks, hard target updates, a replay buffer that does not store the sampled keys plainly, TRL_NO_GRAPH=1)."""
-        algo = self.algo
-        buf, B = getattr(algo, "replay_buffer", None), int(algo.batch_size)
-        if buf is None or count < 1 or count > self._ring.slots or not algo.use_soft_update or \
-                not self._inline_noise() or dist.collectives_active() or os.environ.get("TRL_NO_GRAPH") == "1" or \
-                not hasattr(buf, "gather_sources"):
-            return None
-        keys = ("obs", "next_obs", "acts", "rewards", "terminals")
-        srcs = buf.gather_sources(keys)
-        st = self.static_batch(B)
-        if srcs is None or any(s.dtype != torch.float32 or s[0].numel() * buf._rows_per_batch(B) != st[k].numel()
-                               for s, k in zip(srcs, keys)):
-            return None
-        nrows = buf._rows_per_batch(B)
-        key = ("epoch", count, B, nrows, tuple(s.data_ptr() for s in srcs), self._lrs(), algo.grad_clip, algo.tau,
-               algo.discount, bool(algo.automatic_entropy_tuning))
-        if key not in self._graphs and len(self._graphs) >= 8:
-            return None
-        self._ring.make_room(count)
-        slab = self._slab.upload(self.step_count, buf.draw_indices(B, count))
-        dsts = [st[k] for k in keys]
+    def _epoch_declined(self, count):
+        """Whole epochs need soft target updates and noise drawn inside the sampling launch (device noise, one rank)."""
+        return not self.algo.use_soft_update or not self._inline_noise()
 
-        def launches(n):
-            for _ in range(n):
-                _C.gather_rows_multi(srcs, slab, dsts, slab_counter=self.step_state, n_rows=nrows)
-                self._sequence(st, True)
-        if key in self._graphs:
-            self._graphs[key].replay()
-        elif key not in self._seen:                                      # first visit eager, captured on the second
-            self._seen.add(key)
-            launches(count)
-        else:
-            graph, _ = _C.capture_graph(lambda: launches(count))
-            self._graphs[key] = graph
-            graph.replay()
-        self.noise_ctr += len(self.NOISE) * count
-        self.step_count += count
-        return self._handles(count, B)
+    def _epoch_key(self, soft):
+        algo = self.algo
+        return (self._lrs(), algo.grad_clip, algo.tau, algo.discount, bool(algo.automatic_entropy_tuning))
+
+    def enqueue_epoch(self, count):
+        """`_FusedOffPolicy.enqueue_epoch`; every update of the graph draws its own noise from the update count."""
+        handles = super().enqueue_epoch(count)
+        if handles is not None:
+            self.noise_ctr += len(self.NOISE) * count
+        return handles
 
     def resolve(self, handles):
         """Info dicts of enqueued updates, in order: one D2H per ring (normally one per call), the only host sync."""
@@ -458,9 +356,6 @@ class _FusedSAC:
         parts = (raw[:, o[0]:o[1]].view(np.float64).tolist(), raw[:, o[1]:o[2]].view(np.float64).tolist(),   # one conversion, not
                  raw[:, o[2]:o[3]].view(np.float32).tolist(), raw[:, o[3]:o[4]].view(np.float32).tolist())   # views per update
         return [self._info(part, h[2]) for part, h in zip(zip(*parts), handles)]
-
-    def update(self, batch):
-        return self.resolve([self.enqueue(batch)])[0]
 
     def _reg_terms(self, mom, Bg):
         """w_std mean(log_std^2) + w_mean mean(mean^2) of the policy loss, from the logged moments over Bg rows."""
