@@ -75,19 +75,24 @@ template <int D, int H, int A> struct WvShape {
   static constexpr int O_W2F = 0, O_W2B = H * LDW, O_B1 = 2 * H * LDW, O_B2 = O_B1 + H, O_SCR = O_B2 + H;
   static constexpr int O_H1 = 0, O_H2 = H * LDT, O_DZ2 = 2 * H * LDT, O_DO = 3 * H * LDT, WSCR = O_DO + 16 * LDT;
   static constexpr int P_STRIDE = PpoShape<D, H, A>::P_STRIDE;
-  static constexpr int MAIN = O_SCR + WV_WAVES * WSCR, FOLD = WV_WAVES * P_STRIDE;
-  static constexpr int LDS_FLOATS = MAIN > FOLD ? MAIN : FOLD;
+  static constexpr int MAIN = O_SCR + WV_WAVES * WSCR;
+  // epilogue exchange (re-uses the staging area): per wave its accumulator tiles as they sit in registers, [slot][lane] of
+  // f32x4 -- dW2 16 slots, dW1 4 (+ 4 for the wide tile's second k group), dW3 4 (policy pass) -- then, behind all four
+  // waves' tiles, per wave a block of row-summed scalars: db1 | db2 | dW1[:, 16] (64 each), policy db3 | dlogstd (16 each),
+  // value dW3 (64) | db3 (16)
+  static constexpr int XS_W2 = 0, XS_W1 = 16, XS_W1B = 20, XS_W3 = D > 17 ? 24 : 20, XS_PF = XS_W3 + 4, XS_VF = XS_W3;
+  static constexpr int XSC_PF = 3 * H + 32, XSC_VF = 4 * H + 16;
+  static constexpr int XCH_PF = WV_WAVES * (XS_PF * 256 + XSC_PF), XCH_VF = WV_WAVES * (XS_VF * 256 + XSC_VF);
+  static constexpr int XCH = XCH_PF > XCH_VF ? XCH_PF : XCH_VF;
+  static constexpr int LDS_FLOATS = MAIN > XCH ? MAIN : XCH;
 };
 
-// State-dependent-std head (SD): up to 16 head rows [mean | log_std] and no logstd tail -- a gradient image of its own
-// stride (the Gaussian's assumes at most 8 head rows + 8 logstd floats).  The main-loop layout is WvShape's; at the 17-wide
-// tile the four images (4 x 6400 floats) exceed it by 128 floats, at the 32-wide tile they set the size (4 x 7360 floats).
+// State-dependent-std head (SD): up to 16 head rows [mean | log_std] and no logstd tail -- a partial row of its own
+// stride (the Gaussian's assumes at most 8 head rows + 8 logstd floats).  The LDS layout, main loop and exchange, is
+// WvShape's: the 16 head rows are the same four dW3 accumulator tiles.
 template <int D, int H, int A> struct WvShapeSD : WvShape<D, H, A> {
-  using B = WvShape<D, H, A>;
   static constexpr int P_PF_SD = H * D + H + H * H + H + 2 * A * H + 2 * A, P_VF = MlpFlat<D, H, 1>::P_VF;
   static constexpr int P_STRIDE = ((P_PF_SD > P_VF ? P_PF_SD : P_VF) + 63) & ~63;
-  static constexpr int FOLD = WV_WAVES * P_STRIDE;
-  static constexpr int LDS_FLOATS = B::MAIN > FOLD ? B::MAIN : FOLD;
 };
 template <int D, int H, int A, int HEAD> struct WvPick { using T = WvShape<D, H, A>; };
 template <int D, int H, int A> struct WvPick<D, H, A, HEAD_SD> { using T = WvShapeSD<D, H, A>; };
@@ -121,7 +126,7 @@ __device__ __forceinline__ float row_sum16(float v) {
 // torchrl/policies/continuous_policy.py:134-170).  The head has 2 a.A rows [mean | log_std] (MlpFlat order), the flat policy
 // block has no logstd tail.  Tile row k < 8 is mean k, tile row 8 + k is log_std k, whatever a.A is: lanes (j, g) and
 // (j, g ^ 2) hold a mean and its log_std, one xor-32 exchange apart.  The head row of tile row o -- o < 8 ? o : a.A + (o - 8)
-// -- appears where W3 / b3 are loaded and where dW3 / db3 go to the gradient image.  Per element the arithmetic is
+// -- appears where W3 / b3 are loaded and where dW3 / db3 go to the partial row.  Per element the arithmetic is
 // gauss_sd_losses_kernel's (k_gauss_sd.hip); the per-sample statistics of log_std and std leave through a second block of
 // scalar rows (trl_ppo_sd_scalar_stride).
 template <int D, int H, int A, int ACT, bool IS_PF, bool CONTIG, bool RT, int HEAD = HEAD_GAUSS>
@@ -129,7 +134,7 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
   using S = typename WvPick<D, H, A, HEAD>::T;
   constexpr bool WIDE = D > 17,                      // a second 16-feature group (features 16 .. 31) on the matrix pipe
                  CAT = HEAD == HEAD_CAT, SD = HEAD == HEAD_SD,
-                 SDP = SD && IS_PF;                  // (SD's value pass differs in the stride of its gradient image only)
+                 SDP = SD && IS_PF;                  // (SD's value pass differs in the stride of its partial row only)
   static_assert(!WIDE || RT, "the wide tile exists as a runtime-dims instantiation only");
   static_assert(!CAT || (IS_PF && RT), "the categorical head is a policy pass of the runtime-dims kernels");
   static_assert(!SD || RT, "the state-dependent-std head belongs to the runtime-dims kernels");
@@ -369,6 +374,13 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     else b3v[r] = (o < O) ? gp[F_B3 + (o < O ? o : 0)] : 0.0f;
   }
   const float vb3 = IS_PF ? 0.0f : gp[F_B3];
+#ifdef TRL_EXP_CLK
+  // the set-up split: 22 = every global load issued, 23 = all of them returned (the latency no ready-made operand image can
+  // remove; it includes the first tile's dependent pair), 0 = the work behind them (LDS stores, barrier, f64 constants)
+  WCLK(22)
+  __builtin_amdgcn_s_waitcnt(0);
+  WCLK(23)
+#endif
 #pragma unroll
   for (int t = 0; t < NV; ++t) {
     const int e = 4 * (tid + WV_THREADS * t), r = e / H, c = e - r * H;
@@ -766,52 +778,122 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
     WCLK(6)
   }
 
-  // ---- epilogue: every wave writes its gradient image, then all threads add the 4 images in fixed order ----
   __syncthreads();                                                 // staging / weight copies are dead from here
-  float* gimg = lds + wave * S::P_STRIDE;            // every parameter slot below is written exactly once
-  for (int e = F_END + lane; e < PS; e += 64) gimg[e] = 0.0f;              // padding (and logstd slots of the value net)
+  const int wg = blockIdx.x;
+  // ---- epilogue: the waves exchange their accumulators in register layout, every wave folds the slots it owns ----
+  // Exchange: one 16-byte LDS store per accumulator tile at [wave][slot][lane] (consecutive lanes, consecutive 16 bytes),
+  // and the wave's row-summed scalars.  A wave that ran no tile writes its zeros.
+  {
+    constexpr int NS = IS_PF ? S::XS_PF : S::XS_VF, SC = IS_PF ? S::XSC_PF : S::XSC_VF;
+    f32x4* xch = reinterpret_cast<f32x4*>(lds);
+    float* xsc = lds + WV_WAVES * NS * 256;
+    f32x4* xw = xch + (wave * NS) * 64 + lane;
+    float* sw = xsc + wave * SC;
+    // The per-lane partials db1 | db2 | dW1[:, 16] (| the value net's dW3) are summed over the 16 sample lanes of a row
+    // group.  Instead of a row_sum16 per value in all 64 lanes (four DPP adds each, 48 / 64 values), the wave first
+    // transposes them through its own region: lane (j, g) stores the f32x4 of (kind, so) as entry j of task
+    // tt = 16 kind + 4 so + g, lane tt reads the task's 16 entries back and adds them in row_sum16's tree --
+    // ((x0 + x8) + (x4 + x12)) + ((x2 + x10) + (x6 + x14)), the same over the odd lanes, even + odd: lane j == 0's result
+    // bit for bit (its partners' values are the same sums with the operands swapped).  A task is 17 entries apart from
+    // the next, so the 16 lanes of a read hit 16 different 16-byte bank slots.  LDS operations of one wave execute in
+    // order: no barrier between the stores, the reads and the tile stores that overwrite the region.
+    {
+      constexpr int NK = IS_PF ? 3 : 4, TS = 17;
+      static_assert(NK * 16 <= 64 && NK * 16 * TS <= NS * 64, "one task per lane, inside the wave's own region");
+      f32x4* tr = xch + (wave * NS) * 64;
 #pragma unroll
-  for (int so = 0; so < 4; ++so)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int f = 16 * so + 4 * g + r;                           // output feature (row of W2 / W1)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) gimg[F_W2 + f * H + 16 * c + j] = gW2[so][c][r];
-      if (jv) gimg[F_W1 + f * Dr + j] = gW1[so][r];
-      if (WIDE && jv2) gimg[F_W1 + f * Dr + 16 + j] = gW1b[so][r];
-      const float c16 = WIDE ? 0.0f : row_sum16(gW1c[so][r]), s1 = row_sum16(gb1[so][r]), s2 = row_sum16(gb2[so][r]);
-      if (j == 0) { if (f16) gimg[F_W1 + f * Dr + 16] = c16; gimg[F_B1 + f] = s1; gimg[F_B2 + f] = s2; }
-      if constexpr (IS_PF) {
-        const int o = 4 * g + r;                                   // gW3 rows are outputs
-        if constexpr (SDP) { if (sd_has(o)) gimg[F_W3 + sd_row(o) * H + 16 * so + j] = gW3[so][r]; }
-        else if (o < O) gimg[F_W3 + o * H + 16 * so + j] = gW3[so][r];
-      } else {
-        const float w3s = row_sum16(gW3[so][r]);
-        if (j == 0) gimg[F_W3 + f] = w3s;
+      for (int so = 0; so < 4; ++so) {
+        f32x4* te = tr + (4 * so + g) * TS + j;
+        te[0] = f32x4{gb1[so][0], gb1[so][1], gb1[so][2], gb1[so][3]};
+        te[16 * TS] = f32x4{gb2[so][0], gb2[so][1], gb2[so][2], gb2[so][3]};
+        te[32 * TS] = f32x4{gW1c[so][0], gW1c[so][1], gW1c[so][2], gW1c[so][3]};
+        if constexpr (!IS_PF) te[48 * TS] = gW3[so];
+      }
+      if (lane < NK * 16) {
+        const f32x4* x = tr + lane * TS;
+        const f32x4 even = ((x[0] + x[8]) + (x[4] + x[12])) + ((x[2] + x[10]) + (x[6] + x[14]));
+        const f32x4 odd = ((x[1] + x[9]) + (x[5] + x[13])) + ((x[3] + x[11]) + (x[7] + x[15]));
+        *reinterpret_cast<f32x4*>(sw + 4 * lane) = even + odd;      // kind | feature 16 so + 4 g + r: sw[64 kind + f]
       }
     }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = 4 * g + r;
-    const float b3 = row_sum16(db3[r]), dl = row_sum16(dls[r]);
-    if constexpr (SDP) { if (j == 0 && sd_has(o)) gimg[F_B3 + sd_row(o)] = b3; }
-    else if (j == 0 && o < O) {
-      gimg[F_B3 + o] = b3;
-      if (IS_PF && !CAT) gimg[F_LS + o] = dl;
-    }
-  }
-  WCLK(7)
-  __syncthreads();
-  const int wg = blockIdx.x;
-  static_assert(S::P_STRIDE % 4 == 0, "partial rows are folded and stored 16 bytes at a time");
-  for (int e4 = tid; e4 < PS / 4; e4 += WV_THREADS) {
-    f32x4 acc = lds4(lds + 4 * e4);
+    for (int so = 0; so < 4; ++so) {                               // (behind the reads of the region they overwrite)
 #pragma unroll
-    for (int w = 1; w < WV_WAVES; ++w) acc += lds4(lds + w * S::P_STRIDE + 4 * e4);          // same order per element
-    *reinterpret_cast<f32x4*>(a.partial + (size_t)wg * a.p_stride + 4 * e4) = acc;
+      for (int c = 0; c < 4; ++c) xw[(S::XS_W2 + 4 * so + c) * 64] = gW2[so][c];
+      xw[(S::XS_W1 + so) * 64] = gW1[so];
+      if constexpr (WIDE) xw[(S::XS_W1B + so) * 64] = gW1b[so];
+      if constexpr (IS_PF) xw[(S::XS_W3 + so) * 64] = gW3[so];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 4 * g + r;
+      const float b3 = row_sum16(db3[r]), dl = row_sum16(dls[r]);
+      if (j == 0) {
+        if constexpr (IS_PF) { sw[3 * H + o] = b3; sw[3 * H + 16 + o] = dl; }
+        else sw[4 * H + o] = b3;
+      }
+    }
+    WCLK(7)
+    __syncthreads();
+    // Fold by ownership: wave w owns the dW2 / dW1 / dW3 tiles of feature slice so == w, adds the four waves' values as
+    // ((w0 + w1) + w2) + w3 and stores the sums straight into the partial row (64-byte runs per 16 lanes, the four dW2
+    // tiles of a slice side by side: whole 256-byte rows).  Every float of [0, PS) is stored exactly once.
+    float* prow = a.partial + (size_t)wg * a.p_stride;
+    auto fold4 = [&](int slot) -> f32x4 {
+      const f32x4* p = xch + slot * 64 + lane;
+      f32x4 acc = p[0];
+#pragma unroll
+      for (int w = 1; w < WV_WAVES; ++w) acc += p[w * NS * 64];
+      return acc;
+    };
+    {
+      const int so = wave;
+      f32x4 t2[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) t2[c] = fold4(S::XS_W2 + 4 * so + c);
+      const f32x4 t1 = fold4(S::XS_W1 + so);
+      f32x4 t1b = f32x4{0.f, 0.f, 0.f, 0.f}, t3 = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (WIDE) t1b = fold4(S::XS_W1B + so);
+      if constexpr (IS_PF) t3 = fold4(S::XS_W3 + so);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int f = 16 * so + 4 * g + r;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) prow[F_W2 + f * H + 16 * c + j] = t2[c][r];
+        if (jv) prow[F_W1 + f * Dr + j] = t1[r];
+        if (WIDE && jv2) prow[F_W1 + f * Dr + 16 + j] = t1b[r];
+        if constexpr (IS_PF) {
+          const int o = 4 * g + r;                                 // gW3 rows are outputs
+          if constexpr (SDP) { if (sd_has(o)) prow[F_W3 + sd_row(o) * H + 16 * so + j] = t3[r]; }
+          else if (o < O) prow[F_W3 + o * H + 16 * so + j] = t3[r];
+        }
+      }
+    }
+    for (int k = tid; k < SC; k += WV_THREADS) {
+      float acc = xsc[k];
+#pragma unroll
+      for (int w = 1; w < WV_WAVES; ++w) acc += xsc[w * SC + k];
+      const int q = k & (H - 1);
+      int dst = -1;
+      if (k < H) dst = F_B1 + q;
+      else if (k < 2 * H) dst = F_B2 + q;
+      else if (k < 3 * H) { if (f16) dst = F_W1 + q * Dr + 16; }
+      else if constexpr (IS_PF) {
+        const int o = q & 15;
+        if (q < 16) { if constexpr (SDP) { if (sd_has(o)) dst = F_B3 + sd_row(o); } else if (o < O) dst = F_B3 + o; }
+        else if (!CAT && !SDP && o < O) dst = F_LS + o;
+      } else {
+        if (k < 4 * H) dst = F_W3 + q;
+        else if (q < O) dst = F_B3 + q;
+      }
+      if (dst >= 0) prow[dst] = acc;
+    }
+    // the row's tail: padding, and the logstd slot behind the value net's block
+    for (int e = (IS_PF ? F_END : F_LS) + tid; e < PS; e += WV_THREADS) prow[e] = 0.0f;
   }
   WCLK(8)
 #ifdef TRL_EXP_CLK
+  __syncthreads();                                                 // (the stamps go where other threads stored padding)
   if (tid == 0) for (int ph = 0; ph < 24; ++ph) a.partial[(size_t)wg * a.p_stride + PS - 40 + ph] = clk_acc[ph];
 #endif
   // ---- scalar statistics ----
@@ -1393,7 +1475,7 @@ extern "C" int trl_ppo_sd_supported(int D, int H, int A, int act) { return head_
 // doubles of scal_partial per workgroup: the n_wg x 8 block of every head, then n_wg x SD_SCAL (see SD_SCAL)
 extern "C" int trl_ppo_sd_scalar_stride(void) { return HEADS[HEAD_SD].scal_stride; }
 static_assert(WvShapeSD<17, 64, 8>::P_STRIDE == 6400 && WvShapeSD<32, 64, 8>::P_STRIDE == 7360, "SD image strides at A = 8");
-static_assert(WvShapeSD<32, 64, 8>::LDS_FLOATS * sizeof(float) <= 160 * 1024, "SD fold images fit the LDS");
+static_assert(WvShapeSD<32, 64, 8>::LDS_FLOATS * sizeof(float) <= 160 * 1024, "the wide tile's exchange area fits the LDS");
 
 // Kernel generations that were built and measured on MI355X before this one (profiles/README.md): groups of
 // 4 waves per tile with LDS rendezvous (85 us per 65 536-sample minibatch), this wave-per-tile kernel (64 us),
