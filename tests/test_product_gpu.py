@@ -433,3 +433,35 @@ def test_graph_replay_matches_eager_launches(golden, monkeypatch):
     (f0, m0, v0, i0), (f1, m1, v1, i1) = results
     assert torch.equal(f0, f1) and torch.equal(m0, m1) and torch.equal(v0, v1)
     assert len(i0) == len(i1) and all(a == b for a, b in zip(i0, i1))
+
+
+def test_adam_header_is_handed_over_between_the_joint_sequence_and_the_two_chains(monkeypatch):
+    """The joint sequence keeps its Adam header (step count, beta powers, learning rates) in `red_ws`, the value chain its
+    own in `red_ws_v`; a change of route hands the current one over (`_FusedPPO._sync_headers`).  Smoke's shape, two engines
+    from the same seeds: X runs three epochs on the two chains; Y runs the first with `probe = []` (the joint sequence,
+    eager), the second on the two chains, the third with `probe = []` again.  "Same bits either way": parameters, Adam
+    moments and info dicts are equal."""
+    monkeypatch.setenv("TRL_PPO_CHAINS", "two")
+    monkeypatch.delenv("TRL_NO_GRAPH", raising=False)
+    N, T, horizon, max_frames, B, seed = 64, 16, 10, 7, 256, 0
+    updates = 2 * (N * T // B)                                          # per epoch: opt_epochs passes of N * T / B minibatches
+    results = []
+    for probes in ((None, None, None), ([], None, [])):
+        torch.manual_seed(7)
+        pf, vf, env, buf, col, agent, logger = build(None, "", N, T, horizon, max_frames, B, seed)
+        torch.manual_seed(seed)
+        eng = agent.engine()
+        for epoch, probe in enumerate(probes):
+            eng.probe = probe
+            col.train_one_epoch()
+            agent.current_epoch = epoch
+            np.random.seed(seed + epoch)
+            agent.update_per_epoch()
+            assert eng._hdr_owner == ("two" if probe is None else "joint")
+            assert probe is None or len(probe) == updates                # (the joint route ran: one event pair per gradient launch)
+        torch.cuda.synchronize()
+        assert int(eng.red_ws[:2].view(torch.int32)[1].item()) == eng.step_count == len(logger.infos) == 3 * updates
+        results.append((eng.flat.clone(), eng.m.clone(), eng.v.clone(), logger.infos))
+    (f0, m0, v0, i0), (f1, m1, v1, i1) = results
+    assert torch.equal(f0, f1) and torch.equal(m0, m1) and torch.equal(v0, v1)
+    assert len(i0) == len(i1) and all(a == b for a, b in zip(i0, i1))

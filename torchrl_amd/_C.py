@@ -106,9 +106,10 @@ class AdamArgs(C.Structure):
 
 
 def adam_args(flat, grads, m, v, sizes, lrs, *, offset=0, max_norm=0.0, eps=1e-8, grad_scale=1.0, norms_out=None,
-              step_state=None, step_count=0):
+              step_state=None, step_count=0, device_state=0, device_lr=None):
     """AdamArgs (beta 0.9 / 0.999) for the `sizes` groups that start `offset` elements into the four flat buffers;
-    `norms_out` and `step_state` (where the step count lives on the device) are addresses."""
+    `norms_out`, `step_state` (where the step count lives on the device) and `device_lr` (the learning rates there) are
+    addresses; `device_state=1`: step count and learning rates come from the fold launch's workspace header."""
     a = AdamArgs()
     a.params, a.grads, a.exp_avg, a.exp_avg_sq = (t.data_ptr() + int(offset) * t.element_size() for t in (flat, grads, m, v))
     a.n_groups = len(sizes)
@@ -116,6 +117,7 @@ def adam_args(flat, grads, m, v, sizes, lrs, *, offset=0, max_norm=0.0, eps=1e-8
         a.group_sizes[k], a.group_lr[k] = size, lr
     a.max_norm, a.beta1, a.beta2, a.eps = max_norm, 0.9, 0.999, eps
     a.step_count, a.grad_scale, a.norms_out, a.step_state = step_count, grad_scale, norms_out, step_state
+    a.device_state, a.device_lr = device_state, device_lr
     return a
 
 

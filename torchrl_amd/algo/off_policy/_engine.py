@@ -1,53 +1,15 @@
 """The host-side plumbing every fused off-policy engine shares (none of it is kernel code, all of it runs on CPU tensors):
-the eager -> captured -> replayed rule, the networks' home in one flat buffer, the copy of a sampled batch into the
-fixed-address inputs, the whole-epoch builder, and what an algorithm forwards to its engine."""
+the eager -> captured -> replayed rule (`GraphCache`, algo/_graphs.py, shared with the on-policy engines), the networks'
+home in one flat buffer, the copy of a sampled batch into the fixed-address inputs, the whole-epoch builder, and what an
+algorithm forwards to its engine."""
 import os
-from collections.abc import Mapping
 
 import numpy as np
 import torch
 
 from ... import _C, dist
 from ...networks import flatten_into
-
-
-class GraphCache(Mapping):
-    """Captured HIP graphs by key, at most `cap` of them and none ever evicted (a learning-rate schedule would mint a key
-    per value).  A launch sequence runs eagerly on the first visit of its key, is captured on the second and replayed
-    afterwards: the host then issues one call per update instead of ~45-90 and stays ahead of the device."""
-
-    def __init__(self, cap):
-        self.cap, self._graphs, self._seen = cap, {}, set()
-
-    def __getitem__(self, key):
-        return self._graphs[key]
-
-    def __iter__(self):
-        return iter(self._graphs)
-
-    def __len__(self):
-        return len(self._graphs)
-
-    def clear(self):
-        self._graphs.clear()
-        self._seen.clear()
-
-    def has_room(self, key):
-        return key in self._graphs or len(self._graphs) < self.cap
-
-    def run(self, key, launches):
-        graph = self._graphs.get(key)
-        if os.environ.get("TRL_NO_GRAPH") == "1" or dist.collectives_active() or \
-                (graph is None and len(self._graphs) >= self.cap):
-            launches()                                                   # eager, and the key stays unseen
-        elif graph is not None:
-            graph.replay()
-        elif key not in self._seen:
-            self._seen.add(key)
-            launches()
-        else:
-            self._graphs[key], _ = _C.capture_graph(launches)
-            self._graphs[key].replay()
+from .._graphs import GraphCache  # noqa: F401  (the engines and tests import it from here)
 
 
 class FlatHome:

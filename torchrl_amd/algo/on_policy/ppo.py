@@ -29,9 +29,21 @@ from ... import dist
 from ...networks import flatten_into
 from ...policies.continuous_policy import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, HEAD_TAG, head_kind, is_state_std  # noqa: F401
 from .. import utils as atu
+from .._graphs import GraphCache, LastGraph
 from .a2c import A2C
 
 _HALF_LOG_2PI_PLUS_HALF = 0.5 + 0.5 * math.log(2 * math.pi)
+
+
+def _hyper(algo):
+    """(clip_para, entropy_coeff, clipped_value_loss, tanh_action): what a loss kernel takes besides the data."""
+    return (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
+            int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
+
+
+def _stat_views(block, K):
+    """raw (K, 4) f64 | info (K, 24) f64 | norms (K, 2) f32 of a 29 K statistics block, on the device or its host twin."""
+    return block[:4 * K].view(K, 4), block[4 * K:28 * K].view(K, 24), block[28 * K:].view(torch.float32).view(K, 2)
 
 
 class PPO(A2C):
@@ -158,28 +170,17 @@ class _FusedPPO:
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = pf._mlp2_param_list() + tail(pf)
         vf_list = vf._mlp2_param_list()
-        self.P_pf = sum(p.numel() for p in pf_list)
-        self.P_vf = sum(p.numel() for p in vf_list)
-        self.flat = flatten_into(pf_list + vf_list)                   # [pf | vf], parameters become views
-        pf._flat, vf._flat = self.flat[:self.P_pf], self.flat[self.P_pf:]
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.grads = torch.zeros_like(self.flat)
-        self.step_count = 0
-        # target_pf mirrors the policy block of `flat`: its parameters become views of one buffer too
         tgt = getattr(algo, "target_pf", None)
-        self.target_flat = None
-        if tgt is not None:
-            self.target_flat = flatten_into(tgt._mlp2_param_list() + tail(tgt))
-            if self.categorical or self.state_std:                     # (its forward must find THIS storage, see _GenericPPO)
-                tgt._flat = self.target_flat
-        self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
-        self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
+        self._home(pf_list, vf_list, None if tgt is None else tgt._mlp2_param_list() + tail(tgt))
+        if tgt is not None and (self.categorical or self.state_std):   # (its forward must find THIS storage, see _GenericPPO)
+            tgt._flat = self.target_flat
         lib = _C.lib()
         sfx = HEAD_TAG[self.head]
-        self._k_grad = (getattr(lib, "trl_ppo_%sminibatch_grad_f32" % sfx), "trl_ppo_%sminibatch_grad_f32" % sfx)
-        self._k_fold = (getattr(lib, "trl_ppo_%sreduce_adam_f32" % sfx), "trl_ppo_%sreduce_adam_f32" % sfx)
-        self._k_fold_net = (getattr(lib, "trl_ppo_%sreduce_adam_net_f32" % sfx), "trl_ppo_%sreduce_adam_net_f32" % sfx)
+        kernel = lambda name: (getattr(lib, name), name)
+        self._k_grad = kernel("trl_ppo_%sminibatch_grad_f32" % sfx)
+        self._k_fold, self._k_fold_net = kernel("trl_ppo_%sreduce_adam_f32" % sfx), kernel("trl_ppo_%sreduce_adam_net_f32" % sfx)
+        # (the folds that carry the gradient SUM over ranks exist for the shared-std Gaussian head only)
+        self._k_fold_x, self._k_fold_net_x = kernel("trl_ppo_reduce_adam_xrank_f32"), kernel("trl_ppo_reduce_adam_xrank_net_f32")
         self.p_stride = getattr(_C, "ppo_%spartial_stride" % sfx)(self.D, self.H, self.A)
         # doubles of scalar statistics per workgroup (SD: a second block of rows behind the n_wg x 8 of every head)
         self.scal_w = _C.ppo_sd_scalar_stride() if self.state_std else 8
@@ -196,9 +197,27 @@ class _FusedPPO:
         self.red_ws_v = torch.zeros(n_ws, device=self.dev)            # the value chain's own Adam header + norm granules
         self.red_ws_v[4:8].view(torch.float64).fill_(1.0)
         self._side, self._value_done, self._hdr_owner, self._chain_graphs = None, None, "joint", {}
+        self._joint = LastGraph()                                      # the joint sequence's graph (`_graph`)
         self._pending, self._chain_pend, self._chain_seen = None, [], set()         # deferred statistics; shapes already run eagerly
         self._stats2_key = self._chain_rows = self._pro_ws = None                    # (allocated by the first run of a shape)
         self.red_ws[4:8].view(torch.float64).fill_(1.0)               # beta1^0, beta2^0 (device-side Adam state)
+
+    def _home(self, pf_list, vf_list, target_list):
+        """The networks' home: `flat` = [pf | vf] with the parameters views of it (nets that are MLP2 blocks hand their
+        own flat view to the fused inference kernel, Net.flat_params: it must be THIS storage, or the first forward after
+        the engine exists would re-home the parameters away from it), the moments and gradients beside it, `target_flat`
+        mirroring the policy block, and both optimisers' state bound to the moments."""
+        self.P_pf = sum(p.numel() for p in pf_list)
+        self.P_vf = sum(p.numel() for p in vf_list)
+        self.flat = flatten_into(pf_list + vf_list)
+        for net, lo, hi in ((self.algo.pf, 0, self.P_pf), (self.algo.vf, self.P_pf, self.P_pf + self.P_vf)):
+            if getattr(net, "mlp2_spec", lambda: None)() is not None:
+                net._flat = self.flat[lo:hi]
+        self.m, self.v, self.grads = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.step_count = 0
+        self.target_flat = None if target_list is None else flatten_into(target_list)
+        self._alias_optimizer_state(self.algo.pf_optimizer, pf_list, 0)
+        self._alias_optimizer_state(self.algo.vf_optimizer, vf_list, self.P_pf)
 
     def _alias_optimizer_state(self, opt, plist, offset):
         self._opt_steps = getattr(self, "_opt_steps", [])
@@ -256,8 +275,14 @@ class _FusedPPO:
             self._hyper_host = self._slab_host[K * rows_mb:].view(torch.float32)
             self._hyper = None
             self._stats_host = torch.zeros(29 * K, dtype=torch.float64).pin_memory()
-            self._graph = None
+            if self._joint is not None:
+                self._joint.clear()                                    # (its graph carries the old addresses)
         return self._idx_buf, self._stats
+
+    @property
+    def _graph(self):
+        """The joint sequence's captured graph, or None."""
+        return None if self._joint is None else self._joint.graph
 
     def _set_device_hyper(self, lr_pf, lr_vf, upload=True):
         """The learning rates into their page-locked slot; upload=False: the epoch prologue launch copies them (and the
@@ -269,7 +294,75 @@ class _FusedPPO:
             if upload:
                 self.red_ws[2:4].copy_(self._hyper_host, non_blocking=True)
 
-    defers = True                                                      # run(..., defer=True) is implemented
+    # ---- the launch builder: what the joint sequence and the two chains enqueue, called from their launch closures only
+    # (eager visits and captures; a replayed visit builds nothing) ----
+    def _adam_args(self, lrs=(0.0, 0.0), **kw):
+        """clip_grad_norm_(0.5) + Adam(eps 1e-5) over both networks' groups of the flat buffers."""
+        return _C.adam_args(self.flat, self.grads, self.m, self.v, (self.P_pf, self.P_vf), lrs, max_norm=0.5, eps=1e-5, **kw)
+
+    def _batch_args(self, t, hyper, loss_mode, rows_mb, N, n_global, partial, scal, n_wg, n_wg_pf):
+        """trl_ppo_batch_t of a gradient launch over `n_wg` workgroups that leave their rows in `partial` / `scal`."""
+        g = _C.PpoBatchArgs()
+        for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"):
+            setattr(g, k, _C.dev_ptr(t[k], name=k).value if t.get(k) is not None else None)
+        g.loss_mode = loss_mode
+        g.rows_mb, g.N, g.n_global = rows_mb, N, n_global
+        g.pf_params, g.vf_params = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.P_pf
+        g.D, g.H, g.A, g.act = self.D, self.H, self.A, self.act
+        g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = hyper
+        g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = partial.data_ptr(), scal.data_ptr(), n_wg, n_wg_pf
+        return g
+
+    def _prologue(self, pre, advs, idx, raw, zero, copies):
+        """`pre`, then ONE launch: the advantage statistics of all K minibatches (rows `idx` (K, rows_mb) of `advs`) into
+        `raw`, `zero` cleared, and the copies -- target_pf <- pf when `pre` asked for it, then the route's `copies`."""
+        self._copy_in_prologue = False
+        if pre is not None:
+            pre()
+        if self._pro_ws is None or self._pro_ws_k != tuple(idx.shape):  # (its counters assume one slicing)
+            self._pro_ws, self._pro_ws_k = _C.ppo_epoch_prologue_workspace(idx.shape[0], self.dev), tuple(idx.shape)
+        if self._copy_in_prologue:
+            copies = [(self.target_flat, self.flat[:self.P_pf])] + copies
+        _C.ppo_epoch_prologue(advs, idx, raw, self._pro_ws, zero=zero, copies=copies)
+        dist.reduce_adv_raw_(raw)                                      # C2 (identity in one process)
+
+    def _fold(self, kernel, partial, scal, n_wg, which, info, ws, comm=False):
+        """fold(k, g, a): the fused reduce / clip / Adam launch `kernel` behind minibatch k's gradient launch, its
+        statistics into row k of `info`.  `which`: the policy's workgroup count (joint) or the network (a chain); `comm`:
+        the xrank kernels, which take the peer transport's handle."""
+        import ctypes as C
+        fn, name = kernel
+        head = (partial.data_ptr(), scal.data_ptr(), n_wg, which, self.D, self.H, self.A, self.grads.data_ptr())
+        tail = (ws.data_ptr(),) + ((dist.comm_handle(),) if comm else ()) + (_C.stream_ptr(self.dev),)
+        info_base = info.data_ptr()
+        return lambda k, g, a: _C.check(fn(*head, info_base + 192 * k, C.byref(a), *tail), name)
+
+    def _minibatches(self, K, g, a, idx_dev, raw, norms, fold, probe=None):
+        """K x {gradient launch, `fold(k, g, a)`} on the current stream."""
+        import ctypes as C
+        stream = _C.stream_ptr(self.dev)
+        idx_base, raw_base, norm_base = idx_dev.data_ptr(), raw.data_ptr(), norms.data_ptr()
+        for k in range(K):
+            g.row_idx = idx_base + 8 * g.rows_mb * k
+            g.adv_raw = raw_base + 32 * k
+            a.step_count = self.step_count + k + 1
+            a.norms_out = norm_base + 8 * k
+            if probe is not None:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
+            if probe is not None:
+                ev[1].record()
+                probe.append(ev)
+            fold(k, g, a)
+
+    def _stepped(self, K):
+        """End of a run: K optimiser steps taken (host bookkeeping under the device's shadow)."""
+        self.step_count += K
+        for s in self._opt_steps:
+            s.fill_(float(self.step_count))
+
+    defers = True                                                    # run(..., defer=True) is implemented
 
     def run(self, t, row_idx, N, pre=None, pre_key=None, defer=False):
         """t: dict of (rows, N, feat) device tensors; row_idx: (K, rows_mb) host int64.
@@ -309,8 +402,7 @@ class _FusedPPO:
         idx_dev, stats = self._buffers(K, rows_mb)
         self._idx_host.numpy()[:] = row_idx.reshape(-1)
         rows_total = t["advs"].shape[0]
-        raw, info = stats[:4 * K].view(K, 4), stats[4 * K:28 * K].view(K, 24)
-        norms = stats[28 * K:].view(torch.float32).view(K, 2)
+        raw, info, norms = _stat_views(stats, K)
         # Env shards on several ranks with the peer transport up (dist.init_comm): the gradient SUM over ranks happens
         # INSIDE the fold / clip / Adam launch (trl_ppo_reduce_adam_xrank_f32) and the statistics go through the
         # one-kernel all-reduce -- plain launches, so the sequence is graph-replayed exactly like the single-process one.
@@ -341,105 +433,49 @@ class _FusedPPO:
             if getattr(self, "_lr_host", None) != (float(lr_pf), float(lr_vf)):
                 self._lr_host = (float(lr_pf), float(lr_vf))
                 self.lr_dev.copy_(torch.tensor(self._lr_host, dtype=torch.float32), non_blocking=True)
-        hyper = (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
-                 int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
+        hyper = _hyper(algo)
         use_graph = (fused or xrank or graph_coll) and probe is None and os.environ.get("TRL_NO_GRAPH") != "1"
         key = (n_wg, n_wg_pf, loss_mode, n_global, rows_total, N, pre_key, pre is not None, xrank, in_place) + hyper + tuple(
             0 if t.get(k) is None else t[k].data_ptr() for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"))
 
         def launch_all():
-            import ctypes as C
-            g = _C.PpoBatchArgs()
-            for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"):
-                setattr(g, k, _C.dev_ptr(t[k], name=k).value if t.get(k) is not None else None)
-            g.loss_mode = loss_mode
-            g.rows_mb, g.N, g.n_global = rows_mb, N, n_global
-            g.pf_params, g.vf_params = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.P_pf
-            g.D, g.H, g.A, g.act = self.D, self.H, self.A, self.act
-            g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = hyper
-            g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf
-            a = _C.AdamArgs()
-            a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                          self.m.data_ptr(), self.v.data_ptr())
-            a.n_groups = 2
-            a.group_sizes[0], a.group_sizes[1] = self.P_pf, self.P_vf
-            a.group_lr[0], a.group_lr[1] = lr_pf, lr_vf
-            a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-            a.device_state = int(fused or xrank)                       # step count / lr from the workspace header
-            idx_base, raw_base, info_base, norm_base = idx_dev.data_ptr(), raw.data_ptr(), info.data_ptr(), norms.data_ptr()
-            lib = _C.lib()
-            self._copy_in_prologue = False
-            if pre is not None:
-                pre()
-            stream = _C.stream_ptr(dev)
-            # advantage statistics of all K minibatches; the statistics block cleared and target_pf <- pf in the same launch
-            if self._pro_ws is None or self._pro_ws_k != (K, rows_mb):   # (its counters assume one slicing)
-                self._pro_ws, self._pro_ws_k = _C.ppo_epoch_prologue_workspace(K, dev), (K, rows_mb)
-            copies = [(self.target_flat, self.flat[:self.P_pf])] if self._copy_in_prologue else []
-            if in_place:
-                copies += [(idx_dev, self._idx_host), (self.red_ws[2:4], self._hyper_host)]
-            _C.ppo_epoch_prologue(t["advs"].reshape(rows_total, N),
-                                  (self._idx_host if in_place else idx_dev).view(K, rows_mb), raw, self._pro_ws,
-                                  zero=stats[4 * K:], copies=copies)
-            dist.reduce_adv_raw_(raw)
-            for k in range(K):
-                g.row_idx = idx_base + 8 * rows_mb * k
-                g.adv_raw = raw_base + 32 * k
-                a.step_count = self.step_count + k + 1
-                a.norms_out = norm_base + 8 * k
-                if probe is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
-                if probe is not None:
-                    ev[1].record()
-                    probe.append(ev)
-                if fused:                                              # one process: reduce + clip + Adam in one launch
-                    _C.check(self._k_fold[0](self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf,
-                                             self.D, self.H, self.A, self.grads.data_ptr(), info_base + 192 * k,
-                                             C.byref(a), self.red_ws.data_ptr(), stream), self._k_fold[1])
-                    continue
-                if xrank:                                              # the same launch with the cross-rank SUM inside
-                    _C.check(lib.trl_ppo_reduce_adam_xrank_f32(self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf,
-                                                               self.D, self.H, self.A, self.grads.data_ptr(),
-                                                               info_base + 192 * k, C.byref(a), self.red_ws.data_ptr(),
-                                                               dist.comm_handle(), stream), "trl_ppo_reduce_adam_xrank_f32")
-                    continue
-                _C.check(lib.trl_ppo_reduce_f32(self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf, self.D,
-                                                self.H, self.A, self.flat.data_ptr(), self.grads.data_ptr(),
-                                                info_base + 192 * k, stream), "trl_ppo_reduce_f32")
-                dist.all_reduce_sum_(self.grads)                       # C1: gradient SUM over ranks
-                if graph_coll:
-                    a.step_count, a.step_state, a.device_lr = 0, self.step_state.data_ptr(), self.lr_dev.data_ptr()
-                _C.check(lib.trl_clip_adam_f32(C.byref(a), stream), "trl_clip_adam_f32")
+            g = self._batch_args(t, hyper, loss_mode, rows_mb, N, n_global, self.partial, self.scal, n_wg, n_wg_pf)
+            a = self._adam_args((lr_pf, lr_vf), device_state=int(fused or xrank))   # step count / lr from the workspace header
+            slab = [(idx_dev, self._idx_host), (self.red_ws[2:4], self._hyper_host)] if in_place else []
+            self._prologue(pre, t["advs"].reshape(rows_total, N), (self._idx_host if in_place else idx_dev).view(K, rows_mb),
+                           raw, stats[4 * K:], slab)
+            if fused:                                                  # one process: reduce + clip + Adam in one launch
+                fold = self._fold(self._k_fold, self.partial, self.scal, n_wg, n_wg_pf, info, self.red_ws)
+            elif xrank:                                                # the same launch with the cross-rank SUM inside
+                fold = self._fold(self._k_fold_x, self.partial, self.scal, n_wg, n_wg_pf, info, self.red_ws, comm=True)
+            else:
+                import ctypes as C
+                lib, stream = _C.lib(), _C.stream_ptr(dev)
 
-        if not use_graph:
-            launch_all()
-        elif getattr(self, "_graph", None) is not None and self._graph_key == key:
-            self._graph.replay()
-        elif getattr(self, "_graph_seen", None) != key:
-            self._graph_seen = key                                     # first visit of a shape: run eagerly (warm-up)
-            self._graph = None
-            launch_all()
-        else:
-            graph, _ = _C.capture_graph(launch_all)
-            self._graph, self._graph_key = graph, key
-            graph.replay()
-        self.step_count += K
+                def fold(k, g, a):
+                    _C.check(lib.trl_ppo_reduce_f32(self.partial.data_ptr(), self.scal.data_ptr(), n_wg, n_wg_pf, self.D,
+                                                    self.H, self.A, self.flat.data_ptr(), self.grads.data_ptr(),
+                                                    info.data_ptr() + 192 * k, stream), "trl_ppo_reduce_f32")
+                    dist.all_reduce_sum_(self.grads)                   # C1: gradient SUM over ranks
+                    if graph_coll:
+                        a.step_count, a.step_state, a.device_lr = 0, self.step_state.data_ptr(), self.lr_dev.data_ptr()
+                    _C.check(lib.trl_clip_adam_f32(C.byref(a), stream), "trl_clip_adam_f32")
+            self._minibatches(K, g, a, idx_dev, raw, norms, fold, probe)
+
+        # eager on the first visit of a key, captured on the second, replayed afterwards; a new key starts over
+        self._joint.run(key, launch_all, eager=not use_graph)
         dist.reduce_info_(info)
         self._stats_host.copy_(stats, non_blocking=True)
         landed = torch.cuda.Event()
         landed.record()
-        for s in self._opt_steps:                                      # host bookkeeping under the device's shadow
-            s.fill_(float(self.step_count))
+        self._stepped(K)
         host = self._stats_host
         make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
 
         def build(host):
             if xrank:
                 dist.check_comm(peek=True)                             # a rank that never delivered: raise, do not hang
-            return make(host[:4 * K].view(K, 4).numpy(), host[4 * K:28 * K].view(K, 24).numpy(),
-                        host[28 * K:].view(torch.float32).view(K, 2).numpy(), n_global)
+            return make(*(v.numpy() for v in _stat_views(host, K)), n_global)
         pending = _PendingInfos(K, landed, host, build)
         if defer:
             self._pending = pending
@@ -486,7 +522,6 @@ class _FusedPPO:
         `xrank` (env shards on several ranks, peer transport): each chain's fold launch carries its network's gradient SUM
         over ranks (trl_ppo_reduce_adam_xrank_net_f32: own exchange count, own granules); the advantage statistics are
         reduced in the head, the logged statistics of both chains behind the value chain, on its stream."""
-        import ctypes as C
         algo, dev = self.algo, self.dev
         K, rows_mb = row_idx.shape
         main = torch.cuda.current_stream(dev)
@@ -527,8 +562,7 @@ class _FusedPPO:
         lr_pf, lr_vf = algo.pf_optimizer.param_groups[0]['lr'], algo.vf_optimizer.param_groups[0]['lr']
         hyper_host[0], hyper_host[1] = float(lr_pf), float(lr_vf)
         self._hyper = None                                             # (the joint route uploads its own copy when it runs next)
-        hyper = (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
-                 int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
+        hyper = _hyper(algo)
         n_wg_vf = n_wg - n_wg_pf
         if self._chain_rows is None:
             self._chain_rows = (torch.zeros(self.max_wg, self.p_stride, device=dev),
@@ -539,62 +573,23 @@ class _FusedPPO:
             0 if t.get(k) is None else t[k].data_ptr() for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"))
 
         def head():
-            self._copy_in_prologue = False
-            if pre is not None:
-                pre()
-            if self._pro_ws is None or self._pro_ws_k != (K, rows_mb):
-                self._pro_ws, self._pro_ws_k = _C.ppo_epoch_prologue_workspace(K, dev), (K, rows_mb)
-            copies = [(self.target_flat, self.flat[:self.P_pf])] if self._copy_in_prologue else []
-            copies += [(idx_dev, idx_host), (self.red_ws[2:4], hyper_host), (self.red_ws_v[2:4], hyper_host)]
-            _C.ppo_epoch_prologue(t["advs"].reshape(rows_total, N), idx_host.view(K, rows_mb), raw, self._pro_ws,
-                                  zero=stats2.view(-1)[4 * K:], copies=copies)
-            dist.reduce_adv_raw_(raw)                                  # C2 (identity in one process)
+            self._prologue(pre, t["advs"].reshape(rows_total, N), idx_host.view(K, rows_mb), raw, stats2.view(-1)[4 * K:],
+                           [(idx_dev, idx_host), (self.red_ws[2:4], hyper_host), (self.red_ws_v[2:4], hyper_host)])
 
         def chain(net):
-            lib = _C.lib()
-            stream = _C.stream_ptr(dev)
-            g = _C.PpoBatchArgs()
-            for k in ("obs", "acts", "advs", "rets", "old_values", "old_logp"):
-                setattr(g, k, _C.dev_ptr(t[k], name=k).value if t.get(k) is not None else None)
-            g.loss_mode = loss_mode
-            g.rows_mb, g.N, g.n_global = rows_mb, N, n_global
-            g.pf_params, g.vf_params = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.P_pf
-            g.D, g.H, g.A, g.act = self.D, self.H, self.A, self.act
-            g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = hyper
-            part, scal, ws = (self.partial, self.scal, self.red_ws) if net == 0 else (partial_v, scal_v, self.red_ws_v)
-            g.partial, g.scal_partial = part.data_ptr(), scal.data_ptr()
-            g.n_wg, g.n_wg_pf = (n_wg_pf, n_wg_pf) if net == 0 else (n_wg_vf, -1)
-            a = _C.AdamArgs()
-            a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                          self.m.data_ptr(), self.v.data_ptr())
-            a.n_groups = 2
-            a.group_sizes[0], a.group_sizes[1] = self.P_pf, self.P_vf
-            a.group_lr[0], a.group_lr[1] = lr_pf, lr_vf
-            a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-            a.device_state = 1
-            st = stats2[net]
-            info_base, norm_base = st[4 * K:].data_ptr(), st[28 * K:].data_ptr()
-            for k in range(K):
-                g.row_idx = idx_dev.data_ptr() + 8 * rows_mb * k
-                g.adv_raw = raw.data_ptr() + 32 * k
-                a.step_count, a.norms_out = self.step_count + k + 1, norm_base + 8 * k
-                _C.check(self._k_grad[0](C.byref(g), stream), self._k_grad[1])
-                if xrank:                                              # the network's gradient SUM over ranks inside the launch
-                    _C.check(lib.trl_ppo_reduce_adam_xrank_net_f32(part.data_ptr(), scal.data_ptr(), g.n_wg, net, self.D, self.H,
-                                                                   self.A, self.grads.data_ptr(), info_base + 192 * k, C.byref(a),
-                                                                   ws.data_ptr(), dist.comm_handle(), stream),
-                             "trl_ppo_reduce_adam_xrank_net_f32")
-                    continue
-                _C.check(self._k_fold_net[0](part.data_ptr(), scal.data_ptr(), g.n_wg, net, self.D, self.H, self.A,
-                                             self.grads.data_ptr(), info_base + 192 * k, C.byref(a), ws.data_ptr(), stream),
-                         self._k_fold_net[1])
+            part, scal, ws, wgs, wgs_pf = (self.partial, self.scal, self.red_ws, n_wg_pf, n_wg_pf) if net == 0 else \
+                (partial_v, scal_v, self.red_ws_v, n_wg_vf, -1)
+            g = self._batch_args(t, hyper, loss_mode, rows_mb, N, n_global, part, scal, wgs, wgs_pf)
+            a = self._adam_args((lr_pf, lr_vf), device_state=1)
+            _, info, norms = _stat_views(stats2[net], K)
+            # (xrank: the network's gradient SUM over ranks inside the fold launch)
+            fold = self._fold(self._k_fold_net_x if xrank else self._k_fold_net, part, scal, wgs, net, info, ws, comm=xrank)
+            self._minibatches(K, g, a, idx_dev, raw, norms, fold)
 
         # (graphs by key, a few of them: the stored observations alternate between the ring's tensor and its shadow, see
         # collector/on_policy.py::_launch, so a steady run replays TWO captured sets in turn)
         use_graph = os.environ.get("TRL_NO_GRAPH") != "1"
-        cache = self._chain_graphs if isinstance(self._chain_graphs, dict) else {}
-        self._chain_graphs = cache
-        seen = self._chain_seen
+        cache, seen = self._chain_graphs, self._chain_seen
         graphs = cache.get(key) if use_graph else None
         if use_graph and graphs is None and shape_key in seen and len(cache) < 8:
             # a shape's first run is eager (kernels load, attributes are set); every set of addresses after that is captured
@@ -640,9 +635,7 @@ class _FusedPPO:
         self._value_done = done_v
         from ...networks import nets as _nets
         _nets.set_pending(algo.vf, done_v)
-        self.step_count += K
-        for s_ in self._opt_steps:                                      # host bookkeeping under the device's shadow
-            s_.fill_(float(self.step_count))
+        self._stepped(K)
         make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
 
         class _Both:
@@ -654,14 +647,12 @@ class _FusedPPO:
         def build(host):
             if xrank:
                 dist.check_comm(peek=True)                             # a rank that never delivered: raise, do not hang
-            hp, hv = host[0], host[1]
-            info = hp[4 * K:28 * K].view(K, 24).clone()
-            iv = hv[4 * K:28 * K].view(K, 24)
+            (raw, info, norms), (_, info_v, norms_v) = _stat_views(host[0], K), _stat_views(host[1], K)
+            info, norms = info.clone(), norms.clone()
             for col in (7, 12, 13, 14, 15):                             # the value chain's entries of the statistics row
-                info[:, col] = iv[:, col]
-            norms = hp[28 * K:].view(torch.float32).view(K, 2).clone()
-            norms[:, 1] = hv[28 * K:].view(torch.float32).view(K, 2)[:, 1]
-            return make(hp[:4 * K].view(K, 4).numpy(), info.numpy(), norms.numpy(), n_global)
+                info[:, col] = info_v[:, col]
+            norms[:, 1] = norms_v[:, 1]
+            return make(raw.numpy(), info.numpy(), norms.numpy(), n_global)
         pending = _PendingInfos(K, _Both, stats_host, build)
         if defer:
             pend.append(pending)
@@ -821,27 +812,13 @@ class _GenericPPO(_FusedPPO):
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = ops.plan_params(self.pf_layers) + tail(pf)
         vf_list = ops.plan_params(self.vf_layers)
-        self.P_pf = sum(p.numel() for p in pf_list)
-        self.P_vf = sum(p.numel() for p in vf_list)
         self.D, self.A = int(self.pf_layers[0][0].shape[1]), int(self.pf_layers[-1][0].shape[0])
         if self.state_std:
             self.A //= 2
-        self.flat = flatten_into(pf_list + vf_list)                   # [pf | vf], parameters become views
-        # nets that are MLP2 blocks hand their own flat view to the fused inference kernel (Net.flat_params): it must
-        # be THIS storage, or the first forward after the engine exists would re-home the parameters away from it
-        for net, lo, hi in ((pf, 0, self.P_pf), (vf, self.P_pf, self.P_pf + self.P_vf)):
-            if getattr(net, "mlp2_spec", lambda: None)() is not None:
-                net._flat = self.flat[lo:hi]
-        self.m, self.v, self.grads = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.step_count = 0
         tgt = getattr(algo, "target_pf", None)
-        self.target_flat = None
-        if tgt is not None:
-            self.target_flat = flatten_into(ops.plan_params(layers_of(tgt)[0]) + tail(tgt))
-            if getattr(tgt, "mlp2_spec", lambda: None)() is not None:  # (same storage for its fused forward, as for pf / vf)
-                tgt._flat = self.target_flat
-        self._alias_optimizer_state(algo.pf_optimizer, pf_list, 0)
-        self._alias_optimizer_state(algo.vf_optimizer, vf_list, self.P_pf)
+        self._home(pf_list, vf_list, None if tgt is None else ops.plan_params(layers_of(tgt)[0]) + tail(tgt))
+        if tgt is not None and getattr(tgt, "mlp2_spec", lambda: None)() is not None:
+            tgt._flat = self.target_flat                               # (same storage for its fused forward, as for pf / vf)
         self.gviews, off = [], 0
         for layers in (self.pf_layers, self.vf_layers):
             views = []
@@ -855,7 +832,7 @@ class _GenericPPO(_FusedPPO):
                 self.g_logstd = self.grads[off:off + self.A]; off += self.A
         self.step_state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=self.dev)
         self.lr_dev = torch.zeros(2, device=self.dev)
-        self._graphs, self._seen = {}, set()
+        self._graphs, self._joint = GraphCache(4), None
         self.workspace = None
 
     def _ws(self, B):
@@ -874,20 +851,17 @@ class _GenericPPO(_FusedPPO):
         idx_dev, stats = self._buffers(K, rows_mb)
         idx_dev.copy_(torch.from_numpy(np.ascontiguousarray(row_idx).reshape(-1)), non_blocking=True)
         rows_total = t["advs"].shape[0]
-        raw, info = stats[:4 * K].view(K, 4), stats[4 * K:28 * K].view(K, 24)
-        norms = stats[28 * K:].view(torch.float32).view(K, 2)
+        raw, info, norms = _stat_views(stats, K)
         loss_mode = int(getattr(algo, "loss_mode", _C.LOSS_PPO_CLIP))
         ws = self._ws(n_local)
         idx2d = idx_dev.view(K, rows_mb)
-        replayable = not dist.collectives_active() and os.environ.get("TRL_NO_GRAPH") != "1"
         lrs = (float(algo.pf_optimizer.param_groups[0]['lr']), float(algo.vf_optimizer.param_groups[0]['lr']))
         if getattr(self, "_lr_host", None) != lrs:                     # learning rates live on the device: the linear
             self._lr_host = lrs                                        # schedule changes no launch argument
             self.lr_dev.copy_(torch.tensor(lrs, dtype=torch.float32), non_blocking=True)
         gather = lambda key, k: None if t.get(key) is None else \
             _C.gather_rows(t[key].reshape(rows_total, N, -1), idx2d[k]).reshape(n_local, -1)
-        hyper = (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
-                 bool(getattr(algo, "clipped_value_loss", False)), bool(algo.pf.tanh_action), loss_mode)
+        hyper = _hyper(algo) + (loss_mode,)
 
         def launch_all():
             if pre is not None:
@@ -917,34 +891,14 @@ class _GenericPPO(_FusedPPO):
                 ops.mlp_backward(tape_pf, d_mean, grads=self.gviews[0], workspace=ws)
                 ops.mlp_backward(tape_vf, d_v, grads=self.gviews[1], workspace=ws)
                 dist.all_reduce_sum_(self.grads)                       # C1: gradient SUM over ranks
-                a = _C.AdamArgs()
-                a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                              self.m.data_ptr(), self.v.data_ptr())
-                a.n_groups = 2
-                a.group_sizes[0], a.group_sizes[1] = self.P_pf, self.P_vf
-                a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-                a.step_count, a.norms_out = 0, norms[k].data_ptr()
-                a.step_state, a.device_lr = self.step_state.data_ptr(), self.lr_dev.data_ptr()   # device-side step count / lr
-                _C.clip_adam(a, dev)
+                _C.clip_adam(self._adam_args(norms_out=norms[k].data_ptr(), step_state=self.step_state.data_ptr(),
+                                             device_lr=self.lr_dev.data_ptr()), dev)     # device-side step count / lr
 
         # eager on the first visit of a configuration, captured into a HIP graph on the second, replayed afterwards
         key = (K, rows_mb, N, rows_total, n_global, idx_dev.data_ptr(), stats.data_ptr(), pre_key, pre is not None) + hyper + tuple(
             0 if t.get(k_) is None else t[k_].data_ptr() for k_ in ("obs", "acts", "advs", "rets", "old_values", "old_logp"))
-        graphs = self._graphs
-        if not replayable or (key not in graphs and len(graphs) >= 4):
-            launch_all()
-        elif key in graphs:
-            graphs[key].replay()
-        elif key not in self._seen:
-            self._seen.add(key)
-            launch_all()
-        else:
-            graph, _ = _C.capture_graph(launch_all)
-            graphs[key] = graph
-            graph.replay()
-        self.step_count += K
-        for s in self._opt_steps:
-            s.fill_(float(self.step_count))
+        self._graphs.run(key, launch_all)
+        self._stepped(K)
         ent_sum = None
         if self.categorical and dist.collectives_active():             # slot 20 (entropy SUM) is not among the columns
             ent_sum = info[:, 20].contiguous()                         # reduce_info_ sums: its own all-reduce, put back below
@@ -954,5 +908,4 @@ class _GenericPPO(_FusedPPO):
             info[:, 20] = ent_sum
         host = stats.cpu()                                             # the only host sync of the update
         make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
-        return make(host[:4 * K].view(K, 4).numpy(), host[4 * K:28 * K].view(K, 24).numpy(),
-                    host[28 * K:].view(torch.float32).view(K, 2).numpy(), n_global)
+        return make(*(v.numpy() for v in _stat_views(host, K)), n_global)

@@ -197,14 +197,7 @@ class _TRPOEngine(_GenericPPO):
         d_v = _C.mse_value_loss(v.view(-1), rets, 2 * B, self._stat[10:11])       # 0.5 * mean((v - R)^2): d = (v - R) / B
         ops.mlp_backward(tape, d_v, grads=self.gviews[1], workspace=self._ws(B))
         self.vf_steps += 1
-        a = _C.AdamArgs()
-        o = 4 * self.P_pf
-        a.params, a.grads = self.flat.data_ptr() + o, self.grads.data_ptr() + o
-        a.exp_avg, a.exp_avg_sq = self.m.data_ptr() + o, self.v.data_ptr() + o
-        a.n_groups = 1
-        a.group_sizes[0] = self.P_vf
-        a.group_lr[0] = algo.vf_optimizer.param_groups[0]['lr']
-        a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-        a.step_count, a.norms_out = self.vf_steps, self._vf_norm.data_ptr()
-        _C.clip_adam(a, dev)
+        _C.clip_adam(_C.adam_args(self.flat, self.grads, self.m, self.v, [self.P_vf], [algo.vf_optimizer.param_groups[0]['lr']],
+                                  offset=self.P_pf, max_norm=0.5, eps=1e-5, step_count=self.vf_steps,
+                                  norms_out=self._vf_norm.data_ptr()), dev)
         return {'Training/vf_loss': 0.5 * float(self._stat[10].item()) / B, 'grad_norm/vf': float(self._vf_norm.item())}

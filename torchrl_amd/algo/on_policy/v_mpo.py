@@ -116,19 +116,9 @@ class _VMPOEngine(_GenericPPO):
                                 self.g_logstd, info)
         ops.mlp_backward(tape_pf, d_mean, grads=self.gviews[0], workspace=ws)
         # ---- clip_grad_norm_(0.5) + Adam(eps 1e-5) for both nets ----
-        a = _C.AdamArgs()
-        a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
-                                                      self.m.data_ptr(), self.v.data_ptr())
-        a.n_groups = 2
-        a.group_sizes[0], a.group_sizes[1] = self.P_pf, self.P_vf
-        a.group_lr[0] = algo.pf_optimizer.param_groups[0]['lr']
-        a.group_lr[1] = algo.vf_optimizer.param_groups[0]['lr']
-        a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-5, 1.0
-        self.step_count += 1
-        a.step_count, a.norms_out = self.step_count, norms.data_ptr()
-        _C.clip_adam(a, dev)
-        for s in self._opt_steps:
-            s.fill_(float(self.step_count))
+        _C.clip_adam(self._adam_args((algo.pf_optimizer.param_groups[0]['lr'], algo.vf_optimizer.param_groups[0]['lr']),
+                                     step_count=self.step_count + 1, norms_out=norms.data_ptr()), dev)
+        self._stepped(1)
         host = self._raw.cpu()                                         # the only host sync of the update
         r, i = host[:4].numpy(), host[4:16].numpy()
         nrm = host[17:18].view(torch.float32).numpy()
