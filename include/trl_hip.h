@@ -116,7 +116,10 @@ int trl_mlp2_forward_supported(int D, int H, int O);
 typedef struct trl_rollout_t {
   /* networks (MLP2 blocks, D -> H -> H -> {A,1}) */
   const float* pf_params;     /* incl. logstd[A] at the tail */
-  const float* vf_params;
+  const float* vf_params;     /* NULL: no critic (REINFORCE, reinforce.py:20-21: V == 0).  The value pass behind the
+                                 rollout is then a streaming launch that stores 0.0f in `values` of the n_steps x N
+                                 stored cells and in boot_values, publishes the header like the value pass, leaves
+                                 the rewards alone (gamma * 0) and does not wait for value_wait_event */
   int D, H, A, act;           /* act: TRL_ACT_* */
   int tanh_action;            /* policies' tanh_action flag (continuous_policy.py:92-132) */
   /* synthetic env: obs' = tanh(obs @ env_A + act @ env_B) */
@@ -257,6 +260,7 @@ int trl_gauss_logp_f32(const float* mean, const float* acts, const float* logstd
  * gradients; trl_ppo_reduce_f32 folds them. */
 #define TRL_LOSS_PPO_CLIP 0
 #define TRL_LOSS_A2C      1
+#define TRL_LOSS_REINFORCE 2  /* the policy half of TRL_LOSS_A2C alone (reinforce.py:55-60): no critic anywhere */
 typedef struct trl_ppo_batch_t {
   const float *obs, *acts, *advs, *rets, *old_values, *old_logp;  /* (rows, N, feat) */
   const int64_t* row_idx;     /* (rows_mb) time rows of this minibatch, or NULL = rows 0.. */
@@ -268,7 +272,10 @@ typedef struct trl_ppo_batch_t {
   float clip_para, entropy_coeff;
   int clipped_value_loss, tanh_action;
   int loss_mode;              /* TRL_LOSS_PPO_CLIP: ratio / clip / min surrogate (ppo.py:41-91);
-                                 TRL_LOSS_A2C: -mean(log pi * adv) (a2c.py:69-70; old_logp may be NULL) */
+                                 TRL_LOSS_A2C: -mean(log pi * adv) (a2c.py:69-70; old_logp may be NULL);
+                                 TRL_LOSS_REINFORCE: the same policy arithmetic, bit for bit, in an all-policy launch
+                                 only (n_wg_pf == n_wg, TRL_EINVAL otherwise; clipped_value_loss must be 0): rets,
+                                 old_values, old_logp and vf_params may be NULL */
   float* partial;             /* (n_wg, P_STRIDE) fp32 workspace */
   double* scal_partial;       /* (n_wg, 8) */
   int n_wg;                   /* workgroups launched (>= 2); rows of partial / scal_partial */
@@ -303,7 +310,11 @@ int trl_ppo_reduce_f32(const float* partial, const double* scal_partial, int n_w
  *   from trl_adv_stats_f64 and n_global its sample count (advantage normalisation, ppo.py:141-147)
  *   -> d_mean (B, A), d_v (B), d_logstd (A) and info (24 doubles, trl_ppo_reduce_f32's layout; the sums are
  *      over the local samples, divide by the count on the host).
- * Same per-sample arithmetic as the fused kernel.  workspace: trl_ppo_generic_losses_workspace(B, A) doubles. */
+ * Same per-sample arithmetic as the fused kernel.  workspace: trl_ppo_generic_losses_workspace(B, A) doubles.
+ * loss_mode TRL_LOSS_REINFORCE (this kernel and its categorical / state-dependent-std siblings below): the policy half of
+ * TRL_LOSS_A2C alone, bit for bit -- v, rets, v_old, d_v and old_logp may be NULL and are never dereferenced,
+ * clipped_value_loss must be 0 (TRL_EINVAL), no value-side arithmetic or reduction runs, and info slots 7 and 12..15 are
+ * written as 0.0. */
 int trl_ppo_generic_losses_workspace(int B, int A);
 int trl_ppo_generic_losses_f32(const float* mean, const float* logstd, const float* acts, const float* advs,
                                const float* old_logp, const float* v, const float* rets, const float* v_old,
@@ -439,7 +450,7 @@ int trl_ppo_reduce_adam_f32(const float* partial, const double* scal_partial, in
 /* One network's half of trl_ppo_reduce_adam_f32: the n_wg rows of `partial` / `scal_partial` come from a single-network
  * gradient launch (trl_ppo_batch_t.n_wg_pf = n_wg: net 0, the policy; n_wg_pf = -1: net 1, the value function); folds them,
  * clips that group by its own norm and takes its Adam step (adam: the two-group descriptor; only group `net` is stepped,
- * norms_out[net] written).  PPO.update_critic and update_actor (ppo.py:93-122, 41-91) touch disjoint networks, optimisers
+ * norms_out[net] written; net 0 also takes a ONE-group descriptor [policy] -- an optimiser without a value function).  PPO.update_critic and update_actor (ppo.py:93-122, 41-91) touch disjoint networks, optimisers
  * and statistics, so the two halves are independent launch sequences -- the next rollout needs only the policy's.
  * workspace: trl_ppo_reduce_adam_workspace floats PER NETWORK (each keeps its own Adam header). */
 int trl_ppo_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net,

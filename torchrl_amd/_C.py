@@ -78,7 +78,7 @@ class RolloutArgs(C.Structure):
     ]
 
 
-LOSS_PPO_CLIP, LOSS_A2C = 0, 1                                   # TRL_LOSS_* of include/trl_hip.h
+LOSS_PPO_CLIP, LOSS_A2C, LOSS_REINFORCE = 0, 1, 2                # TRL_LOSS_* of include/trl_hip.h (2: the policy half alone)
 
 
 class PpoBatchArgs(C.Structure):
@@ -781,21 +781,24 @@ def linear_fwd(x, w, bias, act):
 
 def ppo_generic_losses(mean, logstd, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, clip_para, entropy_coeff,
                        clipped_value_loss, tanh_action, loss_mode, d_logstd, info, workspace=None):
-    """The loss half of a PPO / A2C minibatch for arbitrary network shapes; returns (d_mean (B, A), d_v (B, 1))."""
+    """The loss half of a PPO / A2C minibatch for arbitrary network shapes; returns (d_mean (B, A), d_v (B, 1)).
+    loss_mode LOSS_REINFORCE: v / rets / v_old / old_logp may be None and d_v is None."""
     B, A = int(mean.shape[0]), int(mean.shape[1])
+    critic = int(loss_mode) != LOSS_REINFORCE
     need = lib().trl_ppo_generic_losses_workspace(B, A)
     if need < 0:
         raise TrlError("ppo_generic_losses: unsupported sizes B=%d A=%d" % (B, A))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((need,), dtype=torch.float64, device=mean.device)
     d_mean = torch.empty((B, A), dtype=torch.float32, device=mean.device)
-    d_v = torch.empty((B, 1), dtype=torch.float32, device=mean.device)
+    d_v = torch.empty((B, 1), dtype=torch.float32, device=mean.device) if critic else None
     check(lib().trl_ppo_generic_losses_f32(
         dev_ptr(mean, name="mean"), dev_ptr(logstd, name="logstd"), dev_ptr(acts, name="acts"), dev_ptr(advs, name="advs"),
-        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v"), dev_ptr(rets, name="rets"),
+        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v", allow_none=not critic),
+        dev_ptr(rets, name="rets", allow_none=not critic),
         dev_ptr(v_old, name="v_old", allow_none=True), dev_ptr(adv_raw, torch.float64, "adv_raw"), float(n_global), B, A,
         float(clip_para), float(entropy_coeff), int(bool(clipped_value_loss)), int(bool(tanh_action)), int(loss_mode),
-        dev_ptr(d_mean, name="d_mean"), dev_ptr(d_v, name="d_v"), dev_ptr(d_logstd, name="d_logstd"),
+        dev_ptr(d_mean, name="d_mean"), dev_ptr(d_v, name="d_v", allow_none=not critic), dev_ptr(d_logstd, name="d_logstd"),
         dev_ptr(info, torch.float64, "info"), dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(mean.device)),
         "trl_ppo_generic_losses_f32")
     return d_mean, d_v
@@ -803,8 +806,10 @@ def ppo_generic_losses(mean, logstd, acts, advs, old_logp, v, rets, v_old, adv_r
 
 def cat_losses(logits, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, clip_para, entropy_coeff,
                clipped_value_loss, loss_mode, info, workspace=None):
-    """The loss half of a PPO / A2C minibatch for a categorical head; returns (d_logits (B, A), d_v (B, 1))."""
+    """The loss half of a PPO / A2C minibatch for a categorical head; returns (d_logits (B, A), d_v (B, 1)).
+    loss_mode LOSS_REINFORCE: v / rets / v_old / old_logp may be None and d_v is None."""
     B, A = int(logits.shape[0]), int(logits.shape[1])
+    critic = int(loss_mode) != LOSS_REINFORCE
     need = lib().trl_cat_losses_workspace(B, A)
     if need < 0:
         raise TrlError("cat_losses: unsupported sizes B=%d A=%d (2 <= A <= 64)" % (B, A))
@@ -813,13 +818,14 @@ def cat_losses(logits, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, 
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((need,), dtype=torch.float64, device=logits.device)
     d_logits = torch.empty((B, A), dtype=torch.float32, device=logits.device)
-    d_v = torch.empty((B, 1), dtype=torch.float32, device=logits.device)
+    d_v = torch.empty((B, 1), dtype=torch.float32, device=logits.device) if critic else None
     check(lib().trl_cat_losses_f32(
         dev_ptr(logits, name="logits"), dev_ptr(acts, name="acts"), dev_ptr(advs, name="advs"),
-        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v"), dev_ptr(rets, name="rets"),
+        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v", allow_none=not critic),
+        dev_ptr(rets, name="rets", allow_none=not critic),
         dev_ptr(v_old, name="v_old", allow_none=True), dev_ptr(adv_raw, torch.float64, "adv_raw"), float(n_global), B, A,
         float(clip_para), float(entropy_coeff), int(bool(clipped_value_loss)), int(loss_mode),
-        dev_ptr(d_logits, name="d_logits"), dev_ptr(d_v, name="d_v"), dev_ptr(info, torch.float64, "info"),
+        dev_ptr(d_logits, name="d_logits"), dev_ptr(d_v, name="d_v", allow_none=not critic), dev_ptr(info, torch.float64, "info"),
         dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(logits.device)), "trl_cat_losses_f32")
     return d_logits, d_v
 
@@ -833,8 +839,10 @@ def _gauss_sd_dims(head, what):
 
 def gauss_sd_losses(head, acts, advs, old_logp, v, rets, v_old, adv_raw, n_global, clip_para, entropy_coeff,
                     clipped_value_loss, tanh_action, loss_mode, info, workspace=None):
-    """The loss half of a PPO / A2C minibatch for a state-dependent-std Gaussian head; returns (d_head (B, 2A), d_v (B, 1))."""
+    """The loss half of a PPO / A2C minibatch for a state-dependent-std Gaussian head; returns (d_head (B, 2A), d_v (B, 1)).
+    loss_mode LOSS_REINFORCE: v / rets / v_old / old_logp may be None and d_v is None."""
     B, A = _gauss_sd_dims(head, "gauss_sd_losses")
+    critic = int(loss_mode) != LOSS_REINFORCE
     need = lib().trl_gauss_sd_losses_workspace(B, A)
     if need < 0:
         raise TrlError("gauss_sd_losses: unsupported sizes B=%d A=%d (1 <= A <= 32)" % (B, A))
@@ -843,13 +851,14 @@ def gauss_sd_losses(head, acts, advs, old_logp, v, rets, v_old, adv_raw, n_globa
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((need,), dtype=torch.float64, device=head.device)
     d_head = torch.empty((B, 2 * A), dtype=torch.float32, device=head.device)
-    d_v = torch.empty((B, 1), dtype=torch.float32, device=head.device)
+    d_v = torch.empty((B, 1), dtype=torch.float32, device=head.device) if critic else None
     check(lib().trl_gauss_sd_losses_f32(
         dev_ptr(head, name="head"), dev_ptr(acts, name="acts"), dev_ptr(advs, name="advs"),
-        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v"), dev_ptr(rets, name="rets"),
+        dev_ptr(old_logp, name="old_logp", allow_none=True), dev_ptr(v, name="v", allow_none=not critic),
+        dev_ptr(rets, name="rets", allow_none=not critic),
         dev_ptr(v_old, name="v_old", allow_none=True), dev_ptr(adv_raw, torch.float64, "adv_raw"), float(n_global), B, A,
         float(clip_para), float(entropy_coeff), int(bool(clipped_value_loss)), int(bool(tanh_action)), int(loss_mode),
-        dev_ptr(d_head, name="d_head"), dev_ptr(d_v, name="d_v"), dev_ptr(info, torch.float64, "info"),
+        dev_ptr(d_head, name="d_head"), dev_ptr(d_v, name="d_v", allow_none=not critic), dev_ptr(info, torch.float64, "info"),
         dev_ptr(workspace, torch.float64, "workspace"), stream_ptr(head.device)), "trl_gauss_sd_losses_f32")
     return d_head, d_v
 

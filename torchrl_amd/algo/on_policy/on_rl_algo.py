@@ -7,6 +7,7 @@ the reverse scan are HIP kernels (k_ppo.hip / k_gae.hip), nothing leaves the dev
 single pass over `one_iteration` minibatches; PPO / A2C / TRPO / V-MPO override it with their own loops."""
 import torch
 
+from ...networks.nets import ZeroNet
 from ..rl_algo import RLAlgo
 
 _LAST_ROW_KEYS = ("next_obs", "terminals", "time_limits")
@@ -29,6 +30,8 @@ class OnRLAlgo(RLAlgo):
         last = buf.last_sample(list(_LAST_ROW_KEYS))
         if getattr(buf, "_boot_fresh", False):                           # the fused rollout's value pass left V(next_obs) of
             bootstrap = buf._boot                                        # the last row (same parameters: nothing stepped since)
+        elif isinstance(self.vf, ZeroNet):                               # no critic (reinforce.py:20-21): V == 0, never called
+            bootstrap = torch.zeros(buf.env_nums, device=self.device)
         else:
             with torch.no_grad():
                 bootstrap = self.vf(last["next_obs"].to(self.device))

@@ -307,6 +307,10 @@ class VecOnPolicyCollector(VecCollector):
                               "is not reproduced -- noise_mode=%r is not built" % (self.noise_mode,))
         ps = self.pf.mlp2_spec() if hasattr(self.pf, "mlp2_spec") else None
         vs = self.vf.mlp2_spec() if hasattr(self.vf, "mlp2_spec") else None
+        # a ZeroNet critic (REINFORCE, reinforce.py:20-21: V == 0) has no layers: its shape checks are skipped, the routes
+        # below depend on the policy alone, `values` / the bootstrap are stored as zeros and no value forward is launched
+        from ..networks import nets as _nets
+        self._no_critic = isinstance(self.vf, _nets.ZeroNet)
         self._act = ops.net_layers(self.pf)[1]                              # (an `add_ln` net: its plan's activation, ops.net_plan)
         layers = ops.linear_layers(self.pf)
         head_w = int(layers[-1][0].shape[0])
@@ -318,7 +322,8 @@ class VecOnPolicyCollector(VecCollector):
         env_acts = int(getattr(self.env, "action_num", 0) or 0) if self._cat else self.env.act_dim
         if self._cat and not env_acts:
             raise _C.TrlError("a categorical policy needs an env with a Discrete action space")
-        if self._dims != (self.env.obs_dim, env_acts) or int(ops.linear_layers(self.vf)[0][0].shape[1]) != self.env.obs_dim:
+        if self._dims != (self.env.obs_dim, env_acts) or \
+                (not self._no_critic and int(ops.linear_layers(self.vf)[0][0].shape[1]) != self.env.obs_dim):
             raise _C.TrlError("policy / value input and output sizes %s do not match the env (%d obs, %d act)"
                               % (self._dims, self.env.obs_dim, self.env.act_dim))
         # the fused 2-layer forward (and the cooperative, normalised rollout) are instantiated for the benchmark shape
@@ -327,9 +332,10 @@ class VecOnPolicyCollector(VecCollector):
         # shapes the fused UPDATE kernels carry (trl_ppo_partial_stride > 0); anything else is collected by the per-step
         # launch sequence on the dense-layer kernels
         lib = _C.lib()
-        pair = ps is not None and vs is not None and vs[:2] == ps[:2] and vs[2] == 1 and vs[3] == ps[3] and \
-            os.environ.get("TRL_GENERIC_PPO") != "1"
-        mlp2 = pair and lib.trl_mlp2_forward_supported(ps[0], ps[1], ps[2]) and lib.trl_mlp2_forward_supported(ps[0], ps[1], 1)
+        pair = ps is not None and (self._no_critic or (vs is not None and vs[:2] == ps[:2] and vs[2] == 1 and vs[3] == ps[3])) \
+            and os.environ.get("TRL_GENERIC_PPO") != "1"
+        mlp2 = pair and lib.trl_mlp2_forward_supported(ps[0], ps[1], ps[2]) and \
+            (self._no_critic or lib.trl_mlp2_forward_supported(ps[0], ps[1], 1))
         self._mlp2 = ps if mlp2 else None                                   # fused 2-layer forward kernel usable
         # (TRL_NO_RT_ROLLOUT=1 switches the RUNTIME-dims instantiations off for A/B measurements; the compile-time benchmark
         # shape -- the one the fused forward is instantiated for -- keeps its rollout kernel)
@@ -412,13 +418,13 @@ class VecOnPolicyCollector(VecCollector):
             a.norm_update = int(update)
             a.normalize_partial_reset = int(bool(getattr(env, "normalize_partial_reset", False)))
         a.pf_params = self.pf.flat_params().data_ptr()
-        a.vf_params = self.vf.flat_params().data_ptr()
+        a.vf_params = None if self._no_critic else self.vf.flat_params().data_ptr()   # (NULL: the zero-storing value pass)
         # The rollout reads the policy only; the value function may still be in the hands of the previous epoch's critic
         # updates on another stream (algo/on_policy/ppo.py: two update chains): the value pass behind the rollout waits
         # for their end, the rollout itself does not.
         from ..networks import nets as _nets
         _nets.settle(self.pf, env.device)
-        vf_ev = _nets.pending_event(self.vf)
+        vf_ev = None if self._no_critic else _nets.pending_event(self.vf)
         if vf_ev is not None and store:
             # ... and that chain still READS the stored observations: a rollout that rewrites the whole ring gets the
             # shadow `obs` tensor (swapped in here, before the pointers are taken) and runs beside it; one that rewrites
@@ -543,7 +549,9 @@ class VecOnPolicyCollector(VecCollector):
             N, dev = env.env_nums, env.device
             f = lambda *shape: torch.empty(*shape, device=dev)
             W = 1 if self._cat else A                                       # stored action width
-            sb = self._sb = {"N": N, "mean": f(N, self._head_w), "eps": f(N, A), "nxt_raw": f(N, D), "v_next": f(N, 1),
+            # (no critic: V(next_obs) == 0 is this buffer, zeroed once -- nothing ever writes it)
+            v_next = torch.zeros(N, 1, device=dev) if self._no_critic else f(N, 1)
+            sb = self._sb = {"N": N, "mean": f(N, self._head_w), "eps": f(N, A), "nxt_raw": f(N, D), "v_next": v_next,
                              "done": f(N, 1), "any": torch.zeros(1, dtype=torch.int32, device=dev),
                              # rows used when nothing is stored (evaluation)
                              "obs": f(N, D), "next_obs": f(N, D), "acts": f(N, W), "values": f(N, 1), "rewards": f(N, 1),
@@ -567,7 +575,10 @@ class VecOnPolicyCollector(VecCollector):
             r = sb
         r["obs"].copy_(ob)
         mean = self._forward(self.pf, ob, self._head_w, out=sb["mean"])
-        self._forward(self.vf, ob, 1, out=r["values"])
+        if self._no_critic:
+            r["values"].zero_()
+        else:
+            self._forward(self.vf, ob, 1, out=r["values"])
         if self._cat:
             # `mean` holds the logits.  noise_t: this step's (N,) uniforms drawn up front (captured rollout); None: the
             # launch draws the uniform of (seed, global step, global env index) itself -- the same values.  Host envs get
@@ -601,7 +612,8 @@ class VecOnPolicyCollector(VecCollector):
         self._env_advance(env, env_act, raw_next, r["rewards"], sb["done"], r["time_limits"])
         if nz is not None:
             nz.update_filt(raw_next, update=env.training, out=r["next_obs"])            # NormObs.observation
-        self._forward(self.vf, r["next_obs"], 1, out=sb["v_next"])
+        if not self._no_critic:
+            self._forward(self.vf, r["next_obs"], 1, out=sb["v_next"])
         sb["any"].zero_()
         _C.onpolicy_bookkeep(r["rewards"], sb["done"], sb["v_next"], self.discount, r["terminals"], env.cur_step,
                              env.ep_return, self.max_episode_frames if max_frames is None else max_frames, self._mask,

@@ -175,8 +175,9 @@ __global__ __launch_bounds__(PG_THREADS) void cat_losses_kernel(CatLossDev a) {
     }
   }
   // ---- value: loss and d/d(v) ----
+  const bool critic = a.loss_mode != TRL_LOSS_REINFORCE;
   float vv = 0.0f, vl = 0.0f;
-  if (valid) {
+  if (valid && critic) {
     vv = a.v[b];
     float dv;
     pg_value_loss(vv, a.rets[b], a.v_old, b, a.clip_para, a.clipped_value_loss, inv_b, vl, dv);
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(PG_THREADS) void cat_losses_kernel(CatLossDev a) {
   double* out = a.partial + (size_t)blockIdx.x * (1 + PG_SCAL);
   const double hs = pg_block_reduce((double)H, false, smem);
   if (threadIdx.x == 0) out[0] = hs;
-  pg_write_scalars(out + 1, valid, lp, ratio, s1, s2, vl, vv, smem);
+  pg_write_scalars(out + 1, valid, lp, ratio, s1, s2, vl, vv, smem, critic);
 }
 
 extern "C" int trl_cat_losses_workspace(int B, int A) {
@@ -200,9 +201,8 @@ extern "C" int trl_cat_losses_f32(const float* logits, const float* acts, const 
                                   int clipped_value_loss, int loss_mode, float* d_logits, float* d_v, double* info,
                                   double* workspace, void* stream) {
   TRL_REQUIRE(B > 0 && A >= 2 && A <= PG_MAX_A, "bad sizes (2 <= A <= 64)");
-  TRL_REQUIRE(logits && acts && advs && v && rets && adv_raw && d_logits && d_v && info && workspace, "null pointer");
-  TRL_REQUIRE(loss_mode == TRL_LOSS_A2C || old_logp, "the clipped surrogate needs old_logp");
-  TRL_REQUIRE(!clipped_value_loss || v_old, "the clipped value loss needs the old values");
+  TRL_REQUIRE(logits && acts && advs && adv_raw && d_logits && info && workspace, "null pointer");
+  PG_REQUIRE_MODE(loss_mode, old_logp, v, rets, v_old, d_v, clipped_value_loss);
   TRL_REQUIRE(n_global >= 2.0, "need at least two samples for the advantage statistics");
   CatLossDev a{};
   a.logits = logits; a.acts = acts; a.advs = advs; a.old_logp = old_logp; a.v = v; a.rets = rets; a.v_old = v_old;

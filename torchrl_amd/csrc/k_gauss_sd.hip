@@ -141,8 +141,9 @@ __global__ __launch_bounds__(PG_THREADS) void gauss_sd_losses_kernel(GaussSdLoss
     }
   }
   // ---- value: loss and d/d(v) ----
+  const bool critic = a.loss_mode != TRL_LOSS_REINFORCE;
   float vv = 0.0f, vl = 0.0f;
-  if (valid) {
+  if (valid && critic) {
     vv = a.v[b];
     float dv;
     pg_value_loss(vv, a.rets[b], a.v_old, b, a.clip_para, a.clipped_value_loss, inv_b, vl, dv);
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(PG_THREADS) void gauss_sd_losses_kernel(GaussSdLoss
     const double r = pg_block_reduce(vec[k], k >= 5, smem);
     if (threadIdx.x == 0) out[k] = r;
   }
-  pg_write_scalars(out + SD_VEC, valid, lp, ratio, s1, s2, vl, vv, smem);
+  pg_write_scalars(out + SD_VEC, valid, lp, ratio, s1, s2, vl, vv, smem, critic);
 }
 
 // one block: fold the block partials in order into the info row (trl_ppo_reduce_f32's layout); n_elem = B * A
@@ -199,9 +200,8 @@ extern "C" int trl_gauss_sd_losses_f32(const float* head, const float* acts, con
                                        int clipped_value_loss, int tanh_action, int loss_mode, float* d_head, float* d_v,
                                        double* info, double* workspace, void* stream) {
   TRL_REQUIRE(B > 0 && A >= 1 && A <= SD_MAX_A, "bad sizes (1 <= A <= 32)");
-  TRL_REQUIRE(head && acts && advs && v && rets && adv_raw && d_head && d_v && info && workspace, "null pointer");
-  TRL_REQUIRE(loss_mode == TRL_LOSS_A2C || old_logp, "the clipped surrogate needs old_logp");
-  TRL_REQUIRE(!clipped_value_loss || v_old, "the clipped value loss needs the old values");
+  TRL_REQUIRE(head && acts && advs && adv_raw && d_head && info && workspace, "null pointer");
+  PG_REQUIRE_MODE(loss_mode, old_logp, v, rets, v_old, d_v, clipped_value_loss);
   TRL_REQUIRE(n_global >= 2.0, "need at least two samples for the advantage statistics");
   GaussSdLossDev a{};
   a.head = head; a.acts = acts; a.advs = advs; a.old_logp = old_logp; a.v = v; a.rets = rets; a.v_old = v_old;

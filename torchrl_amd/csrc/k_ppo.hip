@@ -1532,9 +1532,14 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HE
                   HEADS[head].tag, p->D, p->H, p->A, p->act, HEADS[head].a_min, HEADS[head].a_max);
     return TRL_EUNSUPPORTED;
   }
-  TRL_REQUIRE(p->obs && p->acts && p->advs && p->rets, "null rollout tensor");
-  TRL_REQUIRE(p->loss_mode == TRL_LOSS_PPO_CLIP || p->loss_mode == TRL_LOSS_A2C, "unknown loss_mode");
-  TRL_REQUIRE(p->loss_mode == TRL_LOSS_A2C || p->old_logp, "the clipped surrogate needs old_logp");
+  // TRL_LOSS_REINFORCE: no critic anywhere -- an all-policy launch only, whose workgroups (ppo_wave_pass<IS_PF = true>) load
+  // obs, acts, advs, adv_raw, pf_params and old_logp where it is set; rets / old_values / vf_params are the value pass's
+  const bool reinforce = p->loss_mode == TRL_LOSS_REINFORCE;
+  TRL_REQUIRE(p->obs && p->acts && p->advs && (p->rets || reinforce), "null rollout tensor");
+  TRL_REQUIRE(p->loss_mode == TRL_LOSS_PPO_CLIP || p->loss_mode == TRL_LOSS_A2C || reinforce, "unknown loss_mode");
+  TRL_REQUIRE(!reinforce || p->n_wg_pf == p->n_wg, "TRL_LOSS_REINFORCE runs in an all-policy launch only (n_wg_pf == n_wg)");
+  TRL_REQUIRE(!reinforce || !p->clipped_value_loss, "TRL_LOSS_REINFORCE has no value loss: clipped_value_loss must be 0");
+  TRL_REQUIRE(p->loss_mode != TRL_LOSS_PPO_CLIP || p->old_logp, "the clipped surrogate needs old_logp");
   TRL_REQUIRE(!p->clipped_value_loss || p->old_values, "the clipped value loss needs old_values");
   TRL_REQUIRE(p->adv_raw && (p->pf_params || p->vf_params) && p->partial && p->scal_partial, "null pointer");
   TRL_REQUIRE(p->rows_mb > 0 && p->N > 0, "empty minibatch");
@@ -1553,7 +1558,8 @@ static int ppo_grad_launch(const trl_ppo_batch_t* p, void* stream, int head = HE
   d.old_logp = p->old_logp; d.row_idx = p->row_idx; d.rows_mb = p->rows_mb; d.N = p->N;
   d.adv_raw = p->adv_raw; d.n_global = p->n_global; d.pf_params = p->pf_params; d.vf_params = p->vf_params;
   d.clip_para = p->clip_para; d.entropy_coeff = p->entropy_coeff;
-  d.clipped_value_loss = p->clipped_value_loss; d.tanh_action = p->tanh_action; d.loss_mode = p->loss_mode;
+  d.clipped_value_loss = p->clipped_value_loss; d.tanh_action = p->tanh_action;
+  d.loss_mode = reinforce ? TRL_LOSS_A2C : p->loss_mode;       // (the policy pass of the two is one and the same)
   d.partial = p->partial; d.scal_partial = p->scal_partial; d.n_wg = p->n_wg;
   d.n_pf = resolve_pf_wgs(p->n_wg, p->n_wg_pf);
   d.D = D; d.A = A;
@@ -1660,7 +1666,9 @@ static int launch_reduce_adam(const float* partial, const double* scal_partial, 
   int rc = fill_adam(adam, d);
   if (rc) return rc;
   const int p_pf = ppo_p_pf(D, H, A, head), p_vf = ppo_p_vf(D, H);
-  TRL_REQUIRE(adam->n_groups == 2 && adam->group_sizes[0] == p_pf && adam->group_sizes[1] == p_vf,
+  // (a policy-only optimiser -- REINFORCE -- steps through the policy's `_net` fold with its single group)
+  TRL_REQUIRE((adam->n_groups == 2 && adam->group_sizes[0] == p_pf && adam->group_sizes[1] == p_vf) ||
+              (only_net == 0 && !xr && adam->n_groups == 1 && adam->group_sizes[0] == p_pf),
               "optimiser groups must be [policy | value] of this shape");
   TRL_REQUIRE(adam->grads == grads, "adam->grads must be the reduce output");
   TRL_REQUIRE(!xr || p_pf + p_vf <= TRL_XR_CAP_GRAD, "gradient exceeds the peer buffer");

@@ -62,8 +62,9 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDe
     if (lane == 0) s_dls[wave][o] = dls;
   }
   // ---- value: loss and d/d(v) ----
+  const bool critic = a.loss_mode != TRL_LOSS_REINFORCE;
   float vv = 0.0f, l = 0.0f;
-  if (valid) {
+  if (valid && critic) {
     vv = a.v[b];
     const float R = a.rets[b];
     float dv;
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(PG_THREADS) void ppo_generic_losses_kernel(PpoGenDe
     for (int w = 0; w < PG_THREADS / 64; ++w) s += s_dls[w][threadIdx.x];
     out[threadIdx.x] = (double)s;
   }
-  pg_write_scalars(out + A, valid, lp, ratio, s1, s2, l, vv, smem);
+  pg_write_scalars(out + A, valid, lp, ratio, s1, s2, l, vv, smem, critic);
 }
 
 // one block: fold the block partials in order; d_logstd (A) and the info row (trl_ppo_reduce_f32's layout).
@@ -141,10 +142,8 @@ extern "C" int trl_ppo_generic_losses_f32(const float* mean, const float* logstd
                                           float* d_mean, float* d_v, float* d_logstd, double* info, double* workspace,
                                           void* stream) {
   TRL_REQUIRE(B > 0 && A > 0 && A <= PG_MAX_A, "bad sizes (1 <= A <= 64)");
-  TRL_REQUIRE(mean && logstd && acts && advs && v && rets && adv_raw && d_mean && d_v && d_logstd && info && workspace,
-              "null pointer");
-  TRL_REQUIRE(loss_mode == TRL_LOSS_A2C || old_logp, "the clipped surrogate needs old_logp");
-  TRL_REQUIRE(!clipped_value_loss || v_old, "the clipped value loss needs the old values");
+  TRL_REQUIRE(mean && logstd && acts && advs && adv_raw && d_mean && d_logstd && info && workspace, "null pointer");
+  PG_REQUIRE_MODE(loss_mode, old_logp, v, rets, v_old, d_v, clipped_value_loss);
   TRL_REQUIRE(n_global >= 2.0, "need at least two samples for the advantage statistics");
   PpoGenDev a{};
   a.mean = mean; a.logstd = logstd; a.acts = acts; a.advs = advs; a.old_logp = old_logp; a.v = v; a.rets = rets;

@@ -847,6 +847,25 @@ __global__ __launch_bounds__(VP_THREADS, RT ? 1 : 2) void value_pass_kernel(Valu
   }
 }
 
+// The value pass of a rollout WITHOUT a critic (trl_rollout_t.vf_params == NULL: REINFORCE's ZeroNet, V == 0): what remains of
+// value_pass_kernel is its stores.  values of the n_steps x N stored cells (same ring addressing; the rollout left its
+// over-length markers there) and boot[0 .. N) become 0.0f, the rewards stay as the rollout wrote them (the bootstrap
+// would add discount * 0), and the header goes to the host first, as in the value pass: posted writes, issued before the
+// cell stores.  Grid-stride over plain vector stores; nothing is read but the header words.
+__global__ __launch_bounds__(256) void zero_value_pass_kernel(float* __restrict__ values, int rows, int top, int N, int n_steps,
+                                                              float* __restrict__ boot, uint32_t* __restrict__ pub_dst,
+                                                              const uint32_t* __restrict__ pub_src, int64_t pub_words) {
+  const int64_t e0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  for (int64_t e = e0; e < pub_words; e += stride) pub_dst[e] = pub_src[e];
+  const int64_t M = (int64_t)n_steps * N;
+  for (int64_t m = e0; m < M; m += stride) {
+    const int t = (int)(m / N), n = (int)(m - (int64_t)t * N);
+    values[(size_t)((top + t) % rows) * N + n] = 0.0f;
+  }
+  if (boot)
+    for (int64_t n = e0; n < N; n += stride) boot[n] = 0.0f;
+}
+
 // Envs the normalised (cooperative) rollout can carry: its workgroups rendezvous once per step, so all of them
 // must be resident at the same time.
 template <int D, int H, int A, int ACT>
@@ -880,7 +899,12 @@ static int launch_rollout(const RolloutDev& d, hipStream_t s, hipEvent_t value_w
     hipLaunchKernelGGL((rollout_kernel<D, H, A, ACT, false>), dim3(n_wg + (e.stg_n4 ? RO_STAGERS : 0)), dim3(RO_THREADS), 0, s, e);
   }
   TRL_LAUNCH_CHECK();
-  if (d.store) {
+  if (d.store && !d.vf_params) {                    // no critic: nothing to wait for, nothing to forward
+    const int64_t blocks = ((int64_t)d.n_steps * d.N + 255) / 256;
+    hipLaunchKernelGGL(zero_value_pass_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s, d.values, d.rows,
+                       d.top, d.N, d.n_steps, d.boot, d.pub_dst, d.pub_src, d.pub_words);
+    TRL_LAUNCH_CHECK();
+  } else if (d.store) {
     if (value_wait) {                               // the value function's parameters are still being stepped on another stream
       hipError_t e = hipStreamWaitEvent(s, value_wait, 0);
       if (e != hipSuccess) { trl_set_error("rollout: hipStreamWaitEvent(value_wait_event): %s", hipGetErrorString(e)); return (int)e; }
@@ -927,7 +951,7 @@ extern "C" int trl_rollout_sd_supported(int D, int H, int A, int act) { return h
 // first global env index; p->A is the number of actions (HEAD_CAT) or of action dims
 static int rollout_synth(const trl_rollout_t* p, void* stream, int head, int64_t cat_seed = 0, int64_t cat_env0 = 0) {
   if (!p) { trl_set_error("rollout: null descriptor"); return TRL_EINVAL; }
-  TRL_REQUIRE(p->pf_params && p->vf_params && p->env_A && p->env_B, "null network / env pointer");
+  TRL_REQUIRE(p->pf_params && p->env_A && p->env_B, "null network / env pointer");   // (vf_params NULL: no critic)
   TRL_REQUIRE(p->cur_obs && p->t_env && p->cur_step && p->episode_idx && p->ep_return, "null env state pointer");
   const bool all_ring = p->obs && p->next_obs && p->acts && p->values && p->rewards && p->terminals && p->time_limits;
   const bool no_ring = !p->obs && !p->next_obs && !p->acts && !p->values && !p->rewards && !p->terminals && !p->time_limits;

@@ -36,7 +36,7 @@ __device__ __forceinline__ PgAdvNorm pg_adv_norm(const double* __restrict__ adv_
 __device__ __forceinline__ void pg_surrogate(bool valid, float lp, const float* __restrict__ old_logp, int b, float advn,
                                              int loss_mode, float clip_para, float inv_b, float& ratio, float& s1,
                                              float& s2, float& g_lp) {
-  if (loss_mode == TRL_LOSS_A2C) {                                // L = -mean(log pi * adv) (a2c.py:69-70)
+  if (loss_mode == TRL_LOSS_A2C || loss_mode == TRL_LOSS_REINFORCE) {   // L = -mean(log pi * adv) (a2c.py:69-70, reinforce.py:59)
     ratio = 1.0f;
     s1 = s2 = lp * advn;
     g_lp = valid ? -advn * inv_b : 0.0f;
@@ -67,8 +67,9 @@ __device__ __forceinline__ void pg_value_loss(float vv, float R, const float* __
 }
 
 // the PG_SCAL scalar statistics of a block into out[0 .. PG_SCAL) (every thread of the block calls this)
+// critic false (TRL_LOSS_REINFORCE, block-uniform): the five value-side entries are stored as 0.0 without a reduction
 __device__ __forceinline__ void pg_write_scalars(double* __restrict__ out, bool valid, float lp, float ratio, float s1,
-                                                 float s2, float l, float vv, double* smem) {
+                                                 float s2, float l, float vv, double* smem, bool critic = true) {
   const double ninf = -INFINITY;
   const double vals[PG_SCAL] = {valid ? (double)lp : 0.0, valid ? (double)lp * lp : 0.0, valid ? (double)lp : ninf,
                                 valid ? -(double)lp : ninf, valid ? (double)ratio : ninf, valid ? -(double)ratio : ninf,
@@ -77,10 +78,26 @@ __device__ __forceinline__ void pg_write_scalars(double* __restrict__ out, bool 
   const bool is_max[PG_SCAL] = {false, false, true, true, true, true, false, false, false, false, true, true};
 #pragma unroll
   for (int k = 0; k < PG_SCAL; ++k) {
+    if (k >= 7 && !critic) {
+      if (threadIdx.x == 0) out[k] = 0.0;
+      continue;
+    }
     const double r = pg_block_reduce(vals[k], is_max[k], smem);
     if (threadIdx.x == 0) out[k] = r;
   }
 }
+
+// what the three loss entry points check alike: TRL_LOSS_REINFORCE runs without v / rets / v_old / d_v / old_logp
+#define PG_REQUIRE_MODE(loss_mode, old_logp, v, rets, v_old, d_v, clipped_value_loss)                                   \
+  do {                                                                                                                  \
+    TRL_REQUIRE((loss_mode) == TRL_LOSS_PPO_CLIP || (loss_mode) == TRL_LOSS_A2C || (loss_mode) == TRL_LOSS_REINFORCE,   \
+                "unknown loss_mode");                                                                                   \
+    TRL_REQUIRE((loss_mode) == TRL_LOSS_REINFORCE || ((v) && (rets) && (d_v)), "null pointer");                         \
+    TRL_REQUIRE((loss_mode) != TRL_LOSS_REINFORCE || !(clipped_value_loss),                                             \
+                "TRL_LOSS_REINFORCE has no value loss: clipped_value_loss must be 0");                                  \
+    TRL_REQUIRE((loss_mode) != TRL_LOSS_PPO_CLIP || (old_logp), "the clipped surrogate needs old_logp");                \
+    TRL_REQUIRE(!(clipped_value_loss) || (v_old), "the clipped value loss needs the old values");                       \
+  } while (0)
 
 // Second pass (one block, fixed order): partial is [blocks][n_vec + PG_SCAL]; the n_vec leading sums go to vec_out (as
 // floats) and the scalars to the info row (trl_ppo_reduce_f32's layout).  logstd given (n_vec == A, Gaussian head): its

@@ -49,6 +49,8 @@ def settle(net, device=None):
     """Make the current stream wait for whatever is still writing `net`'s parameters on another stream.  Inside a stream
     capture this does nothing: the event was recorded outside the capture, and every capture site waits on the current
     stream before it captures or replays (`_FusedPPO._run_chains` / `run`, `VecOnPolicyCollector._rollout_per_step`)."""
+    if isinstance(net, ZeroNet):                                     # no parameters: nothing can be stepping them
+        return
     ev = _PENDING.get(net)
     if ev is not None and not torch.cuda.is_current_stream_capturing():
         torch.cuda.current_stream(device).wait_event(ev)
@@ -287,5 +289,8 @@ class FlattenBootstrappedNet(BootstrappedNet):
 
 
 class ZeroNet(nn.Module):
+    """The vacant critic of REINFORCE (torchrl/networks/nets.py, reinforce.py:20-21): V == 0.  The collector, the epoch
+    post-processing and `settle` recognise it by type and never call it."""
+
     def forward(self, x):
         return torch.zeros(1)
