@@ -84,7 +84,13 @@ template <int D, int H, int A> struct WvShape {
   static constexpr int XSC_PF = 3 * H + 32, XSC_VF = 4 * H + 16;
   static constexpr int XCH_PF = WV_WAVES * (XS_PF * 256 + XSC_PF), XCH_VF = WV_WAVES * (XS_VF * 256 + XSC_VF);
   static constexpr int XCH = XCH_PF > XCH_VF ? XCH_PF : XCH_VF;
-  static constexpr int LDS_FLOATS = MAIN > XCH ? MAIN : XCH;
+  // set-up image (a region of its own behind both): the flat parameter block without W2, [W1 | b1 | b2 | W3 | b3 | logstd]
+  // at the actual dims, loaded with coalesced dword loads (element tid + 256 k) and read back per lane as register operands;
+  // sized for the largest head (8 rows + b3 + logstd) and rounded to whole 256-float load rounds
+  static constexpr int O_IMG = MAIN > XCH ? MAIN : XCH;
+  static constexpr int IMG_HEAD = 8 * H + 16;
+  static constexpr int IMG = (H * D + 2 * H + IMG_HEAD + WV_THREADS - 1) / WV_THREADS * WV_THREADS;
+  static constexpr int LDS_FLOATS = O_IMG + IMG;
 };
 
 // State-dependent-std head (SD): up to 16 head rows [mean | log_std] and no logstd tail -- a partial row of its own
@@ -93,6 +99,9 @@ template <int D, int H, int A> struct WvShape {
 template <int D, int H, int A> struct WvShapeSD : WvShape<D, H, A> {
   static constexpr int P_PF_SD = H * D + H + H * H + H + 2 * A * H + 2 * A, P_VF = MlpFlat<D, H, 1>::P_VF;
   static constexpr int P_STRIDE = ((P_PF_SD > P_VF ? P_PF_SD : P_VF) + 63) & ~63;
+  static constexpr int IMG_HEAD = 16 * H + 16;      // 16 head rows + b3
+  static constexpr int IMG = (H * D + 2 * H + IMG_HEAD + WV_THREADS - 1) / WV_THREADS * WV_THREADS;
+  static constexpr int LDS_FLOATS = WvShape<D, H, A>::O_IMG + IMG;
 };
 template <int D, int H, int A, int HEAD> struct WvPick { using T = WvShape<D, H, A>; };
 template <int D, int H, int A> struct WvPick<D, H, A, HEAD_SD> { using T = WvShapeSD<D, H, A>; };
@@ -161,10 +170,10 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
   float* DZ2S = scr + S::O_DZ2;
   float* DOS = scr + S::O_DO;
 
-  // The first tile's inputs sit behind a dependent pair of loads (row index -> cells): they are requested before
-  // anything else, so that they travel while the weights are staged.
-  // (requested before anything else: behind the set-up's barrier these two loads were a memory round trip of their own --
-  // a load cannot be hoisted across a barrier by the compiler)
+  // The first tile's inputs sit behind a dependent pair of loads (row index -> cells): the index is requested before
+  // anything else and the cells in front of the set-up's LDS stores, so that they travel while the weights are staged.
+  // (behind the set-up's barrier these two loads were a memory round trip of their own -- a load cannot be hoisted
+  // across a barrier by the compiler)
   const double adv_s1 = IS_PF ? a.adv_raw[0] : 0.0, adv_s2 = IS_PF ? a.adv_raw[1] : 0.0;
   const int B = a.rows_mb * a.N;
   const int n_tiles = (B + 15) / 16;
@@ -285,36 +294,30 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
       fetch_row(nt + tile_stride);
     }
   };
+  // ---- one-time setup ----
+  // Order of the set-up's loads: the first tile's row index, then everything that needs the kernel arguments only (W2
+  // twice, the parameter image), and only then the first tile's cells, which wait for the index.  The cells' round trip
+  // ends under the LDS stores, the barrier and the operand reads below.
+  int r0 = 0, c0 = 0;
+  int64_t ridx0 = 0;
   if constexpr (CONTIG) {
     const int t0 = __builtin_amdgcn_readfirstlane(tile);
     const int ts = __builtin_amdgcn_readfirstlane(tile_stride);
     st_r = ts / tpr; st_c = ts - st_r * tpr;
-    int r0 = t0 / tpr, c0 = t0 - (t0 / tpr) * tpr;
-    fetch_contig(load_ridx(r0), r0, c0);                              // tile t (dependent pair of loads, once per kernel)
-    p1r = r0; p1c = c0;
-    pos_advance(p1r, p1c);
-    ridx1 = load_ridx(p1r);
-    p2r = p1r; p2c = p1c;
-    pos_advance(p2r, p2c);
-    ridx2 = load_ridx(p2r);
+    r0 = t0 / tpr; c0 = t0 - (t0 / tpr) * tpr;
+    ridx0 = load_ridx(r0);
   } else {
     fetch_row(tile);
-    const int64_t p0 = (tile * 16 + j < B) ? ridx_nn * a.N + e_nn : 0;
-    fetch_inputs(p0, tile * 16);
-    fetch_row(tile + tile_stride);
   }
-  // ---- one-time setup ----
+  __builtin_amdgcn_sched_barrier(0);
   constexpr int NV = H * H / (4 * WV_THREADS);    // all loads in flight before the first LDS store
   f32x4 wv[NV], wt[NV];
   const int tc = tid & 63, tq = tid >> 6;
-  const float bias1 = tid < H ? gp[F_B1 + tid] : 0.0f, bias2 = tid < H ? gp[F_B2 + tid] : 0.0f;
   {
     // W2 is staged twice, row-major (forward A operand: W2[own row][k]) and transposed (backward A operand: W2[k][own
     // column]).  Both copies are written with 16-byte LDS stores: the transposed one from a second, column-wise read of
     // the 16 KB block (coalesced along the column index, served by L1 / L2) -- scattering the row-wise registers instead
     // took 64 four-byte stores per thread whose 16 lanes of a row hit two banks.
-    // Every global load of the set-up (these, and the register-resident weight slices below) is requested before the
-    // first LDS store waits for one of them.
     static_assert(WV_THREADS == 256 && H == 64, "the transposed staging maps (column, 4 rows) onto 256 threads");
     // (runtime dims: the value block starts P_PF floats into the flat buffer, which is a multiple of 4 only for even A)
     const bool w2_al = !RT || ((reinterpret_cast<uintptr_t>(gp + F_W2) & 15) == 0);
@@ -331,64 +334,129 @@ __device__ void ppo_wave_pass(const PpoDev& a, float* lds, int wg_in_net, int n_
 #pragma unroll
       for (int x = 0; x < 4; ++x) wt[t][x] = gp[F_W2 + (4 * (tq + 4 * t) + x) * H + tc];       // W2[r4 + x][column tc]
   }
-  for (int e = lane; e < 16 * LDT; e += 64) DOS[e] = 0.0f;       // dout rows >= O stay zero
-  // register-resident A operands, lane (i, g): k index of MFMA step (slice sl, r) is feature 16 sl + 4 g + r
-  float w1[4][5], w3h[4][4], w3t[4][4];
-  float w1b[4][4];                                   // WIDE: W1[row][16 + 4g + r]
+  // The parameter image: the two runs of the flat block on either side of W2, [0, F_W2) and [F_B2, F_END), as one
+  // sequence of n_img floats; thread tid loads elements tid + 256 k with dword loads (the value block is 16-byte aligned
+  // only for some A).  An element past the end re-reads the block's last float -- nothing outside [0, F_END) is touched --
+  // and lands in the image's rounding tail, which no lane reads.
+  constexpr int NI = S::IMG / WV_THREADS;
+  const int n_img = F_W2 + (F_END - F_B2);
+  float im[NI];
 #pragma unroll
-  for (int so = 0; so < 4; ++so) {
-    const int row = 16 * so + i;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) w1[so][r] = fv[r] ? gp[F_W1 + row * Dr + (fv[r] ? 4 * g + r : 0)] : 0.0f;
-    w1[so][4] = (g == 0 && f16) ? gp[F_W1 + row * Dr + (f16 ? 16 : 0)] : 0.0f;
-    if constexpr (WIDE) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w1b[so][r] = fv2[r] ? gp[F_W1 + row * Dr + (fv2[r] ? 16 + 4 * g + r : 0)] : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (SDP) {
-        const int o = 4 * g + r;
-        w3h[so][r] = sd_has(i) ? gp[F_W3 + (sd_has(i) ? sd_row(i) : 0) * H + 16 * so + 4 * g + r] : 0.0f;   // head: W3[row of tile row i][k]
-        w3t[so][r] = sd_has(o) ? gp[F_W3 + (sd_has(o) ? sd_row(o) : 0) * H + row] : 0.0f;                   // dH2: W3[row of tile row o][own f]
-      } else if constexpr (IS_PF) {
-        w3h[so][r] = (i < O) ? gp[F_W3 + (i < O ? i : 0) * H + 16 * so + 4 * g + r] : 0.0f;     // head: W3[o = i][k]
-        const int o = 4 * g + r;
-        w3t[so][r] = (o < O) ? gp[F_W3 + (o < O ? o : 0) * H + row] : 0.0f;                     // dH2: W3[k = o][own f]
-      } else {
-        w3h[so][r] = gp[F_W3 + 16 * so + 4 * g + r];                                            // per-lane head weights
-        w3t[so][r] = 0.0f;
-      }
-    }
+  for (int k = 0; k < NI; ++k) {
+    const int e = tid + WV_THREADS * k, ec = e < n_img ? e : n_img - 1;
+    im[k] = gp[ec < F_W2 ? ec : ec + H * H];
   }
-  // per-lane constants of the lane's 4 outputs o = 4g + r (policy)
-  float lsv[4], ivv[4], b3v[4], lspass[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o = 4 * g + r;
-    const float raw = (IS_PF && !CAT && !SDP && o < O) ? gp[F_LS + (o < O ? o : 0)] : 0.0f;
-    lsv[r] = fminf(fmaxf(raw, -20.0f), 2.0f);                   // continuous_policy.py:8-9,185
-    ivv[r] = __expf(-2.0f * lsv[r]);
-    lspass[r] = (raw >= -20.0f && raw <= 2.0f) ? 1.0f : 0.0f;   // clamp passes gradient inside [-20, 2]
-    if constexpr (SDP) b3v[r] = sd_has(o) ? gp[F_B3 + (sd_has(o) ? sd_row(o) : 0)] : 0.0f;      // (lsv / ivv are per tile, see the loop)
-    else b3v[r] = (o < O) ? gp[F_B3 + (o < O ? o : 0)] : 0.0f;
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (CONTIG) {
+    fetch_contig(ridx0, r0, c0);                                      // tile t (dependent pair of loads, once per kernel)
+    p1r = r0; p1c = c0;
+    pos_advance(p1r, p1c);
+    ridx1 = load_ridx(p1r);
+    p2r = p1r; p2c = p1c;
+    pos_advance(p2r, p2c);
+    ridx2 = load_ridx(p2r);
+  } else {
+    const int64_t p0 = (tile * 16 + j < B) ? ridx_nn * a.N + e_nn : 0;
+    fetch_inputs(p0, tile * 16);
+    fetch_row(tile + tile_stride);
   }
-  const float vb3 = IS_PF ? 0.0f : gp[F_B3];
 #ifdef TRL_EXP_CLK
-  // the set-up split: 22 = every global load issued, 23 = all of them returned (the latency no ready-made operand image can
-  // remove; it includes the first tile's dependent pair), 0 = the work behind them (LDS stores, barrier, f64 constants)
+  // the set-up split: 22 = every global load issued, 23 = all of them returned (it includes the first tile's dependent
+  // pair), 0 = the work behind them (LDS stores, barrier, operand reads from the image, f64 constants)
   WCLK(22)
   __builtin_amdgcn_s_waitcnt(0);
   WCLK(23)
 #endif
+  for (int e = lane; e < 16 * LDT; e += 64) DOS[e] = 0.0f;       // dout rows >= O stay zero
 #pragma unroll
   for (int t = 0; t < NV; ++t) {
     const int e = 4 * (tid + WV_THREADS * t), r = e / H, c = e - r * H;
     *reinterpret_cast<f32x4*>(W2F + r * LDW + c) = wv[t];
     *reinterpret_cast<f32x4*>(W2B + tc * LDW + 4 * (tq + 4 * t)) = wt[t];
   }
-  if (tid < H) { lds[S::O_B1 + tid] = bias1; lds[S::O_B2 + tid] = bias2; }
+  // the image, and from its registers b1 | b2 (adjacent in the image: elements [F_B1, F_B1 + 2H)) to their place
+  float* img = lds + S::O_IMG;
+  constexpr int KB_LO = H * (WIDE ? 18 : RT ? 2 : D) / WV_THREADS, KB_HI = (H * D + 2 * H - 1) / WV_THREADS;
+#pragma unroll
+  for (int k = 0; k < NI; ++k) {
+    const int e = tid + WV_THREADS * k;
+    img[e] = im[k];
+    if (k >= KB_LO && k <= KB_HI && e >= F_B1 && e < F_B1 + 2 * H) lds[S::O_B1 + (e - F_B1)] = im[k];
+  }
+  static_assert(S::O_B2 == S::O_B1 + H, "b1 | b2 are stored as one run");
   __syncthreads();
+
+  // register-resident A operands, lane (i, g): k index of MFMA step (slice sl, r) is feature 16 sl + 4 g + r.  Read from
+  // the image at the flat block's offsets (behind W2: less its H * H floats).  Every read is issued before the first mask
+  // is applied (one LDS round trip, not one per group of operands); a masked operand reads an in-range float and is an
+  // exact zero.
+  const int I_W3 = F_W3 - H * H, I_B3 = F_B3 - H * H, I_LS = F_LS - H * H;
+  float w1[4][5], w3h[4][4], w3t[4][4];
+  float w1b[4][4];                                   // WIDE: W1[row][16 + 4g + r]
+  float b3v[4], lsraw[4];                            // per-lane constants of the lane's 4 outputs o = 4g + r (policy)
+#pragma unroll
+  for (int so = 0; so < 4; ++so) {
+    const int row = 16 * so + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w1[so][r] = img[F_W1 + row * Dr + (fv[r] ? 4 * g + r : 0)];
+    w1[so][4] = img[F_W1 + row * Dr + (f16 ? 16 : 0)];
+    if constexpr (WIDE) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) w1b[so][r] = img[F_W1 + row * Dr + (fv2[r] ? 16 + 4 * g + r : 0)];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 4 * g + r;
+      if constexpr (SDP) {
+        w3h[so][r] = img[I_W3 + (sd_has(i) ? sd_row(i) : 0) * H + 16 * so + 4 * g + r];        // head: W3[row of tile row i][k]
+        w3t[so][r] = img[I_W3 + (sd_has(o) ? sd_row(o) : 0) * H + row];                        // dH2: W3[row of tile row o][own f]
+      } else if constexpr (IS_PF) {
+        w3h[so][r] = img[I_W3 + (i < O ? i : 0) * H + 16 * so + 4 * g + r];                    // head: W3[o = i][k]
+        w3t[so][r] = img[I_W3 + (o < O ? o : 0) * H + row];                                    // dH2: W3[k = o][own f]
+      } else {
+        w3h[so][r] = img[I_W3 + 16 * so + 4 * g + r];                                          // per-lane head weights
+        w3t[so][r] = 0.0f;
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int o = 4 * g + r;
+    if constexpr (IS_PF && !CAT && !SDP) lsraw[r] = img[I_LS + (o < O ? o : 0)];
+    else lsraw[r] = 0.0f;
+    if constexpr (SDP) b3v[r] = img[I_B3 + (sd_has(o) ? sd_row(o) : 0)];
+    else b3v[r] = img[I_B3 + (o < O ? o : 0)];
+  }
+  const float vb3 = IS_PF ? 0.0f : img[I_B3];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int so = 0; so < 4; ++so) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int o = 4 * g + r;
+      w1[so][r] = fv[r] ? w1[so][r] : 0.0f;
+      if constexpr (WIDE) w1b[so][r] = fv2[r] ? w1b[so][r] : 0.0f;
+      if constexpr (SDP) {
+        w3h[so][r] = sd_has(i) ? w3h[so][r] : 0.0f;
+        w3t[so][r] = sd_has(o) ? w3t[so][r] : 0.0f;
+      } else if constexpr (IS_PF) {
+        w3h[so][r] = (i < O) ? w3h[so][r] : 0.0f;
+        w3t[so][r] = (o < O) ? w3t[so][r] : 0.0f;
+      }
+    }
+    w1[so][4] = (g == 0 && f16) ? w1[so][4] : 0.0f;
+  }
+  float lsv[4], ivv[4], lspass[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int o = 4 * g + r;
+    const float raw = (IS_PF && !CAT && !SDP && o < O) ? lsraw[r] : 0.0f;
+    lsv[r] = fminf(fmaxf(raw, -20.0f), 2.0f);                   // continuous_policy.py:8-9,185
+    ivv[r] = __expf(-2.0f * lsv[r]);
+    lspass[r] = (raw >= -20.0f && raw <= 2.0f) ? 1.0f : 0.0f;   // clamp passes gradient inside [-20, 2]
+    if constexpr (SDP) b3v[r] = sd_has(o) ? b3v[r] : 0.0f;      // (lsv / ivv are per tile, see the loop)
+    else b3v[r] = (o < O) ? b3v[r] : 0.0f;
+  }
 
   // advantage normalisation constants (ppo.py:141-147): mean, unbiased std
   const double ng = a.n_global;
