@@ -229,6 +229,24 @@ def test_adam_args_equals_the_two_chains_fill():
     assert _fields(self._adam_args((2.5e-4, 5e-4), device_state=1)) == _fields(_fused_fill(self, 2.5e-4, 5e-4, 1))
 
 
+def test_adam_args_equals_the_policy_only_fill():
+    self, lr = _Engine(), 3e-3
+    self.P_pf, self.P_vf, self.eps = 300, 0, 1e-8                        # a vacant critic: `flat` is the policy's alone
+    a = _C.AdamArgs()                                                    # the policy-only engines' fill, field by field
+    a.params, a.grads, a.exp_avg, a.exp_avg_sq = (self.flat.data_ptr(), self.grads.data_ptr(),
+                                                  self.m.data_ptr(), self.v.data_ptr())
+    a.n_groups = 1
+    a.group_sizes[0] = self.P_pf
+    a.group_lr[0] = lr
+    a.max_norm, a.beta1, a.beta2, a.eps, a.grad_scale = 0.5, 0.9, 0.999, 1e-8, 1.0
+    a.device_state = 1
+    got = self._adam_args((lr,), device_state=1)
+    assert _fields(got) == _fields(a)
+    assert got.n_groups == 1 and list(got.group_sizes) == [300, 0, 0, 0] and list(got.group_lr)[1:] == [0.0] * 3
+    assert _fields(self._adam_args((lr, 0.0), device_state=1)) == _fields(a)             # as the shared `run` calls it
+    assert _Engine().eps == 1e-5                                         # (two networks: A2C's)
+
+
 def test_adam_args_equals_the_generic_engines_fill():
     self, k = _Engine(), 3
     norms = self.norms

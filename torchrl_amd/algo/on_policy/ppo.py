@@ -17,6 +17,7 @@ of all minibatches and the logger receives the same info dicts, in order.
 `update(batch)` keeps the reference's single-minibatch entry point (ppo.py:124-152).
 """
 import copy
+import ctypes as C
 import os
 import math
 
@@ -26,7 +27,7 @@ import torch.optim as optim
 
 from ... import _C
 from ... import dist
-from ...networks import flatten_into
+from ...networks import ZeroNet, flatten_into
 from ...policies.continuous_policy import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, HEAD_TAG, head_kind, is_state_std  # noqa: F401
 from .. import utils as atu
 from .._graphs import GraphCache, LastGraph
@@ -39,6 +40,11 @@ def _hyper(algo):
     """(clip_para, entropy_coeff, clipped_value_loss, tanh_action): what a loss kernel takes besides the data."""
     return (float(getattr(algo, "clip_para", 0.0)), float(algo.entropy_coeff),
             int(bool(getattr(algo, "clipped_value_loss", False))), int(bool(algo.pf.tanh_action)))
+
+
+def _critic(algo):
+    """The value network, or None for a vacant critic (`networks.ZeroNet`: the rule the collector uses)."""
+    return None if isinstance(algo.vf, ZeroNet) else algo.vf
 
 
 def _stat_views(block, K):
@@ -144,15 +150,16 @@ class _FusedPPO:
 
     def __init__(self, algo):
         self.algo = algo
-        pf, vf = algo.pf, algo.vf
-        ps, vs = pf.mlp2_spec(), vf.mlp2_spec()
+        pf, vf = algo.pf, _critic(algo)
+        ps, vs = pf.mlp2_spec(), None if vf is None else vf.mlp2_spec()
+        # a vacant critic (vf None): the policy alone in the flat buffers, every gradient workgroup the policy's
         # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's HEAD_CAT instantiations and their folds
         # (trl_ppo_cat_*); no logstd in the flat vector, the entropy arrives through info slot 20
         # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; the gradient kernel's
         # HEAD_SD instantiations and their folds (trl_ppo_sd_*); no logstd in the flat vector either, `self.A` = half the head's
         # width, entropy and the per-element log_std / std statistics arrive through info slots 20, 8-11 and 16-19
         needs = "fused PPO needs MLP2 nets and a GuassianContPolicyBasicBias, GuassianContPolicy or CategoricalDisPolicy policy"
-        if ps is None or vs is None:
+        if ps is None or (vf is not None and vs is None):
             raise _C.TrlError(needs)
         self.head = head_kind(pf, refuse=needs)
         self.categorical, self.state_std = self.head == HEAD_CAT, self.head == HEAD_SD
@@ -161,7 +168,7 @@ class _FusedPPO:
             why = _fused_head_refusal(self.head, ps)
             if why:
                 raise _C.TrlError(why)
-        if vs[0] != ps[0] or vs[1] != ps[1] or vs[2] != 1 or vs[3] != ps[3]:
+        if vf is not None and (vs[0] != ps[0] or vs[1] != ps[1] or vs[2] != 1 or vs[3] != ps[3]):
             raise _C.TrlError("policy %s and value %s must share input, width and activation" % (ps, vs))
         self.D, self.H, self.A, self.act = ps
         self.dev = next(pf.parameters()).device
@@ -169,7 +176,7 @@ class _FusedPPO:
             raise _C.TrlError("PPO networks live on %s: the fused path needs a GPU (no CPU path exists)" % self.dev)
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = pf._mlp2_param_list() + tail(pf)
-        vf_list = vf._mlp2_param_list()
+        vf_list = [] if vf is None else vf._mlp2_param_list()
         tgt = getattr(algo, "target_pf", None)
         self._home(pf_list, vf_list, None if tgt is None else tgt._mlp2_param_list() + tail(tgt))
         if tgt is not None and (self.categorical or self.state_std):   # (its forward must find THIS storage, see _GenericPPO)
@@ -202,22 +209,28 @@ class _FusedPPO:
         self._stats2_key = self._chain_rows = self._pro_ws = None                    # (allocated by the first run of a shape)
         self.red_ws[4:8].view(torch.float64).fill_(1.0)               # beta1^0, beta2^0 (device-side Adam state)
 
+    eps = 1e-5                                                       # Adam's, of A2C's two optimisers (a2c.py:30-31)
+
     def _home(self, pf_list, vf_list, target_list):
         """The networks' home: `flat` = [pf | vf] with the parameters views of it (nets that are MLP2 blocks hand their
         own flat view to the fused inference kernel, Net.flat_params: it must be THIS storage, or the first forward after
         the engine exists would re-home the parameters away from it), the moments and gradients beside it, `target_flat`
-        mirroring the policy block, and both optimisers' state bound to the moments."""
+        mirroring the policy block, and each optimiser's state bound to the moments.  An empty `vf_list` is a vacant
+        critic: `P_vf = 0`, `flat` is the policy's alone, there is no `vf_optimizer`, and `eps` is the one optimiser's own."""
+        algo = self.algo
         self.P_pf = sum(p.numel() for p in pf_list)
         self.P_vf = sum(p.numel() for p in vf_list)
         self.flat = flatten_into(pf_list + vf_list)
-        for net, lo, hi in ((self.algo.pf, 0, self.P_pf), (self.algo.vf, self.P_pf, self.P_pf + self.P_vf)):
-            if getattr(net, "mlp2_spec", lambda: None)() is not None:
-                net._flat = self.flat[lo:hi]
         self.m, self.v, self.grads = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         self.step_count = 0
         self.target_flat = None if target_list is None else flatten_into(target_list)
-        self._alias_optimizer_state(self.algo.pf_optimizer, pf_list, 0)
-        self._alias_optimizer_state(self.algo.vf_optimizer, vf_list, self.P_pf)
+        if not vf_list:
+            self.eps = float(algo.pf_optimizer.param_groups[0]['eps'])
+        for net, plist, opt, lo in ((algo.pf, pf_list, "pf_optimizer", 0), (algo.vf, vf_list, "vf_optimizer", self.P_pf)):
+            if plist:
+                if getattr(net, "mlp2_spec", lambda: None)() is not None:
+                    net._flat = self.flat[lo:lo + sum(p.numel() for p in plist)]
+                self._alias_optimizer_state(getattr(algo, opt), plist, lo)
 
     def _alias_optimizer_state(self, opt, plist, offset):
         self._opt_steps = getattr(self, "_opt_steps", [])
@@ -296,9 +309,16 @@ class _FusedPPO:
 
     # ---- the launch builder: what the joint sequence and the two chains enqueue, called from their launch closures only
     # (eager visits and captures; a replayed visit builds nothing) ----
+    def _lrs(self):
+        """(the policy's, the value function's) learning rate, 0.0 for a network that does not exist."""
+        lr = lambda opt: float(getattr(self.algo, opt).param_groups[0]['lr'])
+        return lr("pf_optimizer"), lr("vf_optimizer") if self.P_vf else 0.0
+
     def _adam_args(self, lrs=(0.0, 0.0), **kw):
-        """clip_grad_norm_(0.5) + Adam(eps 1e-5) over both networks' groups of the flat buffers."""
-        return _C.adam_args(self.flat, self.grads, self.m, self.v, (self.P_pf, self.P_vf), lrs, max_norm=0.5, eps=1e-5, **kw)
+        """clip_grad_norm_(0.5) + Adam(`eps`) over the groups of the flat buffers: one per network that exists."""
+        groups = [(n, lr) for n, lr in zip((self.P_pf, self.P_vf), lrs) if n]
+        return _C.adam_args(self.flat, self.grads, self.m, self.v, [n for n, _ in groups], [lr for _, lr in groups],
+                            max_norm=0.5, eps=self.eps, **kw)
 
     def _batch_args(self, t, hyper, loss_mode, rows_mb, N, n_global, partial, scal, n_wg, n_wg_pf):
         """trl_ppo_batch_t of a gradient launch over `n_wg` workgroups that leave their rows in `partial` / `scal`."""
@@ -307,7 +327,7 @@ class _FusedPPO:
             setattr(g, k, _C.dev_ptr(t[k], name=k).value if t.get(k) is not None else None)
         g.loss_mode = loss_mode
         g.rows_mb, g.N, g.n_global = rows_mb, N, n_global
-        g.pf_params, g.vf_params = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.P_pf
+        g.pf_params, g.vf_params = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.P_pf if self.P_vf else None
         g.D, g.H, g.A, g.act = self.D, self.H, self.A, self.act
         g.clip_para, g.entropy_coeff, g.clipped_value_loss, g.tanh_action = hyper
         g.partial, g.scal_partial, g.n_wg, g.n_wg_pf = partial.data_ptr(), scal.data_ptr(), n_wg, n_wg_pf
@@ -330,7 +350,6 @@ class _FusedPPO:
         """fold(k, g, a): the fused reduce / clip / Adam launch `kernel` behind minibatch k's gradient launch, its
         statistics into row k of `info`.  `which`: the policy's workgroup count (joint) or the network (a chain); `comm`:
         the xrank kernels, which take the peer transport's handle."""
-        import ctypes as C
         fn, name = kernel
         head = (partial.data_ptr(), scal.data_ptr(), n_wg, which, self.D, self.H, self.A, self.grads.data_ptr())
         tail = (ws.data_ptr(),) + ((dist.comm_handle(),) if comm else ()) + (_C.stream_ptr(self.dev),)
@@ -339,7 +358,6 @@ class _FusedPPO:
 
     def _minibatches(self, K, g, a, idx_dev, raw, norms, fold, probe=None):
         """K x {gradient launch, `fold(k, g, a)`} on the current stream."""
-        import ctypes as C
         stream = _C.stream_ptr(self.dev)
         idx_base, raw_base, norm_base = idx_dev.data_ptr(), raw.data_ptr(), norms.data_ptr()
         for k in range(K):
@@ -363,6 +381,7 @@ class _FusedPPO:
             s.fill_(float(self.step_count))
 
     defers = True                                                    # run(..., defer=True) is implemented
+    one_rank = None                                                  # (the refusal's text, where an engine runs on one rank only)
 
     def run(self, t, row_idx, N, pre=None, pre_key=None, defer=False):
         """t: dict of (rows, N, feat) device tensors; row_idx: (K, rows_mb) host int64.
@@ -387,11 +406,14 @@ class _FusedPPO:
         loss_mode = int(getattr(algo, "loss_mode", _C.LOSS_PPO_CLIP))
         probe = getattr(self, "probe", None)                           # bench.py: HIP events around the grad kernel
         fused = not dist.collectives_active()
+        if self.one_rank and not fused:
+            raise _C.TrlError(self.one_rank)
         if (self.categorical or self.state_std) and not fused:
             raise _C.TrlError("the fused %s update runs on one rank (no cross-rank fold exists for this head)"
                               % ("categorical" if self.categorical else "state-dependent-std"))
         # (env shards on several ranks: the two chains need the in-launch gradient exchange of the peer transport, whose
-        # granules and exchange counts are per network; over all-reduce CALLS the joint sequence stays)
+        # granules and exchange counts are per network; over all-reduce CALLS the joint sequence stays.  A launch whose
+        # workgroups are all one network's -- a vacant critic -- has no second chain: the joint sequence carries it)
         xrank_chains = not fused and self.chains_across_ranks()
         if (fused or xrank_chains) and probe is None and self.two_chains and n_wg_pf >= 1 and n_wg - n_wg_pf >= 1:
             return self._run_chains(t, row_idx, N, pre, pre_key, defer, n_wg, n_wg_pf, loss_mode, n_global, xrank=not fused)
@@ -416,7 +438,7 @@ class _FusedPPO:
         # TRL_GRAPH_COLLECTIVES=1 (opt-in, RCCL route): capture the multi-rank sequence -- RCCL all-reduces included -- into
         # the HIP graph as well; the Adam step count and learning rates then live on the device like in the fused launch.
         graph_coll = not fused and not xrank and os.environ.get("TRL_GRAPH_COLLECTIVES") == "1"
-        lr_pf, lr_vf = algo.pf_optimizer.param_groups[0]['lr'], algo.vf_optimizer.param_groups[0]['lr']
+        lr_pf, lr_vf = self._lrs()
         # One process: no copy command for the epoch's row indices and learning rates -- the prologue launch reads the
         # page-locked slab in place and leaves the device copies the update kernels use.  (The slab is rewritten only after
         # the previous run's statistics have landed, see `last.resolve()` above: that run's launches are done by then.)
@@ -430,8 +452,8 @@ class _FusedPPO:
                 n = float(self.step_count)
                 self.step_state = torch.tensor([n, 0.9 ** n, 0.999 ** n, 0.0], dtype=torch.float64, device=dev)
                 self.lr_dev = torch.zeros(2, device=dev)
-            if getattr(self, "_lr_host", None) != (float(lr_pf), float(lr_vf)):
-                self._lr_host = (float(lr_pf), float(lr_vf))
+            if getattr(self, "_lr_host", None) != (lr_pf, lr_vf):
+                self._lr_host = (lr_pf, lr_vf)
                 self.lr_dev.copy_(torch.tensor(self._lr_host, dtype=torch.float32), non_blocking=True)
         hyper = _hyper(algo)
         use_graph = (fused or xrank or graph_coll) and probe is None and os.environ.get("TRL_NO_GRAPH") != "1"
@@ -444,12 +466,12 @@ class _FusedPPO:
             slab = [(idx_dev, self._idx_host), (self.red_ws[2:4], self._hyper_host)] if in_place else []
             self._prologue(pre, t["advs"].reshape(rows_total, N), (self._idx_host if in_place else idx_dev).view(K, rows_mb),
                            raw, stats[4 * K:], slab)
-            if fused:                                                  # one process: reduce + clip + Adam in one launch
-                fold = self._fold(self._k_fold, self.partial, self.scal, n_wg, n_wg_pf, info, self.red_ws)
+            if fused:                                                  # one process: reduce + clip + Adam in one launch --
+                kernel, which = (self._k_fold, n_wg_pf) if self.P_vf else (self._k_fold_net, 0)     # both nets', or the policy's
+                fold = self._fold(kernel, self.partial, self.scal, n_wg, which, info, self.red_ws)
             elif xrank:                                                # the same launch with the cross-rank SUM inside
                 fold = self._fold(self._k_fold_x, self.partial, self.scal, n_wg, n_wg_pf, info, self.red_ws, comm=True)
             else:
-                import ctypes as C
                 lib, stream = _C.lib(), _C.stream_ptr(dev)
 
                 def fold(k, g, a):
@@ -470,7 +492,7 @@ class _FusedPPO:
         landed.record()
         self._stepped(K)
         host = self._stats_host
-        make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
+        make = self._info_builder(loss_mode)
 
         def build(host):
             if xrank:
@@ -559,8 +581,8 @@ class _FusedPPO:
         idx_host.numpy()[:] = row_idx.reshape(-1)
         rows_total = t["advs"].shape[0]
         raw = stats2[0, :4 * K].view(K, 4)
-        lr_pf, lr_vf = algo.pf_optimizer.param_groups[0]['lr'], algo.vf_optimizer.param_groups[0]['lr']
-        hyper_host[0], hyper_host[1] = float(lr_pf), float(lr_vf)
+        lr_pf, lr_vf = self._lrs()
+        hyper_host[0], hyper_host[1] = lr_pf, lr_vf
         self._hyper = None                                             # (the joint route uploads its own copy when it runs next)
         hyper = _hyper(algo)
         n_wg_vf = n_wg - n_wg_pf
@@ -636,7 +658,7 @@ class _FusedPPO:
         from ...networks import nets as _nets
         _nets.set_pending(algo.vf, done_v)
         self._stepped(K)
-        make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
+        make = self._info_builder(loss_mode)
 
         class _Both:
             @staticmethod
@@ -661,12 +683,18 @@ class _FusedPPO:
         self._settle_value_chain()                                     # a caller that reads in place gets settled parameters too
         return out
 
+    def _info_builder(self, loss_mode):
+        """What turns a landed statistics block into the K info dicts, by the loss the kernels ran (`_infos_reinforce` is
+        the policy-only engines' own: algo/on_policy/reinforce.py)."""
+        names = {_C.LOSS_PPO_CLIP: "_infos", _C.LOSS_A2C: "_infos_a2c", _C.LOSS_REINFORCE: "_infos_reinforce"}
+        return getattr(self, names[loss_mode])
+
     def _infos_a2c(self, raw, info, norms, n):
         """The info dict of A2C.update (a2c.py:86-105); `std` is (B, A) there, each dim repeated B times."""
         out = []
         c_ent = float(self.algo.entropy_coeff)
         A = self.A
-        categorical, state_std = getattr(self, "categorical", False), getattr(self, "state_std", False)
+        categorical, state_std = self.categorical, self.state_std
         for r, i, g in zip(raw, info, norms):
             v_var = max((i[13] - i[12] * i[12] / n) / (n - 1), 0.0)
             if categorical or state_std:                                # the kernel's entropy sum; SD: per-element statistics
@@ -689,8 +717,8 @@ class _FusedPPO:
         r, i = raw, info
         adv_var = np.maximum((r[:, 1] - r[:, 0] * r[:, 0] / n) / (n - 1), 0.0)
         lp_var = np.maximum((i[:, 2] - i[:, 1] * i[:, 1] / n) / (n - 1), 0.0)
-        categorical = getattr(self, "categorical", False)              # entropy: the kernel's sum; no log_std/* keys
-        ent = i[:, 20] / n if (categorical or getattr(self, "state_std", False)) else \
+        categorical = self.categorical                                 # entropy: the kernel's sum; no log_std/* keys
+        ent = i[:, 20] / n if (categorical or self.state_std) else \
             self.A * _HALF_LOG_2PI_PLUS_HALF + self.A * i[:, 8]
         cols = (('advs/mean', r[:, 0] / n), ('advs/std', np.sqrt(adv_var)), ('advs/max', r[:, 2]), ('advs/min', -r[:, 3]),
                 ('Training/vf_loss', i[:, 7] / n), ('grad_norm/vf', norms[:, 1].astype(np.float64)),
@@ -748,27 +776,6 @@ def _fused_head_refusal(kind, ps):
     return None
 
 
-def make_engine(algo):
-    """The fused engine when the networks have the shape its kernels are instantiated for, the generic one otherwise."""
-    pf, vf = algo.pf, algo.vf
-    ps = pf.mlp2_spec() if hasattr(pf, "mlp2_spec") else None
-    vs = vf.mlp2_spec() if hasattr(vf, "mlp2_spec") else None
-    kind = head_kind(pf)
-    if kind in _HEAD_OPT_IN:
-        # categorical / [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1 /
-        # TRL_SD_FUSED_UPDATE=1, opt-in) AND both nets have a shape the head's instantiations carry, the optimiser is Adam and
-        # this is the only rank
-        if os.environ.get(_HEAD_OPT_IN[kind]) == "1" and os.environ.get("TRL_GENERIC_PPO") != "1" \
-                and ps is not None and vs is not None and _fused_head_refusal(kind, _head_spec(kind, ps)) is None \
-                and tuple(vs) == (ps[0], ps[1], 1, ps[3]) and getattr(algo, "optimizer_class", None) is optim.Adam:
-            return _FusedPPO(algo)
-        return _GenericPPO(algo)
-    if ps is not None and vs is not None and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 \
-            and os.environ.get("TRL_GENERIC_PPO") != "1":
-        return _FusedPPO(algo)
-    return _GenericPPO(algo)
-
-
 class _GenericPPO(_FusedPPO):
     defers = False                                                     # (its run returns the dicts)
     carries_layernorm = True                                           # `add_ln` nets run here (ops.net_plan, k_layernorm.hip)
@@ -784,7 +791,8 @@ class _GenericPPO(_FusedPPO):
     def __init__(self, algo):
         from ... import ops
         self.algo, self.ops = algo, ops
-        pf, vf = algo.pf, algo.vf
+        pf, vf = algo.pf, _critic(algo)
+        # a vacant critic (vf None): `vf_layers` is empty -- no value forward, backward, pointers or optimiser group
         # a categorical head (policies.CategoricalDisPolicy): no logstd in the flat vector, trl_cat_losses_f32 for the loss half
         # a state-dependent-std head (policies.GuassianContPolicy): the network emits [mean | log_std]; no logstd in the flat
         # vector either, trl_gauss_sd_losses_f32 for the loss half, `self.A` = half the head's width
@@ -806,8 +814,8 @@ class _GenericPPO(_FusedPPO):
         # vector, the gradient views and the Adam moments behind their layer's W, b; the two nets may differ in `add_ln`
         # (TRPO / V-MPO build on this engine and walk the plain layer lists themselves: they keep refusing LayerNorm nets)
         layers_of = ops.net_layers if self.carries_layernorm else (lambda net: (ops.linear_layers(net), ops.act_code(net)))
-        (self.pf_layers, self.act), (self.vf_layers, vf_act) = layers_of(pf), layers_of(vf)
-        if vf_act != self.act:
+        (self.pf_layers, self.act), (self.vf_layers, vf_act) = layers_of(pf), ([], None) if vf is None else layers_of(vf)
+        if vf is not None and vf_act != self.act:
             raise _C.TrlError("policy and value network must use the same activation")
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
         pf_list = ops.plan_params(self.pf_layers) + tail(pf)
@@ -842,8 +850,22 @@ class _GenericPPO(_FusedPPO):
             self.workspace = torch.empty(need, device=self.dev)
         return self.workspace
 
+    def _losses(self, mean, acts, advs, old_lp, v, rets, v_old, raw_k, info_k, n_global, hyper):
+        """The loss half of one minibatch on the head's kernel: (d loss / d head, d loss / d v).  `old_lp`, `v`, `rets` and
+        `v_old` are None where the loss mode takes none; `hyper` is `_hyper(algo) + (loss_mode,)`."""
+        flat = lambda x: None if x is None else x.view(-1)
+        advs, old_lp, v, rets, v_old = flat(advs), flat(old_lp), flat(v), flat(rets), flat(v_old)
+        if self.categorical:                                           # `mean` holds the logits, acts (n_local, 1) the indices
+            return _C.cat_losses(mean, acts.view(-1), advs, old_lp, v, rets, v_old, raw_k, n_global, *hyper[:3], hyper[4], info_k)
+        if self.state_std:                                             # `mean` holds the head [mean | log_std]
+            return _C.gauss_sd_losses(mean, acts, advs, old_lp, v, rets, v_old, raw_k, n_global, *hyper, info_k)
+        return _C.ppo_generic_losses(mean, self.algo.pf.logstd.detach(), acts, advs, old_lp, v, rets, v_old, raw_k, n_global,
+                                     *hyper, self.g_logstd, info_k)
+
     def run(self, t, row_idx, N, pre=None, pre_key=None):
         algo, dev, ops = self.algo, self.dev, self.ops
+        if self.one_rank and dist.collectives_active():
+            raise _C.TrlError(self.one_rank)
         K, rows_mb = row_idx.shape
         world = dist.world_size()
         n_local = rows_mb * N
@@ -855,7 +877,7 @@ class _GenericPPO(_FusedPPO):
         loss_mode = int(getattr(algo, "loss_mode", _C.LOSS_PPO_CLIP))
         ws = self._ws(n_local)
         idx2d = idx_dev.view(K, rows_mb)
-        lrs = (float(algo.pf_optimizer.param_groups[0]['lr']), float(algo.vf_optimizer.param_groups[0]['lr']))
+        lrs = self._lrs()
         if getattr(self, "_lr_host", None) != lrs:                     # learning rates live on the device: the linear
             self._lr_host = lrs                                        # schedule changes no launch argument
             self.lr_dev.copy_(torch.tensor(lrs, dtype=torch.float32), non_blocking=True)
@@ -873,23 +895,11 @@ class _GenericPPO(_FusedPPO):
                 obs, acts, advs, rets = gather("obs", k), gather("acts", k), gather("advs", k), gather("rets", k)
                 v_old, old_lp = gather("old_values", k), gather("old_logp", k)
                 mean, tape_pf = ops.mlp_forward(self.pf_layers, obs, self.act)
-                v, tape_vf = ops.mlp_forward(self.vf_layers, obs, self.act)
-                if self.categorical:                                   # `mean` holds the logits, acts (n_local, 1) the indices
-                    d_mean, d_v = _C.cat_losses(
-                        mean, acts.view(-1), advs.view(-1), None if old_lp is None else old_lp.view(-1), v.view(-1),
-                        rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, hyper[0], hyper[1],
-                        hyper[2], loss_mode, info[k])
-                elif self.state_std:                                   # `mean` holds the head [mean | log_std]
-                    d_mean, d_v = _C.gauss_sd_losses(
-                        mean, acts, advs.view(-1), None if old_lp is None else old_lp.view(-1), v.view(-1), rets.view(-1),
-                        None if v_old is None else v_old.view(-1), raw[k], n_global, *hyper, info[k])
-                else:
-                    d_mean, d_v = _C.ppo_generic_losses(
-                        mean, algo.pf.logstd.detach(), acts, advs.view(-1), None if old_lp is None else old_lp.view(-1),
-                        v.view(-1), rets.view(-1), None if v_old is None else v_old.view(-1), raw[k], n_global, *hyper,
-                        self.g_logstd, info[k])
+                v, tape_vf = ops.mlp_forward(self.vf_layers, obs, self.act) if self.vf_layers else (None, None)
+                d_mean, d_v = self._losses(mean, acts, advs, old_lp, v, rets, v_old, raw[k], info[k], n_global, hyper)
                 ops.mlp_backward(tape_pf, d_mean, grads=self.gviews[0], workspace=ws)
-                ops.mlp_backward(tape_vf, d_v, grads=self.gviews[1], workspace=ws)
+                if self.vf_layers:
+                    ops.mlp_backward(tape_vf, d_v, grads=self.gviews[1], workspace=ws)
                 dist.all_reduce_sum_(self.grads)                       # C1: gradient SUM over ranks
                 _C.clip_adam(self._adam_args(norms_out=norms[k].data_ptr(), step_state=self.step_state.data_ptr(),
                                              device_lr=self.lr_dev.data_ptr()), dev)     # device-side step count / lr
@@ -907,5 +917,27 @@ class _GenericPPO(_FusedPPO):
         if ent_sum is not None:
             info[:, 20] = ent_sum
         host = stats.cpu()                                             # the only host sync of the update
-        make = self._infos_a2c if loss_mode == _C.LOSS_A2C else self._infos
-        return make(*(v.numpy() for v in _stat_views(host, K)), n_global)
+        return self._info_builder(loss_mode)(*(v.numpy() for v in _stat_views(host, K)), n_global)
+
+
+def make_engine(algo, fused=_FusedPPO, generic=_GenericPPO):
+    """The `fused` engine when the networks -- the policy and, unless the critic is vacant, the value function -- have the
+    shape its kernels are instantiated for, the `generic` one otherwise."""
+    pf, vf = algo.pf, _critic(algo)
+    ps = pf.mlp2_spec() if hasattr(pf, "mlp2_spec") else None
+    vs = vf.mlp2_spec() if hasattr(vf, "mlp2_spec") else None
+    blocks = ps is not None and (vf is None or vs is not None)         # every network there is is an MLP2 block
+    forced = os.environ.get("TRL_GENERIC_PPO") == "1"
+    kind = head_kind(pf)
+    if kind in _HEAD_OPT_IN:
+        # categorical / [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1 /
+        # TRL_SD_FUSED_UPDATE=1, opt-in) AND the nets have a shape the head's instantiations carry, the optimiser is Adam and
+        # this is the only rank
+        if os.environ.get(_HEAD_OPT_IN[kind]) == "1" and not forced and blocks \
+                and _fused_head_refusal(kind, _head_spec(kind, ps)) is None \
+                and (vf is None or tuple(vs) == (ps[0], ps[1], 1, ps[3])) and getattr(algo, "optimizer_class", None) is optim.Adam:
+            return fused(algo)
+        return generic(algo)
+    if blocks and hasattr(pf, "logstd") and _C.lib().trl_ppo_partial_stride(ps[0], ps[1], ps[2]) > 0 and not forced:
+        return fused(algo)
+    return generic(algo)
