@@ -34,10 +34,16 @@ def head_of(mean, logstd):
     return torch.cat([mean, logstd.reshape(1, -1).expand(mean.shape[0], -1)], dim=1)
 
 
+def _rows(logstd):
+    """A shared (A,) log_std as one broadcast row; a per-sample (B, A) one as it is."""
+    return logstd if logstd.dim() == 2 else logstd.reshape(1, -1)
+
+
 def logp_parts(mean, logstd, acts, tanh):
     """-> dict of (B, A) tensors: quad = zc^2 / (2 var), ls (clamped), corr, zc, var; log pi = sum(-quad - ls - log(2 pi) / 2
-    - corr), sd.logp's formula."""
-    ls = logstd.clamp(-20.0, 2.0).reshape(1, -1).expand_as(mean)
+    - corr), sd.logp's formula.  `logstd` is the shared (A,) row, or (B, A): one raw log_std per sample and dim (a
+    state-dependent-std head)."""
+    ls = _rows(logstd.clamp(-20.0, 2.0)).expand_as(mean)
     var = torch.exp(ls) ** 2
     pre, corr = acts, torch.zeros_like(mean)
     if tanh:
@@ -55,7 +61,7 @@ def logp(mean, logstd, acts, tanh):
 def explore(mean, logstd, eps, tanh):
     """-> (act (N, A), log pi(act) (N,)); eps None: the deterministic action [tanh](mean).  The std is exp of the CLAMPED
     log_std."""
-    std = torch.exp(logstd.clamp(-20.0, 2.0)).reshape(1, -1)
+    std = _rows(torch.exp(logstd.clamp(-20.0, 2.0)))
     z = mean if eps is None else mean + std * eps
     act = torch.tanh(z) if tanh else z
     return act, logp(mean, logstd, act, tanh)
@@ -66,7 +72,7 @@ def act_bound(mean, logstd, eps, tanh):
     exp2(x log2 e): the rounded product puts |x| 2^-23 into the result and the hardware exp2 one ulp, (2 + |ls|) 2^-23
     relative on the std (profiles/NOTES_offpolicy_kernel_tests.md, alpha); the fma rounds once, 2^-24 |z|; trl_tanh is
     within 2e-7 absolute (trl_mlp.h) and has slope <= 1."""
-    ls = logstd.double().clamp(-20.0, 2.0).reshape(1, -1)
+    ls = _rows(logstd.double().clamp(-20.0, 2.0))
     se = torch.exp(ls) * (0.0 if eps is None else eps.double())
     z = mean.double() + se
     return se.abs() * (2.0 + ls.abs()) * 2.0 * U + U * z.abs() + (2e-7 if tanh else 0.0)

@@ -218,6 +218,81 @@ def test_cat_losses_gradients_vs_autograd(loss_mode, clipv):
     assert all(i[k].item() == 0.0 for k in (8, 9, 10, 11, 16, 17, 18, 19))
 
 
+@pytest.mark.parametrize("loss_mode,clipv", [(ref.LOSS_PPO_CLIP, False), (ref.LOSS_PPO_CLIP, True), (ref.LOSS_A2C, False)])
+@pytest.mark.parametrize("B,A", [(B, A) for A in (2, 64) for B in (2, 256, 257)])
+def test_cat_losses_gradients_at_the_edges_of_the_sizes(B, A, loss_mode, clipv):
+    """The smallest and the largest head (A = 2, 64) at B = 2 (the smallest batch an unbiased advantage std exists for), one
+    full block and one sample more, against float64 autograd with the bound form of the test above."""
+    from torchrl_amd import _C
+    rs = np.random.RandomState(7700 + 3 * B + A)
+    t = lambda *s: torch.from_numpy(rs.randn(*s).astype(np.float32))
+    logits, v, advs, rets, v_old = t(B, A) * 1.5, t(B), t(B) * 2 + 0.5, t(B), t(B)
+    acts = torch.from_numpy(rs.randint(0, A, size=(B,)).astype(np.float32))
+    old_lp = ref.cat_logp(logits, acts)[0] + 0.15 * t(B)
+    clip, c_ent = 0.2, 0.01
+    l64, v64 = logits.double().requires_grad_(True), v.double().requires_grad_(True)
+    ref.objective(l64, v64, acts, advs.double(), rets.double(), v_old.double(), old_lp.double(), clip, c_ent, clipv,
+                  loss_mode).backward()
+    raw = torch.tensor([advs.double().sum(), (advs.double() ** 2).sum(), advs.max(), -advs.min()], dtype=torch.float64)
+    info = torch.zeros(24, dtype=torch.float64, device=DEV)
+    d_logits, d_v = _C.cat_losses(dev(logits), dev(acts), dev(advs), dev(old_lp), dev(v), dev(rets), dev(v_old), dev(raw),
+                                  float(B), clip, c_ent, clipv, loss_mode, info)
+    assert d_logits.shape == (B, A) and d_v.shape == (B, 1)
+    for name, got, want in (("d_logits", d_logits.cpu().double(), l64.grad), ("d_v", d_v.view(-1).cpu().double(), v64.grad)):
+        err = (got - want).abs()
+        bound = 1e-6 / B + 1e-4 * want.abs()
+        print(name, "B %d A %d: max err / bound %.3e, max |grad| %.3e" % (B, A, (err / bound).max().item(), want.abs().max().item()))
+        assert bool((err <= bound).all()), (name, (err - bound).max().item())
+
+
+# ---------------------------------------------------------------- trl_cat_logp_f32: log pi, entropy, probabilities
+@pytest.mark.parametrize("scale", [1.0, 40.0], ids=["ordinary", "peaked"])
+@pytest.mark.parametrize("B,A", [(B, A) for A in (2, 7, 64) for B in (1, 255, 256, 257)])
+def test_cat_logp_probs_and_entropy_in_float64(B, A, scale, errlog):
+    """log pi, probabilities and entropy of stored (logits, index) pairs against `_categorical_ref.cat_logp` in float64, per
+    element, at one sample, a block of 256 and its neighbours, the smallest head, an odd one and the largest; logits 1.5 N(0, 1)
+    and 40 times that (most terms of the sum underflow).  U = 2^-24; x_k = m - l_k; the inputs are exact, so the bounds are the
+    float32 roundings of tests/_rollout_ref.py::cat_terms alone:
+      log pi_k  U (x_k + 4 |log S| + |log pi_k| + 2A + 2): the subtraction, S's (2A + 2) U, logf, the last subtraction
+      p_k       p_k U (x_k + 2A + 5) + 1.2e-38: the exponent's rounding U x_k and expf's 2 U on e_k, S's (2A + 2) U, the division;
+                a term below the smallest normal number may be flushed
+      entropy   sum_k (b_p |log pi_k| + p_k b_logpi + U |p_k log pi_k|) + A U sum_k |p_k log pi_k|: each product, the A additions
+    Guard words behind every output; `_C.cat_probs` returns the same bits."""
+    from torchrl_amd import _C
+    rs = np.random.RandomState(8800 + 5 * B + A)
+    logits = torch.from_numpy((rs.randn(B, A) * 1.5 * scale).astype(np.float32))
+    acts = torch.from_numpy(rs.randint(0, A, size=(B,)).astype(np.float32))
+    acts[0], acts[-1] = A - 1, 0
+    want_lp, want_H, want_p = ref.cat_logp(logits.double(), acts)
+    lp_all, _, _ = ref.log_probs(logits.double())
+    U, G, SENT = 2.0 ** -24, 64, -777.25
+    x = logits.double().max(dim=-1, keepdim=True)[0] - logits.double()
+    logS = torch.log(torch.exp(-x).sum(-1, keepdim=True))
+    b_lp_all = U * (x + 4.0 * logS.abs() + lp_all.abs() + 2.0 * A + 2.0)
+    b_p = want_p * U * (x + 2.0 * A + 5.0) + 1.2e-38
+    plp = (want_p * lp_all).abs()
+    b_H = (b_p * lp_all.abs() + want_p * b_lp_all + U * plp).sum(-1) + A * U * plp.sum(-1)
+    bufs = {k: torch.full((n + G,), SENT, device=DEV) for k, n in (("lp", B), ("ent", B), ("probs", B * A))}
+    dl, da = dev(logits), dev(acts)
+    _C.cat_logp(dl, da, out=bufs["lp"][:B], ent=bufs["ent"][:B])
+    _C.check(_C.lib().trl_cat_logp_f32(_C.dev_ptr(dl, name="logits"), None, None, None, _C.dev_ptr(bufs["probs"], name="probs"), B, A,
+                                       _C.stream_ptr(DEV)), "trl_cat_logp_f32")
+    torch.cuda.synchronize()
+    got = {k: v.cpu() for k, v in bufs.items()}
+    for k, n in (("lp", B), ("ent", B), ("probs", B * A)):
+        assert bool((got[k][n:] == SENT).all()), "guard behind %s overwritten" % k
+        assert bool(torch.isfinite(got[k][:n]).all()), k
+    assert torch.equal(_C.cat_probs(dl).cpu().view(-1), got["probs"][:B * A])
+    idx = acts.long()[:, None]
+    worst = {"logp": ((got["lp"][:B].double() - want_lp).abs() / b_lp_all.gather(1, idx)[:, 0]).max().item(),
+             "probs": ((got["probs"][:B * A].view(B, A).double() - want_p).abs() / b_p).max().item(),
+             "ent": ((got["ent"][:B].double() - want_H).abs() / b_H).max().item()}
+    print("B %d A %d x%g: worst err / bound %s" % (B, A, scale, {k: round(v, 4) for k, v in worst.items()}))
+    for k, v in worst.items():
+        errlog("cat_logp_%s" % k, v, 1.0)
+    assert max(worst.values()) <= 1.0, worst
+
+
 # ---------------------------------------------------------------- collector
 def make_collector(N, T, horizon, max_frames, seed=3, hidden=(24, 40), noise_mode="device", D=17, A=6):
     from torchrl_amd.collector.on_policy import VecOnPolicyCollector

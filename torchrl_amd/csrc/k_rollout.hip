@@ -493,7 +493,11 @@ __global__ __launch_bounds__(RO_THREADS, 1) void rollout_kernel(RolloutDev a) {
     CLK(6)
     // feature 0 lives in lane group 0 (r == 0): broadcast to the other groups with a selector MFMA
     const float nx0 = mfma16(1.0f, g == 0 ? nx[0] : 0.0f, zero4)[0];
-    const float raw_rew = a.reward_scale * (nx0 - 0.1f * act_sq);
+    float raw_rew = a.reward_scale * (nx0 - 0.1f * act_sq);
+    // The ring stores this ROUNDED product, and an episode's return is the float32 sum of the rewards the ring stores
+    // (on_policy.py:118-130).  Left visible, the product is contracted into `ep_ret += raw_rew` below as an fma of the
+    // UNROUNDED one: with reward_scale != 1 the logged return leaves that sum by up to half an ulp of a reward per step.
+    asm volatile("" : "+v"(raw_rew));
     t_env += 1; cur_step += 1;
     const bool done = t_env >= a.horizon;
     const bool surpass = cur_step >= a.max_episode_frames;
