@@ -1027,6 +1027,12 @@ int trl_frame_stream_append_u8(const uint8_t* stacks, uint8_t* stream, int32_t* 
 int trl_frame_stream_gather_u8(const uint8_t* stream, const int32_t* pos, const int64_t* row_idx, int n_rows,
                                int shift, uint8_t* out, const int32_t* head, int32_t* overrun, int S, int N,
                                int C, int HW, void* stream_);
+/* Device-side FrameStack (torchrl/env/atari_wrapper.py:206-227) for envs stepped on the host: stacks (N, C, HW) are
+ * updated IN PLACE from one new frame per env, frames (N, HW).  fill_mask (N, nullable): where non-zero all C channels
+ * become the frame (FrameStack.reset, k copies); elsewhere channel c takes channel c + 1 and channel C-1 the frame
+ * (FrameStack.step).  HW % 16 == 0, C >= 1; N == 0 is a no-op */
+int trl_frame_stack_push_u8(uint8_t* stacks, const uint8_t* frames, const uint8_t* fill_mask, int N, int C, int HW,
+                            void* stream_);
 
 /* --- K1..K3 stand-alone: one VecOnPolicyCollector.take_actions as separate launches
  * (torchrl/collector/on_policy.py:90-155), for envs the persistent rollout kernel cannot carry

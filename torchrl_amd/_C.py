@@ -159,6 +159,7 @@ SIGNATURES = {
     "trl_frame_stream_append_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_frame_stream_gather_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "trl_frame_stack_push_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_detac_losses_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int] + [C.c_void_p] * 5),
     "trl_noisy_action_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "trl_gauss_explore_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -467,6 +468,20 @@ class PinnedStager:
             self._events[k] = ev
         self._k = (k + 1) % len(self._bufs)
         return dst
+
+    def upload_parts(self, parts):
+        """parts: (dst, lo, hi) triples -- elements [lo, hi) of the staged buffer go to the device tensor `dst` (of hi - lo
+        elements), all of them under the ONE event of this buffer."""
+        k = self._k
+        dev = None
+        for dst, lo, hi in parts:
+            dst.copy_(self._bufs[k][lo:hi].view(dst.shape), non_blocking=True)
+            dev = dst.device if dst.is_cuda else dev
+        if dev is not None:
+            ev = self._events[k] or torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._events[k] = ev
+        self._k = (k + 1) % len(self._bufs)
 
 
 # ------------------------------------------------------------------ thin op wrappers
@@ -2204,6 +2219,25 @@ def frame_stream_append(stacks, stream, head, mask, n_frames):
                                            dev_ptr(mask, torch.uint8, "mask", allow_none=True), int(n_frames),
                                            int(stream.shape[0]), N, Cc, HW, stream_ptr(stacks.device)),
           "trl_frame_stream_append_u8")
+
+
+def frame_stack_push(stacks, frames, fill_mask=None):
+    """stacks (N, C, H, W) uint8, in place; frames (N, H, W) or (N, H*W) uint8: one new frame per env; fill_mask (N) uint8 or
+    None: those envs' stacks become C copies of their frame, the others shift by one channel and append it."""
+    if not isinstance(stacks, torch.Tensor) or stacks.dim() < 3:
+        raise TrlError("frame_stack_push: stacks must be a (N, C, H, W) or (N, C, H*W) tensor")
+    N, Cc = int(stacks.shape[0]), int(stacks.shape[1])
+    HW = 1
+    for s in stacks.shape[2:]:
+        HW *= int(s)
+    if not isinstance(frames, torch.Tensor) or frames.numel() != N * HW:
+        raise TrlError("frame_stack_push: frames must hold one (H*W = %d)-byte frame for each of the %d envs" % (HW, N))
+    if fill_mask is not None and (not isinstance(fill_mask, torch.Tensor) or fill_mask.numel() != N):
+        raise TrlError("frame_stack_push: fill_mask must hold one byte per env (%d)" % N)
+    check(lib().trl_frame_stack_push_u8(dev_ptr(stacks, torch.uint8, "stacks"), dev_ptr(frames, torch.uint8, "frames"),
+                                        dev_ptr(fill_mask, torch.uint8, "fill_mask", allow_none=True), N, Cc, HW,
+                                        stream_ptr(stacks.device)), "trl_frame_stack_push_u8")
+    return stacks
 
 
 def frame_stream_gather(stream, pos, row_idx, shift, frame_shape, head, overrun, out=None):

@@ -24,13 +24,18 @@ from .. import _C
 class _CollectorBase:
     def __init__(self, env, eval_env, pf, replay_buffer, epoch_frames, train_render=False,
                  eval_episodes=1, eval_render=False, device='cpu', max_episode_frames=999):
-        from ..env.vecenv import HostEnvBridge, VecEnv
+        from ..env.vecenv import VecEnv, bridge_host_env
         if isinstance(env, VecEnv):                                          # host Python envs: bridge to the device path
-            env = HostEnvBridge(env, device)
+            env = bridge_host_env(env, device)                               # (uint8 images: HostFrameBridge)
         if eval_env is None and getattr(env, "is_host_env", False) and not hasattr(env, "_obs_normalizer"):
-            eval_env = HostEnvBridge(copy.deepcopy(env.venv), device)
+            eval_env = bridge_host_env(copy.deepcopy(env.venv), device, like=env)
         if isinstance(eval_env, VecEnv):
-            eval_env = HostEnvBridge(eval_env, device)
+            eval_env = bridge_host_env(eval_env, device, like=env)
+        if getattr(env, "kind", "vector") == "frames" and getattr(env, "is_host_env", False) and \
+                (hasattr(self, "vf") or not (hasattr(pf, "decay_frames") and hasattr(pf, "quantile_num"))):
+            raise _C.TrlError("host envs with image observations (HostFrameBridge) are collected by VecCollector with an "
+                              "epsilon-greedy DQN / QR-DQN policy over a conv Q network; %s with a %s is not built for them"
+                              % (type(self).__name__, type(pf).__name__))
         self.pf = pf
         self.replay_buffer = replay_buffer
         self.env = env
@@ -413,15 +418,23 @@ class VecCollector(_CollectorBase):
             nxt = None
             rew = torch.empty(n, 1, device=env.device)
             done = torch.empty(n, 1, device=env.device)
-        _C.synth_frames_step(env.cur_obs, act, env.t_env, env.seed_base, env.horizon, env.action_num, nxt, rew, done)
+        host = getattr(env, "is_host_env", False)                           # host pixel envs (HostFrameBridge)
+        if host:
+            # actions out; frames (pushed onto the device-resident stacks), rewards, dones and time limits in
+            env.host_step(act, nxt, rew, done, buf._ensure_key("time_limits", (n, 1))[row] if store else None)
+        else:
+            _C.synth_frames_step(env.cur_obs, act, env.t_env, env.seed_base, env.horizon, env.action_num, nxt, rew, done)
         if dedup:
             buf.append_step(env.cur_obs)                                    # the one new frame of next_obs
-        if store:
+        if store and not host:
             buf._ensure_key("time_limits", (n, 1))[row].copy_(done)
         _C.collector_bookkeep(rew, done, env.cur_step, env.ep_return,
                               self.max_episode_frames if max_frames is None else max_frames, self._mask,
                               self._epoch_reward, self._ep_count, self._ep_log, self.global_step - self._log_step0)
-        _C.synth_frames_reset(env.cur_obs, env.t_env, env.seed_base, self._mask)
+        if host:
+            env.host_partial_reset(self._mask)                              # reset mask out, the masked envs' reset frames in
+        else:
+            _C.synth_frames_reset(env.cur_obs, env.t_env, env.seed_base, self._mask)
         if dedup:
             buf.begin_episodes(env.cur_obs, self._mask)                     # fresh stacks of the envs just reset
         if store:

@@ -46,6 +46,39 @@ extern "C" int trl_frame_stream_append_u8(const uint8_t* stacks, uint8_t* stream
   return TRL_OK;
 }
 
+// Device-side FrameStack (torchrl/env/atari_wrapper.py:206-227) for envs stepped on the host: the host uploads ONE new
+// frame per env and step, the k-stack the Q network reads stays on the device.  fill_mask[n] != 0 (FrameStack.reset):
+// all C channels become frames[n]; otherwise (FrameStack.step) channel c takes channel c + 1 and channel C-1 frames[n].
+// In place without a barrier: a thread owns the same byte offsets p in every channel, so the only reader of
+// stacks[n][c + 1][p] is the thread that writes stacks[n][c][p], and it walks the channels upwards (read c + 1, then
+// write c) -- no thread reads a byte another thread writes.
+__global__ __launch_bounds__(FR_THREADS) void frame_stack_push_kernel(uint8_t* __restrict__ stacks,
+                                                                      const uint8_t* __restrict__ frames,
+                                                                      const uint8_t* __restrict__ fill_mask, int C, int HW) {
+  const int n = blockIdx.x;
+  const bool fill = fill_mask && fill_mask[n];                    // block-uniform
+  uint8_t* st = stacks + (size_t)n * C * HW;
+  const uint8_t* fr = frames + (size_t)n * HW;
+  for (int p = threadIdx.x * 16; p < HW; p += FR_THREADS * 16) {
+    const uint4 fresh = *reinterpret_cast<const uint4*>(fr + p);
+    for (int c = 0; c < C - 1; ++c)
+      *reinterpret_cast<uint4*>(st + (size_t)c * HW + p) =
+          fill ? fresh : *reinterpret_cast<const uint4*>(st + (size_t)(c + 1) * HW + p);
+    *reinterpret_cast<uint4*>(st + (size_t)(C - 1) * HW + p) = fresh;
+  }
+}
+
+extern "C" int trl_frame_stack_push_u8(uint8_t* stacks, const uint8_t* frames, const uint8_t* fill_mask, int N, int C,
+                                       int HW, void* stream_) {
+  TRL_REQUIRE(N >= 0 && C >= 1 && HW > 0 && HW % 16 == 0, "bad sizes (HW must be a multiple of 16, C >= 1)");
+  if (N == 0) return TRL_OK;
+  TRL_REQUIRE(stacks && frames, "null pointer");
+  hipLaunchKernelGGL(frame_stack_push_kernel, dim3(N), dim3(FR_THREADS), 0, (hipStream_t)stream_, stacks, frames, fill_mask,
+                     C, HW);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
+}
+
 // out[(r * N + n)][c] = stream[(pos[row_idx[r]][n] - C + 1 + shift + c) % S][n]; shift 0 = obs, 1 = next_obs.
 // *overrun is set when a requested frame has already been overwritten (position <= head - S).
 __global__ __launch_bounds__(FR_THREADS) void frame_gather_kernel(const uint8_t* __restrict__ stream,

@@ -4,5 +4,5 @@ from .base_wrapper import Normalizer, NormObs
 
 VecEnv = SynthVecEnv
 SubProcVecEnv = SynthVecEnv
-from .vecenv import VecEnv, HostEnvBridge
+from .vecenv import VecEnv, HostEnvBridge, HostFrameBridge
 from .subproc_vecenv import SubProcVecEnv

@@ -1,5 +1,5 @@
-"""A small pure-Python env with the gym interface (no gym / MuJoCo in the image) to exercise the host-env path:
-the classic torque-limited pendulum swing-up.  obs = (cos th, sin th, th_dot), action in [-1, 1] scaled to the
+"""Small pure-Python envs with the gym interface (no gym / MuJoCo in the image) to exercise the host-env path (below:
+a cart-pole with discrete actions and `CatchEnv`, a pixel task).  First the classic torque-limited pendulum swing-up.  obs = (cos th, sin th, th_dot), action in [-1, 1] scaled to the
 +-2 N m torque limit, reward = -(th_norm^2 + 0.1 th_dot^2 + 0.001 u^2), 200-step episodes ended by a time limit."""
 import numpy as np
 from gym import spaces
@@ -90,3 +90,54 @@ class CartPoleEnv:
         fell = abs(self._s[0]) > self.x_limit or abs(self._s[2]) > self.theta_limit
         time_limit = self._t >= self._max_episode_steps and not fell
         return self._s.astype(np.float32), 1.0, bool(fell or time_limit), {"time_limit": bool(time_limit)}
+
+
+class CatchEnv:
+    """A pixel task for the conv Q-network path (the classic "catch" game): 21 x 21 cells of 4 x 4 pixels, one (84, 84) uint8
+    frame per step -- ball cell 255, paddle cells 128, everything else 0.  The ball starts in row 0 at a column drawn from
+    the env's RandomState and falls one row per step; the paddle is three cells wide in the bottom row, starts centred and
+    moves left / stays / moves right (Discrete(3)).  After 20 steps the ball is in the bottom row and the episode ends with
+    reward +1 if it is on the paddle, else -1 (a real termination: `time_limit` False); every other step pays 0.
+    Single frames: the k-stack is `FrameStack`'s business (torchrl_amd.env.HostFrameBridge keeps it on the device)."""
+    cells, cell_px = 21, 4
+    _max_episode_steps = 20
+
+    def __init__(self, seed=0):
+        side = self.cells * self.cell_px
+        self.observation_space = spaces.Box(0, 255, (side, side), dtype=np.uint8)
+        self.action_space = spaces.Discrete(3)
+        self.seed(seed)
+
+    def seed(self, seed):
+        self._rng = np.random.RandomState(int(seed) % (2 ** 32))
+
+    def train(self):
+        pass
+
+    def eval(self):
+        pass
+
+    def close(self):
+        pass
+
+    def _frame(self):
+        px, side = self.cell_px, self.cells * self.cell_px
+        frame = np.zeros((side, side), dtype=np.uint8)
+        frame[side - px:, (self._paddle - 1) * px:(self._paddle + 2) * px] = 128
+        frame[self._row * px:(self._row + 1) * px, self._col * px:(self._col + 1) * px] = 255   # (the ball on top)
+        return frame
+
+    def reset(self):
+        self._col = int(self._rng.randint(0, self.cells))
+        self._row, self._paddle, self._t = 0, self.cells // 2, 0
+        return self._frame()
+
+    def step(self, action):
+        self._paddle = int(np.clip(self._paddle + int(action) - 1, 1, self.cells - 2))   # the paddle's centre cell
+        self._row += 1
+        self._t += 1
+        done = self._t >= self._max_episode_steps
+        reward = 0.0
+        if done:
+            reward = 1.0 if abs(self._col - self._paddle) <= 1 else -1.0
+        return self._frame(), reward, bool(done), {"time_limit": False}
