@@ -367,6 +367,21 @@ int trl_vmpo_losses_f32(const float* mean, const float* target_mean, const float
                         const float* acts, const float* adv_n, float* dual_state, int n, int A, int tanh_action,
                         float eta_eps, float alpha_eps, float dual_lr, float* d_mean, float* d_logstd, double* info,
                         double* workspace, void* stream);
+/* The same loss half for the heads without a free logstd: logits / target logits (n, A), 2 <= A <= 64, with one stored action
+ * index per sample (read as trl_cat_logp_f32 reads it); head / target head (n, 2A) = [mean | log_std], 1 <= A <= 32, log_std
+ * clamped to [-20, 2] per sample in both.  d_logits (n, A) / d_head (n, 2A); info and dual_state as above.
+ * kl_reduce: TRL_KL_MEAN is L_pi above.  TRL_KL_SUM puts sum_b KL_b where mean_b KL_b stands: L_pi = mean(-phi log pi) +
+ *   alpha sum KL, alpha loss and the gradient of alpha from the sum, info 5 = 7 = 8 = the sum and info 6 NaN -- the
+ *   reference with a categorical policy (kl_divergence of two Categoricals has no action axis, its .sum(-1) folds the batch).
+ * workspace: at least trl_vmpo_losses_workspace(n, 1) doubles. */
+#define TRL_KL_MEAN 0
+#define TRL_KL_SUM 1
+int trl_vmpo_losses_cat_f32(const float* logits, const float* target_logits, const float* acts, const float* adv_n,
+                            float* dual_state, int n, int A, int kl_reduce, float eta_eps, float alpha_eps, float dual_lr,
+                            float* d_logits, double* info, double* workspace, void* stream);
+int trl_vmpo_losses_sd_f32(const float* head, const float* target_head, const float* acts, const float* adv_n,
+                           float* dual_state, int n, int A, int tanh_action, int kl_reduce, float eta_eps, float alpha_eps,
+                           float dual_lr, float* d_head, double* info, double* workspace, void* stream);
 
 /* --- TRPO: the element-wise pieces of TRPO.update (torchrl/algo/on_policy/trpo.py:28-226) -----------------
  * trl_trpo_surrogate_f32: L = -mean(p / (p.detach() + 1e-8) * adv_n) - c_ent * mean(ent) (:170-180) on the whole batch:
@@ -384,6 +399,19 @@ int trl_trpo_surrogate_f32(const float* mean, const float* logstd, const float* 
 int trl_jvp_gate_f32(const float* a, const float* b, const float* h, int act, int64_t n, float* out, void* stream);
 int trl_fisher_scale_f32(const float* d_mu, const float* logstd, int n, int A, float* out, void* stream);
 int trl_ratio_loss_f32(const float* logp_new, const float* logp_old, const float* adv_n, int n, double* out, void* stream);
+/* The surrogate and the Fisher scaling for the heads without a free logstd (info as above; the entropy is per sample):
+ *   trl_trpo_surrogate_cat_f32: logits (n, A), 2 <= A <= 64, one stored action index per sample -> d_logits (n, A);
+ *   trl_trpo_surrogate_sd_f32: head (n, 2A) = [mean | log_std], 1 <= A <= 32 -> d_head (n, 2A), the log_std columns gated
+ *   on the closed interval [-20, 2].  workspace: trl_trpo_surrogate_workspace(n, 1) doubles.
+ *   trl_fisher_scale_cat_f32: out = p (t - sum_j p_j t_j) / n with p = softmax(logits), t (n, A) the forward-mode tangent of
+ *   the logits: (diag(p) - p p^T) / n is the Hessian of mean KL(p || p.detach()) in the logits.
+ *   trl_fisher_scale_sd_f32: t, out (n, 2A): mean columns t / sigma_b^2 / n, log_std columns 2 gate_b t / n. */
+int trl_trpo_surrogate_cat_f32(const float* logits, const float* acts, const float* adv_n, int n, int A, float entropy_coeff,
+                               float* d_logits, double* info, double* workspace, void* stream);
+int trl_trpo_surrogate_sd_f32(const float* head, const float* acts, const float* adv_n, int n, int A, int tanh_action,
+                              float entropy_coeff, float* d_head, double* info, double* workspace, void* stream);
+int trl_fisher_scale_cat_f32(const float* t, const float* logits, int n, int A, float* out, void* stream);
+int trl_fisher_scale_sd_f32(const float* t, const float* head, int n, int A, float* out, void* stream);
 
 /* --- K11: global-norm clip + Adam ------------------------------------------
  * replaces clip_grad_norm_(params, max_norm) + Adam(eps).step()

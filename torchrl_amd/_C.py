@@ -323,6 +323,12 @@ SIGNATURES = {
     "trl_mse_value_loss_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trl_vmpo_losses_workspace": (C.c_int, [C.c_int] * 2),
     "trl_vmpo_losses_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_void_p] * 5),
+    "trl_vmpo_losses_cat_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_void_p] * 4),
+    "trl_vmpo_losses_sd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 4),
+    "trl_trpo_surrogate_cat_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_float] + [C.c_void_p] * 4),
+    "trl_trpo_surrogate_sd_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 4),
+    "trl_fisher_scale_cat_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "trl_fisher_scale_sd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "trl_ppo_generic_losses_workspace": (C.c_int, [C.c_int] * 2),
     "trl_ppo_generic_losses_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_float,
                                                                  C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
@@ -1102,6 +1108,110 @@ def vmpo_losses(mean, target_mean, logstd, target_logstd, acts, adv_n, dual_stat
                                     dev_ptr(info, torch.float64, "info"), dev_ptr(ws, torch.float64, "workspace"),
                                     stream_ptr(mean.device)), "trl_vmpo_losses_f32")
     return d_mean
+
+
+KL_MEAN, KL_SUM = 0, 1             # kl_reduce of the head V-MPO losses (TRL_KL_* of include/trl_hip.h)
+
+
+def _cat_dims(logits, acts, what):
+    n, A = int(logits.shape[0]), int(logits.shape[1])
+    if not 2 <= A <= 64:
+        raise TrlError("%s: logits are (n, A) with 2 <= A <= 64, got %s" % (what, (n, A)))
+    if int(acts.numel()) != n:
+        raise TrlError("%s: acts must hold one action index per sample, got %s for n=%d" % (what, tuple(acts.shape), n))
+    return n, A
+
+
+def _sd_dims(head, acts, what):
+    n, A = _gauss_sd_dims(head, what)
+    if tuple(acts.shape) != (n, A):
+        raise TrlError("%s: acts must be (n, A) = %s, got %s" % (what, (n, A), tuple(acts.shape)))
+    return n, A
+
+
+def _f64_workspace(need, device, what):
+    if need < 0:
+        raise TrlError("%s: unsupported sizes" % what)
+    return torch.empty((need,), dtype=torch.float64, device=device)
+
+
+def trpo_surrogate_cat(logits, acts, adv_n, entropy_coeff, info):
+    """TRPO's surrogate for a categorical head: d L / d logits (n, A); info as `trpo_surrogate` fills it."""
+    n, A = _cat_dims(logits, acts, "trpo_surrogate_cat")
+    ws = _f64_workspace(lib().trl_trpo_surrogate_workspace(n, 1), logits.device, "trpo_surrogate_cat")
+    d_logits = torch.empty((n, A), dtype=torch.float32, device=logits.device)
+    check(lib().trl_trpo_surrogate_cat_f32(dev_ptr(logits, name="logits"), dev_ptr(acts, name="acts"), dev_ptr(adv_n, name="adv_n"),
+                                           n, A, float(entropy_coeff), dev_ptr(d_logits, name="d_logits"),
+                                           dev_ptr(info, torch.float64, "info"), dev_ptr(ws, torch.float64, "workspace"),
+                                           stream_ptr(logits.device)), "trl_trpo_surrogate_cat_f32")
+    return d_logits
+
+
+def trpo_surrogate_sd(head, acts, adv_n, tanh_action, entropy_coeff, info):
+    """TRPO's surrogate for a [mean | log_std] head: d L / d head (n, 2A); info as `trpo_surrogate` fills it."""
+    n, A = _sd_dims(head, acts, "trpo_surrogate_sd")
+    ws = _f64_workspace(lib().trl_trpo_surrogate_workspace(n, 1), head.device, "trpo_surrogate_sd")
+    d_head = torch.empty((n, 2 * A), dtype=torch.float32, device=head.device)
+    check(lib().trl_trpo_surrogate_sd_f32(dev_ptr(head, name="head"), dev_ptr(acts, name="acts"), dev_ptr(adv_n, name="adv_n"),
+                                          n, A, int(bool(tanh_action)), float(entropy_coeff), dev_ptr(d_head, name="d_head"),
+                                          dev_ptr(info, torch.float64, "info"), dev_ptr(ws, torch.float64, "workspace"),
+                                          stream_ptr(head.device)), "trl_trpo_surrogate_sd_f32")
+    return d_head
+
+
+def fisher_scale_cat(t, logits):
+    """p (t - sum_j p_j t_j) / n: the Hessian of mean KL(p || p.detach()) in the logits, times the tangent t (n, A)."""
+    n, A = int(logits.shape[0]), int(logits.shape[1])
+    if tuple(t.shape) != (n, A):
+        raise TrlError("fisher_scale_cat: the tangent has the logits' shape %s, got %s" % ((n, A), tuple(t.shape)))
+    out = torch.empty_like(t)
+    check(lib().trl_fisher_scale_cat_f32(dev_ptr(t, name="t"), dev_ptr(logits, name="logits"), n, A, dev_ptr(out, name="out"),
+                                         stream_ptr(t.device)), "trl_fisher_scale_cat_f32")
+    return out
+
+
+def fisher_scale_sd(t, head):
+    """Mean columns t / sigma_b^2 / n, log_std columns 2 gate_b t / n, for a tangent t (n, 2A) of a [mean | log_std] head."""
+    n, A = _gauss_sd_dims(head, "fisher_scale_sd")
+    if tuple(t.shape) != (n, 2 * A):
+        raise TrlError("fisher_scale_sd: the tangent has the head's shape %s, got %s" % ((n, 2 * A), tuple(t.shape)))
+    out = torch.empty_like(t)
+    check(lib().trl_fisher_scale_sd_f32(dev_ptr(t, name="t"), dev_ptr(head, name="head"), n, A, dev_ptr(out, name="out"),
+                                        stream_ptr(t.device)), "trl_fisher_scale_sd_f32")
+    return out
+
+
+def vmpo_losses_cat(logits, target_logits, acts, adv_n, dual_state, kl_reduce, eta_eps, alpha_eps, dual_lr, info):
+    """The loss half of V-MPO's actor step for a categorical head: d L_pi / d logits (n, A); info / dual_state as
+    `vmpo_losses`.  kl_reduce: KL_MEAN or KL_SUM."""
+    n, A = _cat_dims(logits, acts, "vmpo_losses_cat")
+    if tuple(target_logits.shape) != (n, A):
+        raise TrlError("vmpo_losses_cat: the target logits have the logits' shape %s" % ((n, A),))
+    ws = _f64_workspace(lib().trl_vmpo_losses_workspace(n, 1), logits.device, "vmpo_losses_cat")
+    d_logits = torch.empty((n, A), dtype=torch.float32, device=logits.device)
+    check(lib().trl_vmpo_losses_cat_f32(dev_ptr(logits, name="logits"), dev_ptr(target_logits, name="target_logits"),
+                                        dev_ptr(acts, name="acts"), dev_ptr(adv_n, name="adv_n"), dev_ptr(dual_state, name="dual"),
+                                        n, A, int(kl_reduce), float(eta_eps), float(alpha_eps), float(dual_lr),
+                                        dev_ptr(d_logits, name="d_logits"), dev_ptr(info, torch.float64, "info"),
+                                        dev_ptr(ws, torch.float64, "workspace"), stream_ptr(logits.device)),
+          "trl_vmpo_losses_cat_f32")
+    return d_logits
+
+
+def vmpo_losses_sd(head, target_head, acts, adv_n, dual_state, tanh_action, kl_reduce, eta_eps, alpha_eps, dual_lr, info):
+    """The loss half of V-MPO's actor step for a [mean | log_std] head: d L_pi / d head (n, 2A); info / dual_state as
+    `vmpo_losses`.  kl_reduce: KL_MEAN or KL_SUM."""
+    n, A = _sd_dims(head, acts, "vmpo_losses_sd")
+    if tuple(target_head.shape) != (n, 2 * A):
+        raise TrlError("vmpo_losses_sd: the target head has the head's shape %s" % ((n, 2 * A),))
+    ws = _f64_workspace(lib().trl_vmpo_losses_workspace(n, 1), head.device, "vmpo_losses_sd")
+    d_head = torch.empty((n, 2 * A), dtype=torch.float32, device=head.device)
+    check(lib().trl_vmpo_losses_sd_f32(dev_ptr(head, name="head"), dev_ptr(target_head, name="target_head"),
+                                       dev_ptr(acts, name="acts"), dev_ptr(adv_n, name="adv_n"), dev_ptr(dual_state, name="dual"),
+                                       n, A, int(bool(tanh_action)), int(kl_reduce), float(eta_eps), float(alpha_eps),
+                                       float(dual_lr), dev_ptr(d_head, name="d_head"), dev_ptr(info, torch.float64, "info"),
+                                       dev_ptr(ws, torch.float64, "workspace"), stream_ptr(head.device)), "trl_vmpo_losses_sd_f32")
+    return d_head
 
 
 def _ptrs(tensors, name, allow_none=False):

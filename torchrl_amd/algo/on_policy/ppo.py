@@ -776,6 +776,29 @@ def _fused_head_refusal(kind, ps):
     return None
 
 
+def plain_layer_refusals(name, pf, vf, env):
+    """What TRPO and V-MPO refuse before anything touches a device -- their engines walk the plain Linear + activation layer
+    lists themselves, take the gathered-batch route over several ranks for the Gaussian head only, and read a categorical
+    policy's actions as indices and a [mean | log_std] policy's as vectors, so the env's action space has to be of the head's
+    kind.  Returns the head kind."""
+    kind = head_kind(pf)
+    for net in (pf, vf):
+        if getattr(getattr(net, "base", None), "add_ln", False):
+            raise _C.TrlError("%s does not carry LayerNorm nets (add_ln=True): its own passes walk Linear + activation layer "
+                              "lists; PPO and A2C run them" % name)
+    if kind in (HEAD_CAT, HEAD_SD) and dist.collectives_active():
+        raise _C.TrlError("%s with a %s policy runs on one rank: the gathered-batch route over several ranks is exercised "
+                          "for the Gaussian head only" % (name, HEAD_NAME[kind]))
+    want = {HEAD_CAT: "Discrete", HEAD_SD: "Box"}.get(kind)
+    space = getattr(env, "action_space", None)
+    # (by what the space carries, not by its class: the CPU twins of the device envs bring Box classes of their own)
+    have = None if space is None else ("Discrete" if hasattr(space, "n") else ("Box" if len(getattr(space, "shape", None) or ()) else None))
+    if want is not None and have != want:
+        raise _C.TrlError("%s with a %s policy is not built for %s: it takes an env whose action space is a %s"
+                          % (name, HEAD_NAME[kind], "no env" if env is None else "the action space %r" % (space,), want))
+    return kind
+
+
 class _GenericPPO(_FusedPPO):
     defers = False                                                     # (its run returns the dicts)
     carries_layernorm = True                                           # `add_ln` nets run here (ops.net_plan, k_layernorm.hip)

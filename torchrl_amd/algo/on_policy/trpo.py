@@ -13,26 +13,31 @@ The CG recurrences themselves are BLAS-1 on ~5 k-element parameter vectors and s
 device (double-precision dot products as in the reference, :93-106); one scalar read-back per CG iteration and per
 line-search trial, as the reference's Python control flow needs.
 `update_vf` = 0.5 * MSE, clip_grad_norm_(0.5), Adam(eps 1e-5) on the value net (:228-251).
-Works for any MLP shape; policies are used as built (examples/trpo_continuous_vec.py passes no tanh squashing)."""
+Works for any MLP shape; policies are used as built (examples/trpo_continuous_vec.py passes no tanh squashing).
+
+The three policy heads (`_GenericPPO.head`) differ in the three element-wise calls only:
+  head                 surrogate                     Fisher scaling               line search's log pi
+  Gaussian, free logstd  trl_trpo_surrogate_f32      trl_fisher_scale_f32         trl_gauss_logp_f32
+  categorical            trl_trpo_surrogate_cat_f32  trl_fisher_scale_cat_f32     trl_cat_logp_f32
+  [mean | log_std]       trl_trpo_surrogate_sd_f32   trl_fisher_scale_sd_f32      trl_gauss_sd_logp_f32
+The flat policy vector of the last two ends with the head layer (no logstd tail); their Fisher product is all network:
+J^T H J / n with H = diag(p) - p p^T in the logits resp. diag(1 / sigma^2 | 2 gate) in the [mean | log_std] head, the
+Hessian of the mean KL at the expansion point (the reference's discrete KL has `+ 1e-8` inside its log, which moves that
+Hessian by O(1e-8 / p): profiles/NOTES_vmpo_trpo_heads.md).  `acts` of a categorical policy: (B,) or (B, 1) floats.
+Refused: LayerNorm nets, the last two heads on several ranks, and either of them with an env whose action space is not of
+the head's kind (Discrete for the categorical, Box for the [mean | log_std] one)."""
 import numpy as np
 import torch
 
 from ... import _C, dist
 from .. import utils as atu
 from .a2c import A2C
-from .ppo import _GenericPPO
+from .ppo import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, _GenericPPO, plain_layer_refusals
 
 
 class TRPO(A2C):
     def __init__(self, max_kl, cg_damping, v_opt_times, cg_iters, residual_tol, **kwargs):
-        from .ppo import HEAD_CAT, HEAD_SD, head_kind
-        kind = head_kind(kwargs.get("pf"))
-        if kind == HEAD_CAT:
-            raise _C.TrlError("TRPO with a categorical policy is not built: its Fisher-vector product and line search are "
-                              "kernels for the diagonal-Gaussian head; discrete actions run on PPO / A2C")
-        if kind == HEAD_SD:
-            raise _C.TrlError("TRPO with a state-dependent-std policy is not built: its Fisher-vector product and line search "
-                              "are kernels for the state-independent logstd; GuassianContPolicy runs on PPO / A2C")
+        plain_layer_refusals("TRPO", kwargs.get("pf"), kwargs.get("vf"), kwargs.get("env"))
         super().__init__(**kwargs)
         self.max_kl, self.cg_damping, self.cg_iters, self.residual_tol = max_kl, cg_damping, cg_iters, residual_tol
         self.v_opt_times = v_opt_times
@@ -81,19 +86,38 @@ class _TRPOEngine(_GenericPPO):
 
     # ---- flat parameter vectors <-> per-layer views ----
     def _views(self, flat):
-        """[(W, b), ...] and the logstd slice of a flat policy-parameter-shaped vector."""
+        """[(W, b), ...] of a flat policy-parameter-shaped vector -- the head layer as wide as the engine's layer list has it
+        -- and the logstd slice behind them (None: the vector of a categorical / [mean | log_std] head ends with the head layer)."""
         out, off = [], 0
         for w, b in self.pf_layers:
             out.append((flat[off:off + w.numel()].view(w.shape), flat[off + w.numel():off + w.numel() + b.numel()]))
             off += w.numel() + b.numel()
-        return out, flat[off:off + self.A]
+        return out, (flat[off:off + self.A] if self.head == HEAD_GAUSS else None)
+
+    def _logstd(self):
+        return self.algo.pf.logstd.detach() if self.head == HEAD_GAUSS else None
 
     def _forward(self, layers):
         return self.ops.mlp_forward(layers, self.obs, self.act)
 
+    def _logp_of(self, head, logstd):
+        """log pi(acts) from the head layer's output (and the logstd vector, for the head that has one)."""
+        if self.head == HEAD_CAT:
+            return _C.cat_logp(head, self.acts)[0]
+        if self.head == HEAD_SD:
+            return _C.gauss_sd_logp(head, self.acts, self.tanh_action)[0]
+        return _C.gauss_logp(head, self.acts, logstd.contiguous(), self.tanh_action)
+
     def _logp(self, layers, logstd):
-        mean, _ = self._forward(layers)
-        return _C.gauss_logp(mean, self.acts, logstd.contiguous(), self.tanh_action)
+        return self._logp_of(self._forward(layers)[0], logstd)
+
+    def _fisher_scale(self, t, head):
+        """d KL / d head along the tangent t of the head layer's output, at the expansion point."""
+        if self.head == HEAD_CAT:
+            return _C.fisher_scale_cat(t, head)
+        if self.head == HEAD_SD:
+            return _C.fisher_scale_sd(t, head)
+        return _C.fisher_scale(t, self._logstd())
 
     def _fvp(self, v):
         """F v + cg_damping * v at the current parameters (tape of the current forward in self.tape)."""
@@ -107,12 +131,13 @@ class _TRPOEngine(_GenericPPO):
             b = None if dh is None else _C.linear_fwd(dh, w, None, _C.ACT_NONE)                # dx W^T
             last = k == n_layers - 1
             dh = _C.jvp_gate(a, b, None if last else tape.outs[k], act)
-        g_mu = _C.fisher_scale(dh, self.algo.pf.logstd.detach())                                # d KL / d mean
+        g_head = self._fisher_scale(dh, tape.outs[-1])                                          # d KL / d head
         out = torch.zeros_like(v)
         ol, o_ls = self._views(out)
-        self.ops.mlp_backward(tape, g_mu, grads=ol, workspace=self._ws(self.n))
-        raw = self.algo.pf.logstd.detach()
-        o_ls.copy_(2.0 * v_ls * ((raw >= -20.0) & (raw <= 2.0)).to(v.dtype))
+        self.ops.mlp_backward(tape, g_head, grads=ol, workspace=self._ws(self.n))
+        if o_ls is not None:
+            raw = self._logstd()
+            o_ls.copy_(2.0 * v_ls * ((raw >= -20.0) & (raw <= 2.0)).to(v.dtype))
         return out + self.algo.cg_damping * v
 
     def _cg(self, b):
@@ -138,11 +163,14 @@ class _TRPOEngine(_GenericPPO):
 
     def _linesearch(self, x, fullstep, expected_improve_rate):
         fval = self._surrogate(x)
+        self.search = []                                                 # (actual improvement, acceptance ratio) per trial
         for stepfrac in .5 ** np.arange(10):
             xnew = x + float(stepfrac) * fullstep
             actual = fval - self._surrogate(xnew)
-            if actual / (expected_improve_rate * float(stepfrac)) > .1 and actual > 0:
+            self.search.append((actual, actual / (expected_improve_rate * float(stepfrac))))
+            if self.search[-1][1] > .1 and actual > 0:
                 return xnew
+        self.search.append(None)                                         # (no trial was accepted)
         return x
 
     def update(self, batch):
@@ -151,7 +179,11 @@ class _TRPOEngine(_GenericPPO):
             .to(device=dev, dtype=torch.float32).contiguous()
         self.obs, self.acts = as_t(batch['obs']), as_t(batch['acts'])
         advs = as_t(batch['advs']).reshape(-1)
+        if self.head == HEAD_CAT:
+            self.acts = self.acts.reshape(-1)                              # one index per sample, given as (B,) or (B, 1)
         if dist.collectives_active():
+            if self.head != HEAD_GAUSS:
+                raise _C.TrlError("TRPO with a %s policy runs on one rank" % HEAD_NAME[self.head])
             # The natural-gradient step (CG on Fisher products, line search) is one global solve: gather the env shards
             # and run it replicated on the single-process batch -- identical parameters on every rank, no exchange.
             ne = int(algo.replay_buffer.env_nums)
@@ -162,13 +194,19 @@ class _TRPOEngine(_GenericPPO):
         raw, info = self._stat[:4], self._stat[4:9]
         _C.adv_stats(advs.view(1, n), self._zero_idx, raw.view(1, 4))
         self.adv_n = _C.adv_normalize(advs, raw, n, eps=1e-4)            # trpo.py:168
-        logstd = algo.pf.logstd.detach()
-        mean, self.tape = self._forward(self.pf_layers)
+        logstd = self._logstd()
+        head, self.tape = self._forward(self.pf_layers)
         g = torch.zeros(self.P_pf, device=dev)
         gl, g_ls = self._views(g)
-        d_mean = _C.trpo_surrogate(mean, logstd, self.acts, self.adv_n, self.tanh_action, algo.entropy_coeff, g_ls, info)
-        self.ops.mlp_backward(self.tape, d_mean, grads=gl, workspace=self._ws(n))
-        self.lp_old = _C.gauss_logp(mean, self.acts, logstd, self.tanh_action)
+        if self.head == HEAD_CAT:
+            d_head = _C.trpo_surrogate_cat(head, self.acts, self.adv_n, algo.entropy_coeff, info)
+        elif self.head == HEAD_SD:
+            d_head = _C.trpo_surrogate_sd(head, self.acts, self.adv_n, self.tanh_action, algo.entropy_coeff, info)
+        else:
+            d_head = _C.trpo_surrogate(head, logstd, self.acts, self.adv_n, self.tanh_action, algo.entropy_coeff, g_ls, info)
+        self.ops.mlp_backward(self.tape, d_head, grads=gl, workspace=self._ws(n))
+        self.lp_old = self._logp_of(head, logstd)
+        self.search = None                                               # (stays None when the gradient is zero)
         if bool((g != 0).any()):                                          # "ensure gradient is not zero" (:188)
             step = self._cg(-g)
             shs = .5 * step.dot(self._fvp(step))

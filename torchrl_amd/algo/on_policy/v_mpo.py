@@ -9,7 +9,16 @@ the top half of the minibatch by advantage -- as a fixed launch sequence with an
   phi = softmax(adv / eta), log pi, KL(pi || pi_target), L_pi and its gradients, the dual variables' gradients,
   their Adam step and clamp ............... trl_vmpo_losses_f32 (eta, alpha and their moments stay on the device)
   policy backward, clip 0.5 + Adam x2 ..... dense-layer kernels + trl_clip_adam_f32 on the flat [pf | vf] buffer
-One read-back per update.  Works for any MLP shape (the arbitrary-shape engine of ppo.py)."""
+One read-back per update.  Works for any MLP shape (the arbitrary-shape engine of ppo.py).
+
+The loss launch follows the policy head (`_GenericPPO.head`): trl_vmpo_losses_f32 for the free-logstd Gaussian,
+trl_vmpo_losses_sd_f32 for a [mean | log_std] head (std per sample in the policy and in the target), trl_vmpo_losses_cat_f32
+for a categorical one.  The categorical KL is taken as the reference EXECUTES it: kl_divergence of two Categoricals has shape
+(B',), so the `.sum(-1, keepdim=True)` behind it (v_mpo.py:94) sums over the selected half-batch -- L_pi = mean(-phi log pi)
++ alpha * sum KL, the alpha loss uses the sum, KL/mean = KL/max = KL/min = the sum and KL/std is NaN (`kl_reduce` = KL_SUM
+of the fold; profiles/NOTES_vmpo_trpo_heads.md).  `acts` of a categorical policy: (B,) or (B, 1) floats.
+Refused: LayerNorm nets, optimisers other than Adam, the last two heads on several ranks, and either of them with an env
+whose action space is not of the head's kind (Discrete for the categorical, Box for the [mean | log_std] one)."""
 import copy
 
 import numpy as np
@@ -17,19 +26,14 @@ import torch
 
 from ... import _C
 from .a2c import A2C
-from .ppo import _GenericPPO
+from .ppo import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, _GenericPPO, plain_layer_refusals
 
 
 class VMPO(A2C):
     def __init__(self, pf, opt_epochs=10, eta_eps=0.02, alpha_eps=0.1, clipped_value_loss=False, **kwargs):
-        from .ppo import HEAD_CAT, HEAD_SD, head_kind
-        kind = head_kind(pf)
-        if kind == HEAD_CAT:
-            raise _C.TrlError("VMPO with a categorical policy is not built: its KL terms are kernels for the "
-                              "diagonal-Gaussian head; discrete actions run on PPO / A2C")
-        if kind == HEAD_SD:
-            raise _C.TrlError("VMPO with a state-dependent-std policy is not built: its KL terms are kernels for the "
-                              "state-independent logstd; GuassianContPolicy runs on PPO / A2C")
+        plain_layer_refusals("VMPO", pf, kwargs.get("vf"), kwargs.get("env"))
+        if kwargs.get("optimizer_class", torch.optim.Adam) is not torch.optim.Adam:
+            raise _C.TrlError("the V-MPO step implements torch.optim.Adam only")
         self.target_pf = copy.deepcopy(pf)
         super().__init__(pf=pf, **kwargs)
         self.eta_eps, self.alpha_eps = eta_eps, alpha_eps
@@ -85,8 +89,12 @@ class _VMPOEngine(_GenericPPO):
         as_t = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))) \
             .to(device=dev, dtype=torch.float32).contiguous()
         obs, acts = as_t(batch['obs']), as_t(batch['acts'])
+        if self.head == HEAD_CAT:
+            acts = acts.reshape(-1, 1)                                 # one index per sample, given as (B,) or (B, 1)
         advs, rets = as_t(batch['advs']).reshape(-1), as_t(batch['estimate_returns']).reshape(-1)
         if dist.collectives_active():
+            if self.head != HEAD_GAUSS:
+                raise _C.TrlError("VMPO with a %s policy runs on one rank" % HEAD_NAME[self.head])
             # The actor step runs on the top half of the GLOBAL minibatch by advantage, which no rank can pick from its
             # env shard alone: gather the shards (4 small tensors) and run the whole update replicated -- every rank
             # then holds the single-process minibatch, so no gradient exchange is needed and parameters stay identical.
@@ -109,12 +117,18 @@ class _VMPOEngine(_GenericPPO):
         # ---- actor on the top half by advantage (v_mpo.py:64-70) ----
         idx = torch.sort(adv_n, descending=True).indices.chunk(2, dim=0)[0].contiguous()
         obs_s, acts_s, adv_s = _C.gather_rows(obs, idx), _C.gather_rows(acts, idx), adv_n[idx].contiguous()
-        mean, tape_pf = ops.mlp_forward(self.pf_layers, obs_s, self.act)
-        tmean, _ = ops.mlp_forward(self.tlayers, obs_s, self.act)
-        d_mean = _C.vmpo_losses(mean, tmean, algo.pf.logstd.detach(), algo.target_pf.logstd.detach(), acts_s, adv_s,
-                                self.dual, bool(algo.pf.tanh_action), algo.eta_eps, algo.alpha_eps, algo.plr,
-                                self.g_logstd, info)
-        ops.mlp_backward(tape_pf, d_mean, grads=self.gviews[0], workspace=ws)
+        head, tape_pf = ops.mlp_forward(self.pf_layers, obs_s, self.act)
+        thead, _ = ops.mlp_forward(self.tlayers, obs_s, self.act)
+        dual_hyper = (algo.eta_eps, algo.alpha_eps, algo.plr)
+        if self.head == HEAD_CAT:                                      # the reference's KL of two Categoricals: summed
+            d_head = _C.vmpo_losses_cat(head, thead, acts_s.view(-1), adv_s, self.dual, _C.KL_SUM, *dual_hyper, info)
+        elif self.head == HEAD_SD:
+            d_head = _C.vmpo_losses_sd(head, thead, acts_s, adv_s, self.dual, bool(algo.pf.tanh_action), _C.KL_MEAN,
+                                       *dual_hyper, info)
+        else:
+            d_head = _C.vmpo_losses(head, thead, algo.pf.logstd.detach(), algo.target_pf.logstd.detach(), acts_s, adv_s,
+                                    self.dual, bool(algo.pf.tanh_action), *dual_hyper, self.g_logstd, info)
+        ops.mlp_backward(tape_pf, d_head, grads=self.gviews[0], workspace=ws)
         # ---- clip_grad_norm_(0.5) + Adam(eps 1e-5) for both nets ----
         _C.clip_adam(self._adam_args((algo.pf_optimizer.param_groups[0]['lr'], algo.vf_optimizer.param_groups[0]['lr']),
                                      step_count=self.step_count + 1, norms_out=norms.data_ptr()), dev)

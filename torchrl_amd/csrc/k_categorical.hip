@@ -13,20 +13,11 @@
 // One thread owns one row: A <= 64 logits are 256 bytes, re-read from L1 per pass instead of held in registers (A is a
 // run-time value); the ascending-k sums the semantics fix are a per-thread loop anyway.
 #include "trl_common.h"
+#include "trl_cat.h"
 #include "trl_philox.h"
 #include "trl_ppo_loss.h"
 
 #define CAT_THREADS 256
-
-__device__ __forceinline__ float cat_row_max(const float* __restrict__ l, int A, int& arg) {
-  float m = l[0];
-  arg = 0;
-  for (int k = 1; k < A; ++k) {
-    const float x = l[k];
-    if (x > m) { m = x; arg = k; }                                // strict: the lowest index wins a tie
-  }
-  return m;
-}
 
 __global__ __launch_bounds__(CAT_THREADS) void cat_act_kernel(const float* __restrict__ logits, const float* __restrict__ u_in,
                                                               int64_t seed, int64_t ctr, int64_t env_offset,
