@@ -5,6 +5,10 @@
 
 With TRL_CAT_FUSED_ROLLOUT=1 TRL_CAT_FUSED_UPDATE=1 (both opt-in) the synthetic config's 64 x 64 nets are collected by the
 one-launch rollout and updated by the fused two-launch sequence instead of the per-step collector and the generic engine.
+
+`--optimizer {adam,rmsprop,sgd}` (default adam) with `--optimizer_info '{"alpha": 0.95}'` (a JSON object of keyword arguments)
+chooses the optimiser class; A2C constructs it with eps = 1e-5 as the reference does, so `sgd` fails in torch's constructor.
+RMSprop -- the optimiser A2C was published with -- steps on the generic engine.
 """
 import os.path as osp
 import random
@@ -21,6 +25,7 @@ from torchrl.collector.on_policy import VecOnPolicyCollector  # noqa: E402
 from torchrl.env import get_vec_env                       # noqa: E402
 from torchrl.replay_buffers.on_policy import OnPolicyReplayBuffer  # noqa: E402
 from torchrl.utils import Logger, get_args, get_params    # noqa: E402
+from torchrl.utils.args import optimizer_kwargs           # noqa: E402
 
 
 def main():
@@ -50,7 +55,7 @@ def main():
                                      device=device, train_render=False, noise_mode="device", **params["collector"])
     general = dict(params['general_setting'], env=collector.env, replay_buffer=replay_buffer, logger=logger,
                    device=device, collector=collector, save_dir=osp.join(logger.work_dir, "model"))
-    A2C(pf=pf, vf=vf, **params["a2c"], **general).train()
+    A2C(pf=pf, vf=vf, **dict(params["a2c"], **optimizer_kwargs(args, with_info=False)), **general).train()
 
 
 if __name__ == "__main__":

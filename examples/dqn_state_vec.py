@@ -4,6 +4,9 @@ behind `torchrl.env.VecEnv` (no gym in the image): env physics on the host, Q-ne
 and the target update on the GPU kernels.
 
     python examples/dqn_state_vec.py --config config/dqn_cartpole_host.json --vec_env_nums 8 --seed 0 --overwrite
+
+`--optimizer {adam,rmsprop,sgd}` (default adam) and `--optimizer_info '{"alpha": 0.95, "eps": 0.01, "centered": true}'` (a
+JSON object of the optimiser's keyword arguments) choose the step: the classic DQN set-up is `--optimizer rmsprop`.
 """
 import os.path as osp
 import random
@@ -21,6 +24,7 @@ from torchrl.env import VecEnv                            # noqa: E402
 from torchrl.env.py_envs import CartPoleEnv               # noqa: E402
 from torchrl.replay_buffers import BaseReplayBuffer       # noqa: E402
 from torchrl.utils import Logger, get_args, get_params    # noqa: E402
+from torchrl.utils.args import optimizer_kwargs           # noqa: E402
 
 
 def main():
@@ -44,7 +48,7 @@ def main():
                              train_render=False, **params["collector"])
     general = dict(params['general_setting'], env=collector.env, replay_buffer=replay_buffer, logger=logger, device=device,
                    collector=collector, save_dir=osp.join(logger.work_dir, "model"))
-    DQN(pf=pf, qf=qf, **params["dqn"], **general).train()
+    DQN(pf=pf, qf=qf, **dict(params["dqn"], **optimizer_kwargs(args)), **general).train()
 
 
 if __name__ == "__main__":

@@ -451,6 +451,47 @@ int trl_clip_adam_f32(const trl_adam_t* args, void* stream);
  * `ring`; args->step_state is then required */
 int trl_clip_adam_polyak_f32(const trl_adam_t* args, float* target, const float* source, int64_t n, float tau,
                              const void* raw, int raw_bytes, void* ring, int slots, void* stream);
+/* --- global-norm clip + RMSprop / SGD ---------------------------------------
+ * clip_grad_norm_(params, max_norm) + torch.optim.RMSprop.step() / torch.optim.SGD.step() (single-tensor arithmetic) for up
+ * to 4 parameter groups laid out back to back in params / grads / state0..2: the launch behind trl_clip_adam_f32's call
+ * sites for the other two optimiser classes.  The clip is trl_clip_adam_f32's, summation order included: norms_out carries
+ * the same bits for the same gradients.  With g the scaled and clipped gradient:
+ *   RMSprop: g += weight_decay p; sq = alpha sq + (1 - alpha) g g; centered: ga += (g - ga)(1 - alpha),
+ *            avg = sqrt(sq - ga ga) + eps, else avg = sqrt(sq) + eps; momentum: buf = momentum buf + g / avg, p -= lr buf,
+ *            else p -= lr g / avg.
+ *   SGD:     g += weight_decay p; momentum: buf = g on a group's first step, else buf = momentum buf + (1 - dampening) g;
+ *            g = nesterov ? g + momentum buf : buf; p -= lr g.
+ * One thread per element, no in-kernel wait. */
+enum { TRL_OPT_RMSPROP = 1, TRL_OPT_SGD = 2 };
+typedef struct trl_opt_t {
+  int kind;
+  float* params; const float* grads;
+  float* state0;              /* RMSprop: square_avg            SGD: momentum_buffer (NULL iff momentum == 0) */
+  float* state1;              /* RMSprop: momentum_buffer (NULL iff momentum == 0)      SGD: unused */
+  float* state2;              /* RMSprop: grad_avg (NULL iff !centered)                 SGD: unused */
+  int n_groups;               /* 1..4, each clipped by its own global norm */
+  int group_sizes[4];
+  float group_lr[4];
+  float max_norm;             /* <= 0: no clipping, the norm pass is skipped and 0 is written to norms_out */
+  float grad_scale;           /* grads are multiplied by this first (1/world_size) */
+  float* norms_out;           /* (n_groups), nullable */
+  double* step_state;         /* nullable: trl_adam_t's four doubles.  This launch reads slot 0 (SGD's first step is
+                                 step_state[0] == 0) and advances slot 0 only, by 1 -- the last block that has read it
+                                 (up to 32 768 elements; slot 3 is the block counter, zero between launches) or a
+                                 one-thread kernel */
+  const float* device_lr;     /* nullable: n_groups learning rates on the device, used instead of group_lr */
+  float alpha, eps, momentum, dampening, weight_decay;
+  int centered, nesterov;
+  int first_step;             /* SGD with momentum and NO step_state: non-zero on the first step of the buffers (buf = g);
+                                 ignored when step_state is given */
+} trl_opt_t;
+/* TRL_EINVAL: a null state pointer the options need, n_groups outside 1..4, nesterov with zero momentum or non-zero
+ * dampening, an unknown kind. */
+int trl_clip_step_f32(const trl_opt_t* args, void* stream);
+/* the same followed by trl_clip_adam_polyak_f32's Polyak / filing launch (that very kernel): where the step state would
+ * need the one-thread tick launch, the Polyak kernel advances it.  ring non-NULL without args->step_state: TRL_EINVAL. */
+int trl_clip_step_polyak_f32(const trl_opt_t* args, float* target, const float* source, int64_t n, float tau,
+                             const void* raw, int raw_bytes, void* ring, int slots, void* stream);
 /* The whole tail of an off-policy update as ONE launch (twin_sac_q.py:162-220, algo/utils.py:16-20): the fold of the split
  * weight-gradient partials of every layer (entry k: splits[k] slices of n[k] floats at part[k]; the entries cover
  * args->grads -- which receives the folded gradient -- exactly, in order; trl_fold_partials_multi_f32's summation order),

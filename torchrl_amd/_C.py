@@ -121,6 +121,45 @@ def adam_args(flat, grads, m, v, sizes, lrs, *, offset=0, max_norm=0.0, eps=1e-8
     return a
 
 
+OPT_RMSPROP, OPT_SGD = 1, 2                                       # TRL_OPT_* of include/trl_hip.h
+
+
+class OptArgs(C.Structure):             # include/trl_hip.h trl_opt_t
+    _fields_ = [
+        ("kind", C.c_int), ("params", C.c_void_p), ("grads", C.c_void_p),
+        ("state0", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p),
+        ("n_groups", C.c_int), ("group_sizes", C.c_int * 4), ("group_lr", C.c_float * 4),
+        ("max_norm", C.c_float), ("grad_scale", C.c_float), ("norms_out", C.c_void_p),
+        ("step_state", C.c_void_p), ("device_lr", C.c_void_p),
+        ("alpha", C.c_float), ("eps", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float),
+        ("weight_decay", C.c_float), ("centered", C.c_int), ("nesterov", C.c_int), ("first_step", C.c_int),
+    ]
+
+
+def opt_args(spec, flat, grads, states, sizes, lrs, *, offset=0, max_norm=0.0, grad_scale=1.0, norms_out=None,
+             step_state=None, device_lr=None, first_step=0):
+    """OptArgs of an RMSprop / SGD step: `spec` is algo/_optim.py's step_spec tuple, `states` the (up to three) flat
+    state buffers in trl_opt_t's order (None where the options need none); the rest as in `adam_args`."""
+    a = OptArgs()
+    at = lambda t: None if t is None else t.data_ptr() + int(offset) * t.element_size()
+    states = tuple(states) + (None,) * (3 - len(states))
+    a.params, a.grads, a.state0, a.state1, a.state2 = at(flat), at(grads), at(states[0]), at(states[1]), at(states[2])
+    a.n_groups = len(sizes)
+    for k, (size, lr) in enumerate(zip(sizes, lrs)):
+        a.group_sizes[k], a.group_lr[k] = size, lr
+    a.max_norm, a.grad_scale, a.norms_out, a.step_state, a.device_lr = max_norm, grad_scale, norms_out, step_state, device_lr
+    if spec[0] == "rmsprop":
+        a.kind = OPT_RMSPROP
+        a.alpha, a.eps, a.momentum, a.centered, a.weight_decay = spec[1], spec[2], spec[3], int(bool(spec[4])), spec[5]
+    elif spec[0] == "sgd":
+        a.kind = OPT_SGD
+        a.momentum, a.dampening, a.nesterov, a.weight_decay = spec[1], spec[2], int(bool(spec[3])), spec[4]
+    else:
+        raise TrlError("opt_args: %r is not an RMSprop / SGD step (Adam goes through adam_args)" % (spec[0],))
+    a.first_step = int(first_step)
+    return a
+
+
 class ConvRiders(C.Structure):          # include/trl_hip.h trl_conv_riders_t
     _fields_ = [("n_perm", C.c_int), ("perm_src", C.c_void_p * 4), ("perm_dst", C.c_void_p * 4), ("perm_cout", C.c_int * 4),
                 ("perm_c", C.c_int * 4), ("perm_khw", C.c_int * 4), ("n_dx", C.c_int), ("dx_w", C.c_void_p * 4),
@@ -231,6 +270,9 @@ SIGNATURES = {
     "trl_tanh_gauss_rsample_bwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "trl_tanh_gauss_rsample_bwd_cols_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] + [C.c_float] * 3 +
                                             [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "trl_clip_step_f32": (C.c_int, [C.POINTER(OptArgs), C.c_void_p]),
+    "trl_clip_step_polyak_f32": (C.c_int, [C.POINTER(OptArgs), C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p]),
     "trl_fold_clip_adam_polyak_workspace": (C.c_int, []),
     "trl_fold_clip_adam_polyak_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamArgs), C.c_void_p,
                                               C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
@@ -703,19 +745,27 @@ def clip_adam(args, device):
     check(lib().trl_clip_adam_f32(C.byref(args), stream_ptr(device)), "trl_clip_adam_f32")
 
 
-def clip_adam_polyak(args, target, source, tau, device, file=None):
+def clip_step(args, device):
+    """`clip_adam` for an `opt_args` descriptor (RMSprop / SGD)."""
+    check(lib().trl_clip_step_f32(C.byref(args), stream_ptr(device)), "trl_clip_step_f32")
+
+
+def clip_step_polyak(args, target, source, tau, device, file=None):
+    """`clip_adam_polyak` for an `opt_args` descriptor (RMSprop / SGD)."""
+    clip_adam_polyak(args, target, source, tau, device, file, fn="trl_clip_step_polyak_f32")
+
+
+def clip_adam_polyak(args, target, source, tau, device, file=None, fn="trl_clip_adam_polyak_f32"):
     """clip + Adam, then target <- (1 - tau) target + tau source (the Polyak kernel also advances the device step state).
     file = (raw uint8 statistics block, ring (slots, raw bytes) uint8): the Polyak launch also archives `raw` into ring row
     (steps taken before this update) % slots."""
     raw, ring = file if file is not None else (None, None)
     if ring is not None and (ring.dim() != 2 or int(ring.shape[1]) != raw.numel() or not ring.is_contiguous()):
         raise TrlError("clip_adam_polyak: ring rows must be statistics blocks")
-    check(lib().trl_clip_adam_polyak_f32(C.byref(args), dev_ptr(target, name="target"), dev_ptr(source, name="source"),
-                                         int(target.numel()), float(tau), dev_ptr(raw, torch.uint8, "raw", allow_none=True),
-                                         0 if raw is None else int(raw.numel()),
-                                         dev_ptr(ring, torch.uint8, "ring", allow_none=True),
-                                         0 if ring is None else int(ring.shape[0]), stream_ptr(device)),
-          "trl_clip_adam_polyak_f32")
+    check(getattr(lib(), fn)(C.byref(args), dev_ptr(target, name="target"), dev_ptr(source, name="source"),
+                             int(target.numel()), float(tau), dev_ptr(raw, torch.uint8, "raw", allow_none=True),
+                             0 if raw is None else int(raw.numel()), dev_ptr(ring, torch.uint8, "ring", allow_none=True),
+                             0 if ring is None else int(ring.shape[0]), stream_ptr(device)), fn)
 
 
 def fold_clip_adam_polyak_workspace(device):

@@ -9,6 +9,7 @@ import torch
 
 from ... import _C, dist
 from ...networks import flatten_into
+from .. import _optim
 from .._graphs import GraphCache  # noqa: F401  (the engines and tests import it from here)
 
 
@@ -28,13 +29,16 @@ class FlatHome:
             self.m, self.v = keep[0].to(self.flat.device), keep[1].to(self.flat.device)
         else:
             self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        # Adam: m = exp_avg, v = exp_avg_sq.  RMSprop: m = square_avg, v = momentum_buffer, c = grad_avg (allocated for a
+        # centered RMSprop only).  SGD: m = momentum_buffer.  The state is bound under torch's names for the class.
+        self.specs = [_optim.step_spec(opt) for opt in optimizers]
+        self.c = torch.zeros_like(self.flat) if _optim.needs_third(self.specs) else None
         self.views, self._counts, off = [], [len(pl) for pl in plists], 0
-        for opt, pl in zip(optimizers, plists):
+        for opt, spec, pl in zip(optimizers, self.specs, plists):
+            _optim.bind_state(opt, spec, pl, off, (self.m, self.v, self.c))
             for p in pl:
                 n = p.numel()
                 self.views.append(self.grads[off:off + n].view(p.shape))
-                opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + n].view(p.shape),
-                                "exp_avg_sq": self.v[off:off + n].view(p.shape)}
                 off += n
 
     def pairs(self):

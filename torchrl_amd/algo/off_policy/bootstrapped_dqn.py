@@ -86,6 +86,7 @@ class _FusedBootDQN(_FusedDQN):
         plist, tlist = qf.param_list(), tqf.param_list()
         home = FlatHome([plist], [algo.qf_optimizer], tlist, keep=(self.m, self.v) if hasattr(self, "m") else None)
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
+        self.opt_spec, self.c = home.specs[0], home.c                    # (Adam: `engine()` refuses anything else)
         pairs = home.pairs()[0]
         nt, nh = len(self.trunk), len(self.heads[0])
         self.trunk_gviews = pairs[:nt]

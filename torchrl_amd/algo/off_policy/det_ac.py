@@ -7,7 +7,7 @@ TwinSACQ with an explicit chain rule instead of autograd:
   target smoothing (TD3) .. trl_noisy_action_f32 (explore noise of target_pf, then the clipped smoothing noise)
   TD target, MSE, dQ ...... trl_detac_losses_f32 (also -mean Q(s, pi(s)) and its gradient)
   dL/da through the critic  bwd_input of the Q net + trl_slice_add_f32
-  clip + Adam ............. trl_clip_adam_f32 on one flat [pf | qf (| qf2)] buffer
+  clip + step ............. trl_clip_adam_f32 (Adam) or trl_clip_step_f32 (RMSprop, SGD) on one flat [pf | qf (| qf2)] buffer
   target update ........... trl_polyak_f32 on the flat buffers (policy AND critics, as the reference does)
 The reference's order of operations is kept, including TD3's delayed policy step, which is taken when
 `training_update_num % policy_update_delay != 0` (td3.py:124, as written) and evaluates Q1 AFTER its step.
@@ -20,6 +20,7 @@ import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
+from .. import _optim
 from ._deferred import StatRing
 from ._engine import FlatHome, GraphCache, load_static
 from .off_rl_algo import OffRLAlgo
@@ -129,8 +130,6 @@ class _FusedDetAC:
     """Flat [pf | qf1 (| qf2)] parameter / gradient / Adam-state buffers and the two launch sequences."""
 
     def __init__(self, algo, nets, targets, optimizers):
-        if algo.optimizer_class is not optim.Adam:
-            raise _C.TrlError("the fused DDPG / TD3 step implements torch.optim.Adam only")
         self.algo = algo
         self.dev = next(nets[0].parameters()).device
         if self.dev.type != "cuda":
@@ -146,7 +145,8 @@ class _FusedDetAC:
         home = FlatHome(plists, optimizers, [t for ls in self.tlayers for wb in ls for t in wb])
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
         self.sizes, self.offsets, self.gviews = home.sizes, home.offsets, home.pairs()
-        self.optimizers = optimizers
+        self.optimizers, self.c = optimizers, home.c                       # (c: grad_avg of a centered RMSprop, else None)
+        self._state_names = [_optim.state_names(s) for s in home.specs]
         self.steps = [0] * len(nets)                                       # per-network Adam step counts (TD3's policy lags)
         self._raw = torch.zeros(96 + 16, dtype=torch.uint8, device=self.dev)   # every logged statistic: one D2H per update
         self.sums = self._raw[0:32].view(torch.float64)
@@ -200,19 +200,27 @@ class _FusedDetAC:
     def _run(self, key, seq):
         """`seq` through the graph cache, under `key` and everything else a captured sequence has baked in."""
         algo = self.algo
-        self._graphs.run(key + (self._lrs(), algo.grad_clip, algo.tau, algo.discount), seq)
+        self._graphs.run(key + (self._lrs(), algo.grad_clip, algo.tau, algo.discount, self._specs()), seq)
+
+    def _specs(self):
+        """Every optimiser's step as it holds it now (`_optim.step_spec`); which state buffers exist was settled at the home."""
+        specs = tuple(_optim.step_spec(o) for o in self.optimizers)
+        if [_optim.state_names(s) for s in specs] != self._state_names:
+            raise _C.TrlError("an optimiser's momentum / centered options changed after the engine was built")
+        return specs
 
     def _adam(self, which):
-        """clip_grad_norm_ + Adam for the networks in `which` (indices into the flat buffer), one launch each;
-        every network keeps its own step count, on the device."""
-        algo = self.algo
+        """clip_grad_norm_ + the optimiser's step (Adam, RMSprop or SGD) for the networks in `which` (indices into the flat
+        buffer), one launch each; every network keeps its own step count, on the device (SGD reads its first step there)."""
+        algo, specs = self.algo, self._specs()
         for k in which:
             dist.all_reduce_sum_(self.grads[int(self.offsets[k]):int(self.offsets[k + 1])])   # C1: local means -> SUM / world
-            a = _C.adam_args(self.flat, self.grads, self.m, self.v, [self.sizes[k]], [self.optimizers[k].param_groups[0]['lr']],
-                             offset=self.offsets[k], max_norm=float(algo.grad_clip) if algo.grad_clip else 0.0,
-                             grad_scale=1.0 / dist.world_size(), norms_out=self.norms.data_ptr() + 4 * k,
-                             step_state=self.step_state.data_ptr() + 32 * k)
-            _C.clip_adam(a, self.dev)
+            a = _optim.step_args(specs[k], self.flat, self.grads, (self.m, self.v, self.c), [self.sizes[k]],
+                                 [self.optimizers[k].param_groups[0]['lr']], offset=self.offsets[k],
+                                 max_norm=float(algo.grad_clip) if algo.grad_clip else 0.0,
+                                 grad_scale=1.0 / dist.world_size(), norms_out=self.norms.data_ptr() + 4 * k,
+                                 step_state=self.step_state.data_ptr() + 32 * k)
+            _optim.clip_step(a, self.dev)
 
     def _hard_update_due(self):
         algo = self.algo

@@ -14,6 +14,7 @@ import torch
 import torch.optim as optim
 
 from ... import _C, dist, ops
+from .. import _optim
 from ._deferred import IndexSlab, StatRing
 from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static
 from .off_rl_algo import OffRLAlgo
@@ -48,8 +49,6 @@ class DQN(_EngineSurface, OffRLAlgo):
 
     def engine(self):
         if self._engine is None:
-            if self.optimizer_class is not optim.Adam:
-                raise _C.TrlError("the fused DQN step implements torch.optim.Adam only")
             self._engine = _FusedDQN(self)
         return self._engine
 
@@ -77,6 +76,7 @@ class _FusedDQN(_FusedOffPolicy):
             plist, tlist = ops.cnn_param_list(algo.qf), ops.cnn_param_list(algo.target_qf)
         home = FlatHome([plist], [algo.qf_optimizer], tlist)
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
+        self.opt_spec, self.c = home.specs[0], home.c                     # (the whole of `optimizer_info`, as torch read it)
         self.gviews = home.pairs()[0]
         self.A = int(algo.env.action_space.n)
         self._init_run_state()
@@ -177,21 +177,29 @@ class _FusedDQN(_FusedOffPolicy):
         dist.all_reduce_sum_(self.sums)
 
     def _adam_polyak(self, soft, grad_scale):
-        """Adam over the whole flat buffer, then Polyak when `soft` (which also advances the step state)."""
+        """The optimiser's step (Adam, RMSprop or SGD: `_optim.step_spec`) over the whole flat buffer, then Polyak when
+        `soft` (which also advances the step state)."""
         algo = self.algo
-        a = _C.adam_args(self.flat, self.grads, self.m, self.v, [self.flat.numel()], [algo.qf_optimizer.param_groups[0]['lr']],
-                         eps=float(algo.optimizer_info.get("eps", 1e-8)), grad_scale=grad_scale,
-                         step_state=self.step_state.data_ptr())
+        a = _optim.step_args(self._spec(), self.flat, self.grads, (self.m, self.v, self.c), [self.flat.numel()],
+                             [algo.qf_optimizer.param_groups[0]['lr']], grad_scale=grad_scale,
+                             step_state=self.step_state.data_ptr())
         if soft:
-            _C.clip_adam_polyak(a, self.tflat, self.flat, algo.tau, self.dev)
+            _optim.clip_step_polyak(a, self.tflat, self.flat, algo.tau, self.dev)
         else:
-            _C.clip_adam(a, self.dev)
+            _optim.clip_step(a, self.dev)
+
+    def _spec(self):
+        """The step's hyper-parameters as the optimiser holds them now; which state buffers exist was settled at the home."""
+        spec = _optim.step_spec(self.algo.qf_optimizer)
+        if _optim.state_names(spec) != _optim.state_names(self.opt_spec):
+            raise _C.TrlError("the optimiser's momentum / centered options changed after the engine was built")
+        return spec
 
     def _epoch_key(self, soft):
         """What a captured launch sequence has baked in, beside its shapes."""
         algo = self.algo
         return (soft, float(algo.qf_optimizer.param_groups[0]['lr']), float(algo.discount), float(algo.tau),
-                int(algo.quantile_num))
+                int(algo.quantile_num), self._spec())
 
     def enqueue(self, batch):
         """Launch one update without waiting for it; its loss sums wait in their ring row for `resolve`."""

@@ -29,6 +29,7 @@ from ... import _C
 from ... import dist
 from ...networks import ZeroNet, flatten_into
 from ...policies.continuous_policy import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, HEAD_TAG, head_kind, is_state_std  # noqa: F401
+from .. import _optim
 from .. import utils as atu
 from .._graphs import GraphCache, LastGraph
 from .a2c import A2C
@@ -70,8 +71,6 @@ class PPO(A2C):
 
     def engine(self):
         if self._engine is None:
-            if self.optimizer_class is not optim.Adam:
-                raise _C.TrlError("the fused PPO step implements torch.optim.Adam only")
             self._engine = make_engine(self)
         return self._engine
 
@@ -224,23 +223,30 @@ class _FusedPPO:
         self.m, self.v, self.grads = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
         self.step_count = 0
         self.target_flat = None if target_list is None else flatten_into(target_list)
+        # the step both optimisers take (`_optim.step_spec`).  Adam: m = exp_avg, v = exp_avg_sq; RMSprop: m = square_avg,
+        # v = momentum_buffer, c = grad_avg (centered only); SGD: m = momentum_buffer -- bound under torch's names for the class
+        self.opt_spec = _optim.step_spec(algo.pf_optimizer)
+        if self.opt_spec[0] not in self.step_kinds:
+            raise _C.TrlError("%s implements torch.optim.Adam only (got %s)"
+                              % (type(self).__name__, type(algo.pf_optimizer).__name__))
+        if vf_list and _optim.step_spec(algo.vf_optimizer) != self.opt_spec:
+            raise _C.TrlError("the policy's and the value function's optimisers must take the same step (%r / %r)"
+                              % (self.opt_spec, _optim.step_spec(algo.vf_optimizer)))
+        self.c = torch.zeros_like(self.flat) if _optim.needs_third([self.opt_spec]) else None
         if not vf_list:
-            self.eps = float(algo.pf_optimizer.param_groups[0]['eps'])
+            self.eps = float(algo.pf_optimizer.param_groups[0].get('eps', self.eps))
         for net, plist, opt, lo in ((algo.pf, pf_list, "pf_optimizer", 0), (algo.vf, vf_list, "vf_optimizer", self.P_pf)):
             if plist:
                 if getattr(net, "mlp2_spec", lambda: None)() is not None:
                     net._flat = self.flat[lo:lo + sum(p.numel() for p in plist)]
                 self._alias_optimizer_state(getattr(algo, opt), plist, lo)
 
+    step_kinds = ("adam",)                                           # what `_optim.step_spec` may name for this engine
+    c = None                                                         # the third state buffer: a centered RMSprop's alone
+
     def _alias_optimizer_state(self, opt, plist, offset):
         self._opt_steps = getattr(self, "_opt_steps", [])
-        for p in plist:
-            n = p.numel()
-            step = torch.tensor(0.0)
-            opt.state[p] = {"step": step, "exp_avg": self.m[offset:offset + n].view(p.shape),
-                            "exp_avg_sq": self.v[offset:offset + n].view(p.shape)}
-            self._opt_steps.append(step)
-            offset += n
+        self._opt_steps += _optim.bind_state(opt, self.opt_spec, plist, offset, (self.m, self.v, self.c))
 
     def sync_target_pf(self, in_prologue=False):
         """target_pf <- pf.  in_prologue (called from an epoch's device prologue): the copy rides in the launch that
@@ -316,9 +322,13 @@ class _FusedPPO:
 
     def _adam_args(self, lrs=(0.0, 0.0), **kw):
         """clip_grad_norm_(0.5) + Adam(`eps`) over the groups of the flat buffers: one per network that exists."""
+        return self._step_args(("adam", self.eps), lrs, **kw)
+
+    def _step_args(self, spec, lrs=(0.0, 0.0), **kw):
+        """`_adam_args` for the step `spec` names: an AdamArgs, or the OptArgs of an RMSprop / SGD launch."""
         groups = [(n, lr) for n, lr in zip((self.P_pf, self.P_vf), lrs) if n]
-        return _C.adam_args(self.flat, self.grads, self.m, self.v, [n for n, _ in groups], [lr for _, lr in groups],
-                            max_norm=0.5, eps=self.eps, **kw)
+        return _optim.step_args(spec, self.flat, self.grads, (self.m, self.v, self.c), [n for n, _ in groups],
+                                [lr for _, lr in groups], max_norm=0.5, **kw)
 
     def _batch_args(self, t, hyper, loss_mode, rows_mb, N, n_global, partial, scal, n_wg, n_wg_pf):
         """trl_ppo_batch_t of a gradient launch over `n_wg` workgroups that leave their rows in `partial` / `scal`."""
@@ -801,6 +811,7 @@ def plain_layer_refusals(name, pf, vf, env):
 
 class _GenericPPO(_FusedPPO):
     defers = False                                                     # (its run returns the dicts)
+    step_kinds = ("adam", "rmsprop", "sgd")                            # trl_clip_adam_f32 / trl_clip_step_f32 behind `run`
     carries_layernorm = True                                           # `add_ln` nets run here (ops.net_plan, k_layernorm.hip)
     """PPO / A2C minibatch loop for ARBITRARY MLP shapes (any observation / action size, width, depth): the layers run
     on the generic dense-layer kernels (k_gemm.hip, through ops.mlp_forward / mlp_backward), the loss half on
@@ -866,6 +877,14 @@ class _GenericPPO(_FusedPPO):
         self._graphs, self._joint = GraphCache(4), None
         self.workspace = None
 
+    def _spec(self):
+        """The step as the policy's optimiser holds it now (Adam: the engine's own `eps`); which state buffers exist was
+        settled at the home."""
+        spec = _optim.step_spec(self.algo.pf_optimizer)
+        if _optim.state_names(spec) != _optim.state_names(self.opt_spec):
+            raise _C.TrlError("the optimiser's momentum / centered options changed after the engine was built")
+        return ("adam", self.eps) if spec[0] == "adam" else spec
+
     def _ws(self, B):
         need = max(_C.lib().trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0]))
                    for w in (l[0] for l in self.pf_layers + self.vf_layers))
@@ -907,6 +926,7 @@ class _GenericPPO(_FusedPPO):
         gather = lambda key, k: None if t.get(key) is None else \
             _C.gather_rows(t[key].reshape(rows_total, N, -1), idx2d[k]).reshape(n_local, -1)
         hyper = _hyper(algo) + (loss_mode,)
+        spec = self._spec()
 
         def launch_all():
             if pre is not None:
@@ -924,11 +944,11 @@ class _GenericPPO(_FusedPPO):
                 if self.vf_layers:
                     ops.mlp_backward(tape_vf, d_v, grads=self.gviews[1], workspace=ws)
                 dist.all_reduce_sum_(self.grads)                       # C1: gradient SUM over ranks
-                _C.clip_adam(self._adam_args(norms_out=norms[k].data_ptr(), step_state=self.step_state.data_ptr(),
-                                             device_lr=self.lr_dev.data_ptr()), dev)     # device-side step count / lr
+                _optim.clip_step(self._step_args(spec, norms_out=norms[k].data_ptr(), step_state=self.step_state.data_ptr(),
+                                                 device_lr=self.lr_dev.data_ptr()), dev)  # device-side step count / lr
 
         # eager on the first visit of a configuration, captured into a HIP graph on the second, replayed afterwards
-        key = (K, rows_mb, N, rows_total, n_global, idx_dev.data_ptr(), stats.data_ptr(), pre_key, pre is not None) + hyper + tuple(
+        key = (K, rows_mb, N, rows_total, n_global, idx_dev.data_ptr(), stats.data_ptr(), pre_key, pre is not None, spec) + hyper + tuple(
             0 if t.get(k_) is None else t[k_].data_ptr() for k_ in ("obs", "acts", "advs", "rets", "old_values", "old_logp"))
         self._graphs.run(key, launch_all)
         self._stepped(K)
@@ -952,6 +972,9 @@ def make_engine(algo, fused=_FusedPPO, generic=_GenericPPO):
     blocks = ps is not None and (vf is None or vs is not None)         # every network there is is an MLP2 block
     forced = os.environ.get("TRL_GENERIC_PPO") == "1"
     kind = head_kind(pf)
+    opt = getattr(algo, "pf_optimizer", None)
+    if opt is not None and type(opt) is not optim.Adam:
+        return generic(algo)                                           # RMSprop / SGD: the fused fold / clip / Adam launches are Adam's
     if kind in _HEAD_OPT_IN:
         # categorical / [mean | log_std] head: the generic engine, unless the fused update is asked for (TRL_CAT_FUSED_UPDATE=1 /
         # TRL_SD_FUSED_UPDATE=1, opt-in) AND the nets have a shape the head's instantiations carry, the optimiser is Adam and

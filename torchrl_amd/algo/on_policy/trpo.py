@@ -38,6 +38,8 @@ from .ppo import HEAD_CAT, HEAD_GAUSS, HEAD_NAME, HEAD_SD, _GenericPPO, plain_la
 class TRPO(A2C):
     def __init__(self, max_kl, cg_damping, v_opt_times, cg_iters, residual_tol, **kwargs):
         plain_layer_refusals("TRPO", kwargs.get("pf"), kwargs.get("vf"), kwargs.get("env"))
+        if kwargs.get("optimizer_class", torch.optim.Adam) is not torch.optim.Adam:
+            raise _C.TrlError("the TRPO value step implements torch.optim.Adam only")
         super().__init__(**kwargs)
         self.max_kl, self.cg_damping, self.cg_iters, self.residual_tol = max_kl, cg_damping, cg_iters, residual_tol
         self.v_opt_times = v_opt_times
@@ -76,6 +78,7 @@ class TRPO(A2C):
 
 class _TRPOEngine(_GenericPPO):
     carries_layernorm = False                                          # (its own passes walk the plain layer lists)
+    step_kinds = ("adam",)                                             # (`update_vf` launches trl_clip_adam_f32 itself)
 
     def __init__(self, algo):
         super().__init__(algo)

@@ -72,6 +72,7 @@ class VMPO(A2C):
 
 class _VMPOEngine(_GenericPPO):
     carries_layernorm = False                                          # (its own passes walk the plain layer lists)
+    step_kinds = ("adam",)                                             # (its launches are trl_clip_adam_f32's, duals included)
 
     def __init__(self, algo):
         super().__init__(algo)

@@ -1859,18 +1859,25 @@ __global__ __launch_bounds__(256) void polyak_tick_kernel(float* __restrict__ tg
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
     tgt[e] = tgt[e] * (1.0f - tau) + src[e] * tau;
 }
+// the launch itself (trl_common.h): behind clip_adam_kernel here and behind k_optim.hip's step kernel
+int trl_polyak_file_launch(float* target, const float* source, int64_t n, float tau, double* tick_state, float beta1,
+                           float beta2, const void* raw, int raw_bytes, void* ring, const double* count, int slots,
+                           int ticked, void* stream) {
+  int grid = trl_ceil_div(n, 256);
+  if (grid > 1024) grid = 1024;
+  FileRing file = {(const uint32_t*)raw, (uint32_t*)ring, count, raw_bytes / 4, slots, ticked};
+  hipLaunchKernelGGL(polyak_tick_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, target, source, n, tau,
+                     tick_state, beta1, beta2, file);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
+}
 static int clip_adam_polyak(const trl_adam_t* p, float* target, const float* source, int64_t n, float tau,
                             const void* raw, int raw_bytes, void* ring, int slots, void* stream) {
   TRL_REQUIRE(n > 0 && target && source, "polyak: empty / null");
   int rc = clip_adam_launch(p, stream, false);
   if (rc != TRL_OK && rc != TICK_PENDING) return rc;
-  int grid = trl_ceil_div(n, 256);
-  if (grid > 1024) grid = 1024;
-  FileRing file = {(const uint32_t*)raw, (uint32_t*)ring, p->step_state, raw_bytes / 4, slots, rc == TICK_PENDING ? 0 : 1};
-  hipLaunchKernelGGL(polyak_tick_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, target, source, n, tau,
-                     rc == TICK_PENDING ? p->step_state : (double*)nullptr, p->beta1, p->beta2, file);
-  TRL_LAUNCH_CHECK();
-  return TRL_OK;
+  return trl_polyak_file_launch(target, source, n, tau, rc == TICK_PENDING ? p->step_state : (double*)nullptr, p->beta1,
+                                p->beta2, raw, raw_bytes, ring, p->step_state, slots, rc == TICK_PENDING ? 0 : 1, stream);
 }
 extern "C" int trl_clip_adam_polyak_f32(const trl_adam_t* p, float* target, const float* source, int64_t n, float tau,
                                         const void* raw, int raw_bytes, void* ring, int slots, void* stream) {

@@ -15,6 +15,13 @@ void trl_set_error(const char* fmt, ...);
        if (e_ != hipSuccess) { trl_set_error("%s: %s", __func__, hipGetErrorString(e_)); \
                                return (int)e_; } } while (0)
 
+// k_ppo.hip's Polyak step target <- (1 - tau) target + tau source of n floats, whose block 0 also files `raw` into row
+// (count[0] - ticked) mod slots of `ring` (ring nullable) and advances `tick_state` {steps, beta1^steps, beta2^steps}
+// (nullable) -- the launch behind a clip + step kernel of any file.
+int trl_polyak_file_launch(float* target, const float* source, int64_t n, float tau, double* tick_state, float beta1,
+                           float beta2, const void* raw, int raw_bytes, void* ring, const double* count, int slots,
+                           int ticked, void* stream);
+
 static inline int trl_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4  __attribute__((ext_vector_type(4)));

@@ -17,7 +17,10 @@ _FLAGS = (
     ("overwrite", None, False, "overwrite previous experiments"),
     ("device", int, 0, "gpu specification"),
     ("id", str, None, "experiment id"),
+    ("optimizer", str, "adam", "adam | rmsprop | sgd (the examples that pass it on: see optimizer_kwargs)"),
+    ("optimizer_info", str, "{}", "the optimiser's keyword arguments as a JSON object, e.g. '{\"alpha\": 0.95, \"eps\": 0.01}'"),
 )
+OPTIMIZERS = {"adam": torch.optim.Adam, "rmsprop": torch.optim.RMSprop, "sgd": torch.optim.SGD}
 
 
 def get_args(argv=None):
@@ -30,6 +33,21 @@ def get_args(argv=None):
     args = parser.parse_args(argv)
     args.cuda = torch.cuda.is_available() and not args.no_cuda
     return args
+
+
+def optimizer_kwargs(args, with_info=True):
+    """`--optimizer` / `--optimizer_info` as an algorithm's constructor arguments: `optimizer_class` and, for the classes
+    that take it (DQN, QRDQN), `optimizer_info`; elsewhere the keyword arguments are bound into the class."""
+    import functools
+    if args.optimizer not in OPTIMIZERS:
+        raise SystemExit("--optimizer must be one of %s, got %r" % (", ".join(sorted(OPTIMIZERS)), args.optimizer))
+    info = json.loads(args.optimizer_info)
+    if not isinstance(info, dict):
+        raise SystemExit("--optimizer_info must be a JSON object, got %r" % (args.optimizer_info,))
+    cls = OPTIMIZERS[args.optimizer]
+    if with_info:
+        return dict(optimizer_class=cls, optimizer_info=info)
+    return dict(optimizer_class=functools.partial(cls, **info) if info else cls)
 
 
 def get_params(file_name):
