@@ -1171,6 +1171,30 @@ int trl_layernorm_bwd_f32(const float* dy, const float* a, const float* stats, c
                           float* dgamma, float* dbeta, float* workspace, int M, int H, void* stream);
 int trl_act2_fwd_f32(const float* t1, float* t2, int64_t n, int act, void* stream);
 int trl_act2_bwd_f32(const float* d, const float* t1, const float* t2, float* dz, int64_t n, int act, void* stream);
+/* The same for G <= 12 problems of one shape in ONE launch (twin critics, targets, several inputs); the arrays hold G device
+ * pointers and are read on the host -- the kernels take them by value.  The grid covers the G * M rows, every problem with
+ * the same number of workgroups, so a problem's bits do not depend on its neighbours.  A launch moves 16-byte pieces only
+ * when every problem's tensors allow it.
+ *   bwd_group   dgamma[g] == NULL: problem g wants dz only (it writes no slabs and the fold skips it).  The slabs of the other
+ *               problems (problem g's at workspace + g * slabs * 2 H, trl_layernorm_bwd_group_workspace(G, M, H) floats in all)
+ *               are added by ONE second launch, in the single-problem fold's order.
+ *   bwd_group_partials   the first of those two launches alone (want[g] != 0: problem g writes slabs; want NULL: all do).
+ *               Problem g's slabs are trl_layernorm_bwd_group_slabs(G, M, H) rows of [dgamma (H) | dbeta (H)]: where dgamma and
+ *               dbeta lie back to back they are an entry (n = 2 H, splits = slabs) of trl_fold_partials_multi_f32 or
+ *               trl_fold_clip_adam_polyak_f32, so an update with a deferred fold spends no launch on them. */
+int trl_layernorm_fwd_group_f32(int G, const float* const* a, const float* const* gamma, const float* const* beta, float* const* y,
+                                float* const* stats, int M, int H, void* stream);
+int trl_layernorm_bwd_group_slabs(int G, int M, int H);
+int trl_layernorm_bwd_group_workspace(int G, int M, int H);
+int trl_layernorm_bwd_group_partials_f32(int G, const float* const* dy, const float* const* a, const float* const* stats,
+                                         const float* const* gamma, int act, float* const* dz, const int* want, float* workspace,
+                                         int M, int H, void* stream);
+int trl_layernorm_bwd_group_f32(int G, const float* const* dy, const float* const* a, const float* const* stats,
+                                const float* const* gamma, int act, float* const* dz, float* const* dgamma, float* const* dbeta,
+                                float* workspace, int M, int H, void* stream);
+int trl_act2_fwd_group_f32(int G, const float* const* t1, float* const* t2, int64_t n, int act, void* stream);
+int trl_act2_bwd_group_f32(int G, const float* const* d, const float* const* t1, const float* const* t2, float* const* dz,
+                           int64_t n, int act, void* stream);
 
 /* --- K18: running observation normaliser (torchrl/env/base_wrapper.py:44-121) --------------
  * state = {mean[D], var[D], count} fp64 on the device (Normalizer._mean/_var/_count; a fresh

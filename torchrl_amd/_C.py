@@ -398,6 +398,15 @@ SIGNATURES = {
     "trl_layernorm_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "trl_act2_fwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "trl_act2_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
+    "trl_layernorm_fwd_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
+    "trl_layernorm_bwd_group_slabs": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_layernorm_bwd_group_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "trl_layernorm_bwd_group_partials_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 +
+                                             [C.c_int, C.c_int, C.c_void_p]),
+    "trl_layernorm_bwd_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
+                                    [C.c_int, C.c_int, C.c_void_p]),
+    "trl_act2_fwd_group_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "trl_act2_bwd_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "trl_outer_gate_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "trl_mlp3_forward_ok": (C.c_int, [C.c_int] * 4),
     "trl_mlp3_forward_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
@@ -1533,6 +1542,128 @@ def linear_bwd_weight_partials_group(dys, y_gates, gate_act, xs, dws, dbs, plan)
         plan.entries.append((ws[base:base + splits * N * K], dws[i], N * K, splits))
         if want_db:
             plan.entries.append((ws[base + splits * N * K:base + per], dbs[i], N, splits))
+
+
+def _opt_ptrs(tensors, name):
+    """Host array of device pointers with per-entry NULLs."""
+    return (C.c_void_p * len(tensors))(*[dev_ptr(t, name=name, allow_none=True) for t in tensors])
+
+
+def layernorm_fwd_group(as_, gammas, betas, ys=None, statss=None):
+    """`layernorm_fwd` of G same-shaped problems in one launch (more than GROUP_MAX: ceil(G / GROUP_MAX) launches);
+    returns ([y_g], [stats_g])."""
+    G = len(as_)
+    if G > GROUP_MAX:
+        ys_o, st_o = [], []
+        for lo, hi in _group_chunks(G):
+            y, st = layernorm_fwd_group(as_[lo:hi], gammas[lo:hi], betas[lo:hi], _cut(ys, lo, hi), _cut(statss, lo, hi))
+            ys_o, st_o = ys_o + y, st_o + st
+        return ys_o, st_o
+    M, H = _ln_dims(as_[0], "layernorm_fwd_group")
+    dev = as_[0].device
+    if ys is None:
+        ys = [torch.empty((M, H), dtype=torch.float32, device=dev) for _ in range(G)]
+    if statss is None:
+        statss = [torch.empty((M, 2), dtype=torch.float32, device=dev) for _ in range(G)]
+    if any(tuple(t.shape) != (M, H) for t in list(as_) + list(ys)) or any(int(t.numel()) != 2 * M for t in statss) or \
+            any(int(t.numel()) != H for t in list(gammas) + list(betas)) or not len(gammas) == len(betas) == len(ys) == len(statss) == G:
+        raise TrlError("layernorm_fwd_group: G problems of one shape (M, H) = %s: a, y (M, H), stats (M, 2), gamma / beta (H)"
+                       % ((M, H),))
+    check(lib().trl_layernorm_fwd_group_f32(G, _ptrs(as_, "a"), _ptrs(gammas, "gamma"), _ptrs(betas, "beta"), _ptrs(ys, "y"),
+                                            _ptrs(statss, "stats"), M, H, stream_ptr(dev)), "trl_layernorm_fwd_group_f32")
+    return ys, statss
+
+
+def _ln_bwd_group_check(what, dys, as_, statss, gammas, dgammas, dbetas):
+    M, H = _ln_dims(as_[0], what)
+    G = len(as_)
+    if not len(dys) == len(statss) == len(gammas) == len(dgammas) == len(dbetas) == G or \
+            any(tuple(t.shape) != (M, H) for t in list(as_) + list(dys)) or any(int(t.numel()) != 2 * M for t in statss) or \
+            any(int(t.numel()) != H for t in gammas) or any((dg is None) != (db is None) for dg, db in zip(dgammas, dbetas)) or \
+            any(t is not None and int(t.numel()) != H for t in list(dgammas) + list(dbetas)):
+        raise TrlError("%s: G problems of one shape (M, H) = %s: dy, a (M, H), stats (M, 2), gamma (H), dgamma / dbeta (H) or "
+                       "both None" % (what, (M, H)))
+    if M <= 0:
+        raise TrlError("%s: no rows" % what)
+    return M, H
+
+
+def layernorm_bwd_group(dys, as_, statss, gammas, act, dgammas, dbetas, dzs=None, workspace=None, plan=None):
+    """`layernorm_bwd` of G same-shaped problems: one launch for every dz and the per-workgroup slabs, one for the sums of the
+    slabs of all problems (more than GROUP_MAX: ceil(G / GROUP_MAX) such pairs, using the workspace one after the other).
+    dgammas[g] / dbetas[g] None: problem g wants dz only.  plan (FoldPlan): the slabs stay in the plan's workspace and their
+    sums are entries of the plan's one fold launch -- dgamma / dbeta are final after `plan.run()` / `plan.run_fused()`; a
+    problem whose dbeta does not start where its dgamma ends cannot be such an entry and takes the fold launch here."""
+    G = len(dys)
+    if G > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(G):
+            out += layernorm_bwd_group(dys[lo:hi], as_[lo:hi], statss[lo:hi], gammas[lo:hi], act, dgammas[lo:hi], dbetas[lo:hi],
+                                       _cut(dzs, lo, hi), workspace, plan)
+        return out
+    M, H = _ln_bwd_group_check("layernorm_bwd_group", dys, as_, statss, gammas, dgammas, dbetas)
+    dev = dys[0].device
+    if dzs is None:
+        dzs = [torch.empty((M, H), dtype=torch.float32, device=dev) for _ in range(G)]
+    elif len(dzs) != G or any(tuple(t.shape) != (M, H) for t in dzs):
+        raise TrlError("layernorm_bwd_group: dzs must be %d tensors of shape %s" % (G, (M, H)))
+    want = [dg is not None for dg in dgammas]
+    packed = all(db.data_ptr() == dg.data_ptr() + 4 * H for dg, db in zip(dgammas, dbetas) if dg is not None)
+    need = lib().trl_layernorm_bwd_group_workspace(G, M, H)
+    if need < 0:
+        raise TrlError("layernorm_bwd_group: unsupported sizes G=%d M=%d H=%d" % (G, M, H))
+    if plan is not None and packed and any(want):
+        slabs = lib().trl_layernorm_bwd_group_slabs(G, M, H)
+        ws = plan.take(need)
+        check(lib().trl_layernorm_bwd_group_partials_f32(
+            G, _ptrs(dys, "dy"), _ptrs(as_, "a"), _ptrs(statss, "stats"), _ptrs(gammas, "gamma"), int(act), _ptrs(dzs, "dz"),
+            (C.c_int * G)(*[int(w) for w in want]), dev_ptr(ws, name="workspace"), M, H, stream_ptr(dev)),
+            "trl_layernorm_bwd_group_partials_f32")
+        for g in range(G):
+            if want[g]:                                                  # [dgamma | dbeta] as one fold of 2 H values
+                plan.entries.append((ws[g * slabs * 2 * H:(g + 1) * slabs * 2 * H], dgammas[g], 2 * H, slabs))
+        return dzs
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.float32, device=dev)
+    check(lib().trl_layernorm_bwd_group_f32(
+        G, _ptrs(dys, "dy"), _ptrs(as_, "a"), _ptrs(statss, "stats"), _ptrs(gammas, "gamma"), int(act), _ptrs(dzs, "dz"),
+        _opt_ptrs(dgammas, "dgamma"), _opt_ptrs(dbetas, "dbeta"), dev_ptr(workspace, name="workspace"), M, H, stream_ptr(dev)),
+        "trl_layernorm_bwd_group_f32")
+    return dzs
+
+
+def act2_fwd_group(t1s, act, outs=None):
+    """`act2_fwd` of G same-sized tensors in one launch (more than GROUP_MAX: ceil(G / GROUP_MAX) launches)."""
+    G = len(t1s)
+    if G > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(G):
+            out += act2_fwd_group(t1s[lo:hi], act, _cut(outs, lo, hi))
+        return out
+    if outs is None:
+        outs = [torch.empty_like(t) for t in t1s]
+    if len(outs) != G or any(t.shape != t1s[0].shape for t in list(t1s) + list(outs)):
+        raise TrlError("act2_fwd_group: G tensors of one shape")
+    check(lib().trl_act2_fwd_group_f32(G, _ptrs(t1s, "t1"), _ptrs(outs, "out"), int(t1s[0].numel()), int(act),
+                                       stream_ptr(t1s[0].device)), "trl_act2_fwd_group_f32")
+    return outs
+
+
+def act2_bwd_group(ds, t1s, t2s, act, outs=None):
+    """`act2_bwd` of G same-sized problems in one launch (more than GROUP_MAX: ceil(G / GROUP_MAX) launches)."""
+    G = len(ds)
+    if G > GROUP_MAX:
+        out = []
+        for lo, hi in _group_chunks(G):
+            out += act2_bwd_group(ds[lo:hi], t1s[lo:hi], t2s[lo:hi], act, _cut(outs, lo, hi))
+        return out
+    if outs is None:
+        outs = [torch.empty_like(d) for d in ds]
+    if not len(t1s) == len(t2s) == len(outs) == G or any(t.shape != ds[0].shape for t in list(ds) + list(t1s) + list(t2s) + list(outs)):
+        raise TrlError("act2_bwd_group: d, t1, t2 and out are G tensors of one shape")
+    check(lib().trl_act2_bwd_group_f32(G, _ptrs(ds, "d"), _ptrs(t1s, "t1"), _ptrs(t2s, "t2"), _ptrs(outs, "out"),
+                                       int(ds[0].numel()), int(act), stream_ptr(ds[0].device)), "trl_act2_bwd_group_f32")
+    return outs
 
 
 def linear_bwd_input(dy, y_gate, gate_act, w):

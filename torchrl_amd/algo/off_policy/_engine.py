@@ -7,15 +7,15 @@ import os
 import numpy as np
 import torch
 
-from ... import _C, dist
+from ... import _C, dist, ops
 from ...networks import flatten_into
 from .. import _optim
 from .._graphs import GraphCache  # noqa: F401  (the engines and tests import it from here)
 
 
 class FlatHome:
-    """`plists` (one parameter list per network, W and b alternating) back to back in one buffer `flat`, the parameters
-    views of it; `grads`, `m`, `v` beside it, with `views` the per-parameter gradient views and every
+    """`plists` (one parameter list per network: per layer W, b and, behind a LayerNorm layer, gamma, beta --
+    `ops.plan_params`) back to back in one buffer `flat`, the parameters views of it; `grads`, `m`, `v` beside it, with `views` the per-parameter gradient views and every
     `optimizer.state[p]` bound to its slices of the moments.  `targets`: the target networks' parameters, homed in `tflat`
     (allocated right behind `flat`, where it has always been).  `keep=(m, v)`: moments of an earlier home, reused when
     the size still matches."""
@@ -45,6 +45,61 @@ class FlatHome:
         """The gradient views as (gW, gb) pairs: one list per parameter list."""
         firsts = np.concatenate([[0], np.cumsum(self._counts)])
         return [[(self.views[i], self.views[i + 1]) for i in range(f, f + n, 2)] for f, n in zip(firsts, self._counts)]
+
+    def layer_views(self, layers_list):
+        """`pairs()` for layer lists that may carry LayerNorms (`ops.net_layers`): per network one tuple per layer,
+        (gW, gb) or (gW, gb, ggamma, gbeta), cut from the views in `ops.plan_params` order."""
+        firsts, out = np.concatenate([[0], np.cumsum(self._counts)]), []
+        for f, n, layers in zip(firsts, self._counts, layers_list):
+            i, views = int(f), []
+            for l in layers:
+                k = len(ops.plan_params([l]))
+                views.append(tuple(self.views[i:i + k]))
+                i += k
+            if i != f + n:
+                raise _C.TrlError("FlatHome.layer_views: the layer lists do not match the homed parameter lists")
+            out.append(views)
+        return out
+
+
+def post_kinds(layers):
+    """What follows each layer's activation: None, "ln" or "act" (`ops.net_plan`)."""
+    return [None if len(l) < 3 or l[2] is None else l[2][0] for l in layers]
+
+
+def net_home(named_nets, named_targets, optimizers, same=(), keep=None):
+    """The layer lists (`ops.net_layers`: plain (W, b) lists, or plans with post-ops for `add_ln` nets), the one activation
+    code and the `FlatHome` of an engine's trained networks and targets -- parameters per layer in the order W, b, gamma,
+    beta for both, so the Polyak step and the hard copy cover the norms.  named_nets / named_targets: [(name, net)], the
+    targets tracking the LAST len(named_targets) trained networks.  `add_ln` nets need TRL_OFFPOLICY_LN=1
+    (`ops.offpolicy_layers`).  `same`: groups of names that run in one grouped launch
+    and must agree on `add_ln` (twin critics); a network and its target always must."""
+    got = [ops.offpolicy_layers(n) for _, n in named_nets]
+    tgot = [ops.offpolicy_layers(n) for _, n in named_targets]
+    names = [n for n, _ in named_nets]
+    if any(a != got[0][1] for _, a in got + tgot):
+        raise _C.TrlError("%s must use the same activation" % ", ".join(names))
+    layers, tlayers = [ls for ls, _ in got], [ls for ls, _ in tgot]
+    kinds = dict(zip(names, (post_kinds(ls) for ls in layers)))
+    for group in same:
+        for other in group[1:]:
+            if kinds[other] != kinds[group[0]]:
+                raise _C.TrlError("%s and %s run as one grouped launch per layer and must agree on add_ln (LayerNorm on both or "
+                                  "on neither, over the same layers)" % (group[0], other))
+    off = len(named_nets) - len(named_targets)
+    for (tname, _), tl, (name, _), sl in zip(named_targets, tlayers, named_nets[off:], layers[off:]):
+        if post_kinds(tl) != post_kinds(sl) or [tuple(l[0].shape) for l in tl] != [tuple(l[0].shape) for l in sl]:
+            raise _C.TrlError("%s and its target %s differ in structure (add_ln / layer shapes)" % (name, tname))
+    home = FlatHome([ops.plan_params(ls) for ls in layers], optimizers, [p for ls in tlayers for p in ops.plan_params(ls)], keep)
+    return layers, tlayers, got[0][1], home
+
+
+def ln_slab_floats(layers, B, G=1):
+    """Floats of gradient slabs the LayerNorms of one network leave in a fold plan's workspace per backward pass of B rows
+    that runs as one of G problems."""
+    lib = _C.lib()
+    return sum(max(0, lib.trl_layernorm_bwd_group_workspace(G, B, int(l[0].shape[0]))) for l, k in zip(layers, post_kinds(layers))
+               if k == "ln")
 
 
 def load_static(st, batch, keys):

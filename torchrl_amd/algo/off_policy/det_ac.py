@@ -22,7 +22,7 @@ import torch.optim as optim
 from ... import _C, dist, ops
 from .. import _optim
 from ._deferred import StatRing
-from ._engine import FlatHome, GraphCache, load_static
+from ._engine import GraphCache, ln_slab_floats, load_static, net_home
 from .off_rl_algo import OffRLAlgo
 
 
@@ -134,17 +134,15 @@ class _FusedDetAC:
         self.dev = next(nets[0].parameters()).device
         if self.dev.type != "cuda":
             raise _C.TrlError("networks live on %s: the HIP path needs a GPU (no CPU path exists)" % self.dev)
-        self.act = ops.act_code(nets[0])
-        if any(ops.act_code(n) != self.act for n in nets[1:]):
-            raise _C.TrlError("policy and critics must use the same activation")
         self.pf_last = _C.ACT_TANH if getattr(nets[0], "tanh_action", False) else _C.ACT_NONE
         self.sigma_explore = float(getattr(nets[0], "norm_std_explore", 0.0))
-        self.layers = [ops.linear_layers(n) for n in nets]
-        self.tlayers = [ops.linear_layers(n) for n in targets]
-        plists = [[t for wb in ls for t in wb] for ls in self.layers]
-        home = FlatHome(plists, optimizers, [t for ls in self.tlayers for wb in ls for t in wb])
+        # the policy and the critic(s) may differ in `add_ln`; twin critics, and a network and its target, may not
+        names = ["pf", "qf"] if len(nets) == 2 else ["pf", "qf1", "qf2"]
+        self.layers, self.tlayers, self.act, home = net_home(
+            list(zip(names, nets)), list(zip(["target_" + n for n in names], targets)), optimizers,
+            same=(tuple(names[1:]),) if len(nets) == 3 else ())
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
-        self.sizes, self.offsets, self.gviews = home.sizes, home.offsets, home.pairs()
+        self.sizes, self.offsets, self.gviews = home.sizes, home.offsets, home.layer_views(self.layers)
         self.optimizers, self.c = optimizers, home.c                       # (c: grad_avg of a centered RMSprop, else None)
         self._state_names = [_optim.state_names(s) for s in home.specs]
         self.steps = [0] * len(nets)                                       # per-network Adam step counts (TD3's policy lags)
@@ -163,8 +161,10 @@ class _FusedDetAC:
 
     # ---- helpers ----
     def _ws(self, B):
-        need = 2 * max(_C.lib().trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0]))
-                       for ls in self.layers for w, _ in ls)               # x2: the twin critics' grouped weight gradient
+        need = 2 * max(_C.lib().trl_linear_bwd_weight_workspace(B, int(l[0].shape[1]), int(l[0].shape[0]))
+                       for ls in self.layers for l in ls)                  # x2: the twin critics' grouped weight gradient
+        need = max(need, max(ln_slab_floats(ls, B, G=2) for ls in self.layers))   # (a LayerNorm's slabs: used and folded before
+                                                                           # the layer's weight gradient takes the workspace)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, device=self.dev)
         return self.workspace

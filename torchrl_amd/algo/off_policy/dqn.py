@@ -16,7 +16,7 @@ import torch.optim as optim
 from ... import _C, dist, ops
 from .. import _optim
 from ._deferred import IndexSlab, StatRing
-from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static
+from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static, net_home
 from .off_rl_algo import OffRLAlgo
 
 
@@ -68,16 +68,16 @@ class _FusedDQN(_FusedOffPolicy):
         from ...networks.base import MLPBase
         self.is_mlp = isinstance(algo.qf.base, MLPBase)                 # state-vector Q net (examples/dqn_state_vec.py)
         if self.is_mlp:
-            self.layers, self.tlayers = ops.linear_layers(algo.qf), ops.linear_layers(algo.target_qf)
-            self.act = ops.act_code(algo.qf)
-            plist = [t for wb in self.layers for t in wb]
-            tlist = [t for wb in self.tlayers for t in wb]
+            # an `add_ln` Q net: its plan with the LayerNorms (ops.net_layers), gamma / beta homed behind their layer's W, b
+            (self.layers,), (self.tlayers,), self.act, home = net_home([("qf", algo.qf)], [("target_qf", algo.target_qf)],
+                                                                       [algo.qf_optimizer])
+            self.gviews = home.layer_views([self.layers])[0]
         else:
             plist, tlist = ops.cnn_param_list(algo.qf), ops.cnn_param_list(algo.target_qf)
-        home = FlatHome([plist], [algo.qf_optimizer], tlist)
+            home = FlatHome([plist], [algo.qf_optimizer], tlist)
+            self.gviews = home.pairs()[0]
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v
         self.opt_spec, self.c = home.specs[0], home.c                     # (the whole of `optimizer_info`, as torch read it)
-        self.gviews = home.pairs()[0]
         self.A = int(algo.env.action_space.n)
         self._init_run_state()
 
@@ -161,7 +161,7 @@ class _FusedDQN(_FusedOffPolicy):
         else:
             dq = _C.quantile_huber(q, acts, qn, rew, term, algo.discount, A, Q, self.sums, ring=ring)
         if self.is_mlp:
-            need = max(_C.lib().trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0])) for w, _ in self.layers)
+            need = max(_C.lib().trl_linear_bwd_weight_workspace(B, int(l[0].shape[1]), int(l[0].shape[0])) for l in self.layers)
         else:
             need = ops.cnn_backward_workspace(tape)                          # every conv layer its own region (one fold launch)
             need = max(need, max(_C.lib().trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0]))

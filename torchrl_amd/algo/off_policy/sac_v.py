@@ -15,7 +15,10 @@ d/d(action) is propagated here.  `assert v_target == v_pred` of the reference (s
 for every batch of more than one row) is taken as the shape check it evidently stands for: both are (B, 1) here by
 construction.
 
-Not built: reparameterization=False, optimisers other than Adam, LayerNorm networks, several ranks.
+Under TRL_OFFPOLICY_LN=1 `add_ln=True` networks run on the grouped LayerNorm launches (ops.mlp_forward_group / mlp_backward_group): the policy,
+the critics and V may each carry norms or not; twin critics must agree, and V's target is V's copy.
+
+Not built: reparameterization=False, optimisers other than Adam, several ranks.
 """
 import copy
 
@@ -67,7 +70,7 @@ class _ValueSAC(_SoftSurface, OffRLAlgo):
             raise _C.TrlError("%s runs on one rank: the exchange of gradients and statistics between several ranks is not "
                               "built for the value-network soft actor-critics (TwinSACQ has it)" % name)
         for net in self._critics() + [self.pf, self.vf]:
-            ops.act_code(net)                                            # Tanh / ReLU MLPs without LayerNorm, or TrlError
+            ops.offpolicy_layers(net)                   # Tanh / ReLU MLPs (with LayerNorm: under TRL_OFFPOLICY_LN=1), or TrlError
 
     def _critics(self):
         return [getattr(self, name) for name in self._critic_names]
@@ -115,6 +118,10 @@ class _FusedSACV(_FusedSAC):
         return ((algo.pf, *algo._critics(), algo.vf),
                 (algo.pf_optimizer, *[getattr(algo, n + "_optimizer") for n in names], algo.vf_optimizer),
                 (algo.target_vf,))
+
+    def _names(self, algo):
+        names = tuple(algo._critic_names)
+        return ("pf",) + names + ("vf",), ("target_vf",), ((names,) if len(names) > 1 else ())
 
     def _sequence(self, st, soft):
         """The fixed launch sequence of one update on the static inputs (eager, or under graph capture)."""

@@ -14,6 +14,9 @@ explicit chain rule instead of autograd:
   target update ........... trl_polyak_f32 on flat [qf1 | qf2] -> [tqf1 | tqf2]
 policy_loss.backward() in the reference also deposits gradients in qf1/qf2 that the following
 zero_grad() discards (its Q20); only d/d(action) is propagated here.
+`add_ln=True` networks (opt-in: TRL_OFFPOLICY_LN=1, refused otherwise): the layer lists are `ops.net_layers` plans, every grouped pass runs one grouped LayerNorm launch per
+normed layer, and the norms' gradient slabs are entries of the update's one fold (gamma / beta live behind their layer's W, b
+in the flat buffers, targets included).  The policy and the critics may differ in `add_ln`; the two critics may not.
 The two N(0,1) draws per update come from the CPU torch generator (reference parity) or from the
 device Philox stream (`noise_mode="device"`).
 """
@@ -25,7 +28,7 @@ import torch.optim as optim
 
 from ... import _C, dist, ops
 from ._deferred import IndexSlab, StatRing
-from ._engine import FlatHome, GraphCache, _EngineSurface, _FusedOffPolicy, load_static
+from ._engine import GraphCache, _EngineSurface, _FusedOffPolicy, ln_slab_floats, load_static, net_home, post_kinds
 from .off_rl_algo import OffRLAlgo
 
 
@@ -101,6 +104,10 @@ class _FusedSAC(_FusedOffPolicy):
         return ((algo.pf, algo.qf1, algo.qf2), (algo.pf_optimizer, algo.qf1_optimizer, algo.qf2_optimizer),
                 (algo.target_qf1, algo.target_qf2))
 
+    def _names(self, algo):
+        """(names of the trained networks, names of the targets, the groups that must agree on `add_ln`)."""
+        return ("pf", "qf1", "qf2"), ("target_qf1", "target_qf2"), (("qf1", "qf2"),)
+
     def __init__(self, algo):
         self.algo = algo
         nets, self.optimizers, targets = self._roles(algo)
@@ -108,15 +115,12 @@ class _FusedSAC(_FusedOffPolicy):
         if self.dev.type != "cuda":
             raise _C.TrlError("%s networks live on %s: the HIP path needs a GPU (no CPU path exists)"
                               % (type(algo).__name__, self.dev))
-        self.act = ops.act_code(algo.pf)
-        if any(ops.act_code(n) != self.act for n in nets[1:]):
-            raise _C.TrlError("the policy and the critics must use the same activation")
-        self.layers = [ops.linear_layers(n) for n in nets]
-        plists = [[t for wb in ls for t in wb] for ls in self.layers]
-        self.tlayers = [ops.linear_layers(n) for n in targets]
-        home = FlatHome(plists, self.optimizers, [t for ls in self.tlayers for wb in ls for t in wb])
+        # the policy and the critics may differ in `add_ln`; the critics among themselves, and a network and its target, not
+        names, tnames, same = self._names(algo)
+        self.layers, self.tlayers, self.act, home = net_home(list(zip(names, nets)), list(zip(tnames, targets)),
+                                                             self.optimizers, same=same)
         self.flat, self.tflat, self.grads, self.m, self.v = home.flat, home.tflat, home.grads, home.m, home.v   # [pf | qf1 | qf2]
-        self.sizes, self.gviews = home.sizes, home.pairs()
+        self.sizes, self.gviews = home.sizes, home.layer_views(self.layers)
         self.target_off = sum(self.sizes[:len(nets) - len(targets)])    # the targets' sources: flat[target_off:]
         self.step_count = 0
         self.alpha_state = torch.zeros(4, device=self.dev)               # log_alpha, exp_avg, exp_avg_sq, step
@@ -146,7 +150,9 @@ class _FusedSAC(_FusedOffPolicy):
         lib = _C.lib()
         need = sum(max(lib.trl_linear_bwd_weight_workspace(B, int(w.shape[1]), int(w.shape[0])),
                        lib.trl_linear_bwd_weight_multi_splits(B, int(w.shape[1]), int(w.shape[0])) * (w.numel() + int(w.shape[0])))
-                   for ls in self.layers for w, _ in ls)                  # every layer's partials live until the one fold
+                   for ls in self.layers for w in (l[0] for l in ls))     # every layer's partials live until the one fold
+        # ... and so do the LayerNorms' gradient slabs (a critic's pass is one of up to four problems of its launch)
+        need += sum(ln_slab_floats(ls, B, G=4) for ls in self.layers)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, device=self.dev)
         return self.workspace
@@ -229,7 +235,9 @@ class _FusedSAC(_FusedOffPolicy):
             if _C.sac_policy_grad_ok(dys, w0, A):
                 # ... and the policy's own head backward rides along: dZ2 = (d_head W3) * act'(H2) leaves the same launch
                 # already gated (a 2A-deep input-gradient GEMM launch less; the layer below reads one operand, not two)
-                hl = (pf_l[-1][0], tape_pf.outs[-2], self.act) if len(pf_l) >= 2 and len(tape_pf.outs) >= 2 else None
+                # (not behind a post-op: the layer below is then gated by its LayerNorm / second-Tanh backward launch)
+                hl = (pf_l[-1][0], tape_pf.outs[-2], self.act) \
+                    if len(pf_l) >= 2 and len(tape_pf.outs) >= 2 and post_kinds(pf_l)[-2] is None else None
                 d_head = _C.sac_policy_grad(head, eps, new_a, dys, ys, gate_act, w0, D, alpha, 1.0 / B,
                                             algo.policy_std_reg_weight, algo.policy_mean_reg_weight, tanh_action,
                                             head_layer=hl)

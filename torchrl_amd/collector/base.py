@@ -21,6 +21,14 @@ import torch
 from .. import _C
 
 
+def _policy_mlp(pf, ob, last_act=None):
+    """The policy's MLP on `ob`, no tape kept: the plain layer list, or the plan with its LayerNorm / second-Tanh launches
+    of an `add_ln` net (ops.net_layers) -- a captured collection sequence carries those launches like any other."""
+    from .. import ops
+    layers, act = ops.offpolicy_layers(pf)                                  # (`add_ln`: under TRL_OFFPOLICY_LN=1, else refused)
+    return ops.mlp_forward(layers, ob, act, last_act=last_act, keep=False)[0]
+
+
 class _CollectorBase:
     def __init__(self, env, eval_env, pf, replay_buffer, epoch_frames, train_render=False,
                  eval_episodes=1, eval_render=False, device='cpu', max_episode_frames=999):
@@ -262,7 +270,6 @@ class VecCollector(_CollectorBase):
 
     def _policy_action(self, env, deterministic, ob=None):
         """`ob`: what the policy sees -- env.cur_obs, or the normalised observation of a NormObs env."""
-        from .. import ops
         pf = self.pf
         ob = env.cur_obs if ob is None else ob
         if not self.continuous and hasattr(pf, "head_num"):
@@ -280,7 +287,7 @@ class VecCollector(_CollectorBase):
         if hasattr(pf, "norm_std_explore") or type(pf).__name__ == "DetContPolicy":
             # deterministic policies (continuous_policy.py:28-74): [tanh](mlp(obs)) (+ N(0, norm_std_explore))
             last = _C.ACT_TANH if pf.tanh_action else _C.ACT_NONE
-            act, _ = ops.mlp_forward(ops.linear_layers(pf), ob, ops.act_code(pf), last_act=last, keep=False)
+            act = _policy_mlp(pf, ob, last_act=last)
             sigma = float(getattr(pf, "norm_std_explore", 0.0))
             if deterministic or not sigma:
                 return act
@@ -289,7 +296,7 @@ class VecCollector(_CollectorBase):
             raise _C.TrlError("VecCollector's kernel path expects a GuassianContPolicy (mean | log_std head); "
                               "state-independent-std policies use VecOnPolicyCollector")
         n, a_dim = env.env_nums, env.act_dim
-        head, _ = ops.mlp_forward(ops.linear_layers(pf), ob, ops.act_code(pf), keep=False)
+        head = _policy_mlp(pf, ob)
         eps = torch.zeros(n, a_dim, device=env.device) if deterministic else self._explore_noise(env)
         act, _ = _C.rsample_fwd(head, eps, bool(pf.tanh_action))
         return act
@@ -360,10 +367,9 @@ class VecCollector(_CollectorBase):
                 and type(pf).__name__ != "DetContPolicy" and hasattr(env, "env_A"))
 
     def _step_one_launch(self, env, store, deterministic, max_frames):
-        from .. import ops
         buf, pf = self.replay_buffer, self.pf
         n, d, a_dim = env.env_nums, env.obs_dim, env.act_dim
-        head, _ = ops.mlp_forward(ops.linear_layers(pf), env.cur_obs, ops.act_code(pf), keep=False)
+        head = _policy_mlp(pf, env.cur_obs)
         noise = None
         if deterministic:
             if getattr(self, "_zero_eps", None) is None or self._zero_eps.shape[0] != n:
@@ -458,7 +464,7 @@ class VecCollector(_CollectorBase):
         trl_synth_collect_step_f32 with its device-side state, whose step counter / ring row / epoch start live on the device -- captured into
         a HIP graph (all `n_steps` of the call) on the second call and replayed afterwards: one host call per epoch.
         Returns False when the configuration is outside that path."""
-        from .. import dist, ops
+        from .. import dist
         env, buf, pf = self.env, self.replay_buffer, self.pf
         if not (self._one_launch_step(env, getattr(env, "_obs_normalizer", None)) and self.noise_mode == "device"
                 and dist.world_size() == 1 and os.environ.get("TRL_NO_GRAPH") != "1"
@@ -479,7 +485,7 @@ class VecCollector(_CollectorBase):
             + self._capture_key_extras(env, pf)
 
         def one_step():
-            head, _ = ops.mlp_forward(ops.linear_layers(pf), env.cur_obs, ops.act_code(pf), keep=False)
+            head = _policy_mlp(pf, env.cur_obs)
             _C.synth_collect_step_dyn(env, head, env.cur_step, env.ep_return, self.max_episode_frames, ring, self._dyn,
                                       self._mask, self._epoch_reward, self._ep_count, self._ep_log, bool(pf.tanh_action),
                                       self._noise_seed, 0)

@@ -8,9 +8,13 @@ gradient buffer, and optionally d(input).  act'(.) is applied inside the kernels
 stored layer OUTPUTS, so no pre-activation tensors are kept.
 
 `add_ln=True` nets carry post-ops behind their hidden layers (`net_plan`): a LayerNorm, or the second activation that
-replaces the trunk's last LayerNorm.  The ungrouped `mlp_forward` / `mlp_backward` run them on k_layernorm.hip; the
-grouped routes and the fused three-layer forward do not know them.
+replaces the trunk's last LayerNorm.  They run on k_layernorm.hip: one launch per post-op on the ungrouped `mlp_forward` /
+`mlp_backward`, one GROUPED launch per post-op (for all G networks of the call) on `mlp_forward_group` /
+`mlp_backward_group`; under a `_C.FoldPlan` the sums of the norms' gradient slabs are entries of the plan's one fold.  The
+fused three-layer forward does not know post-ops: layer lists that carry them never take it.
 """
+
+import os
 
 import torch
 import torch.nn as nn
@@ -85,6 +89,19 @@ def net_layers(net):
         return linear_layers(net), act_code(net)
     plan = net_plan(net)
     return (plan if has_post(plan) else [(w, b) for w, b, _ in plan]), ACT_OF[net.base.activation_func]
+
+
+def offpolicy_layernorm():
+    """TRL_OFFPOLICY_LN=1: the off-policy engines and their collector carry `add_ln=True` networks.  Unset, they refuse such
+    nets with `act_code`'s "without LayerNorm" message, as they always have (opt-in, like TRL_CAT_FUSED_UPDATE)."""
+    return os.environ.get("TRL_OFFPOLICY_LN") == "1"
+
+
+def offpolicy_layers(net):
+    """`net_layers(net)` with the switch on; with it off the plain layer list, or `act_code`'s refusal."""
+    if not offpolicy_layernorm():
+        return linear_layers(net), act_code(net)
+    return net_layers(net)
 
 
 def plan_params(layers):
@@ -186,11 +203,10 @@ def mlp_backward(tape, d_out, grads=None, need_input=False, workspace=None, plan
     to skip weight gradients).  Returns d(input) if need_input.  plan (_C.FoldPlan): the weight gradients are only
     final after `plan.run()` (one fold launch for the whole pass).  head_dx (with plan): the gradient at the last hidden
     layer, ALREADY gated by that layer's act' (somebody computed it along the way): the last layer's input-gradient launch
-    is skipped."""
-    if getattr(tape, "posts", None) is not None:
-        if plan is not None or head_dx is not None:
-            raise _C.TrlError("mlp_backward: LayerNorm nets run the ungrouped route (no fold plan, no head_dx)")
-        return _mlp_backward_post(tape, d_out, grads, need_input, workspace)
+    is skipped.  A tape with post-ops runs `_mlp_backward_post` without a plan and the grouped route with one (dgamma /
+    dbeta are then final after `plan.run()` too; head_dx is ignored where the last hidden layer has a post-op)."""
+    if getattr(tape, "posts", None) is not None and plan is None:
+        return _mlp_backward_post(tape, d_out, grads, need_input, workspace)    # (head_dx: needs a plan, as below)
     if plan is not None:
         out = mlp_backward_group([tape], [d_out], None if grads is None else [grads], need_input, plan=plan,
                                  head_dx=None if head_dx is None else [head_dx])
@@ -216,9 +232,16 @@ def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None, out=None):
     keep[g] = False: network g's hidden activations are not needed (no backward pass, e.g. target networks); networks
     of the shape D -> 256 -> 256 -> O then run through ONE fused launch that leaves their hidden layers on chip.
     out: the G tensors the LAST layer writes (the blocks of one (G, M, O) stack, Bootstrapped DQN's heads); the layers
-    then run one grouped launch each."""
+    then run one grouped launch each.
+    Layer lists with post-ops (`net_plan`; all G of one structure, or a TrlError names the layer): per layer the grouped
+    dense launch, then one grouped LayerNorm or second-Tanh launch; the tapes carry `posts` / `stats`; never the fused
+    launch."""
     G = len(layers_list)
     code_last = _C.ACT_NONE if last_act is None else last_act
+    if any(has_post(ls) for ls in layers_list):
+        return _mlp_forward_group_post(layers_list, xs, act, code_last, out)
+    if any(len(l) > 2 for ls in layers_list for l in ls):             # (plans without post-ops)
+        layers_list = [[(l[0], l[1]) for l in ls] for ls in layers_list]
     ls0 = layers_list[0]
     if out is None and len(ls0) == 3 and _C.mlp3_forward_ok(ls0[0][0].shape[1], ls0[0][0].shape[0], ls0[1][0].shape[0], ls0[2][0].shape[0]) and \
             all(b is not None for ls in layers_list for _, b in ls[:2]):
@@ -249,6 +272,56 @@ def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None, out=None):
     return hs, tapes
 
 
+def _post_of(layer):
+    return layer[2] if len(layer) > 2 else None
+
+
+def _group_posts(layers_list, what):
+    """The post-op kinds (None, "ln", "act") per layer of G layer lists of ONE structure."""
+    n = len(layers_list[0])
+    if any(len(ls) != n for ls in layers_list):
+        raise _C.TrlError("%s: the networks of a group have one depth (got %s layers)" % (what, [len(ls) for ls in layers_list]))
+    kinds = []
+    for k in range(n):
+        ks = [None if _post_of(ls[k]) is None else _post_of(ls[k])[0] for ls in layers_list]
+        if any(q != ks[0] for q in ks):
+            raise _C.TrlError("%s: the networks of a group carry the same post-op behind layer %d (got %s): LayerNorm on all "
+                              "of them or on none" % (what, k, ks))
+        kinds.append(ks[0])
+    if kinds[-1] is not None:
+        raise _C.TrlError("%s: the head (layer %d) carries no post-op" % (what, n - 1))
+    return kinds
+
+
+def _mlp_forward_group_post(layers_list, xs, act, code_last, out):
+    """`mlp_forward_group` of layer lists with post-ops: per layer the grouped dense launch, then ONE grouped LayerNorm launch
+    or ONE grouped second-Tanh launch for all G networks (`_mlp_forward_post`'s arithmetic per network)."""
+    kinds = _group_posts(layers_list, "mlp_forward_group")
+    tapes = []
+    for g in range(len(layers_list)):
+        t = Tape()
+        t.x, t.act, t.last_act, t.outs, t.posts, t.stats = xs[g], act, code_last, [], [], []
+        t.layers = [(l[0], l[1], _post_of(l)) for l in layers_list[g]]
+        tapes.append(t)
+    hs, n = list(xs), len(kinds)
+    for k in range(n):
+        last = k == n - 1
+        hs = _C.linear_fwd_group(hs, [ls[k][0] for ls in layers_list], [ls[k][1] for ls in layers_list],
+                                 code_last if last else act, ys=out if last else None)
+        for t, h in zip(tapes, hs):
+            t.outs.append(h)
+        sts = [None] * len(tapes)
+        if kinds[k] == "ln":
+            hs, sts = _C.layernorm_fwd_group(hs, [t.layers[k][2][1].detach() for t in tapes],
+                                             [t.layers[k][2][2].detach() for t in tapes])
+        elif kinds[k] == "act" and act == _C.ACT_TANH:
+            hs = _C.act2_fwd_group(hs, act)
+        for t, h, st in zip(tapes, hs, sts):
+            t.posts.append(h if kinds[k] is not None else None)
+            t.stats.append(st)
+    return hs, tapes
+
+
 def mlp_backward_group(tapes, d_outs, grads_list=None, need_input=False, workspace=None, plan=None, input_sink=None,
                        head_dx=None):
     """`mlp_backward` of G same-shaped tapes with grouped launches.  grads_list: [grads of tape g] or None; an entry may
@@ -258,11 +331,29 @@ def mlp_backward_group(tapes, d_outs, grads_list=None, need_input=False, workspa
     that layer's outputs, the outputs that gate them (or None) and the layer's weights, for the tapes that need d(input)
     -- a caller that only needs some columns of it (SAC's policy gradient: the action columns) computes them itself.
     head_dx: [gradient at the last hidden layer of tape g, already gated by its act'] -- replaces the last layer's
-    input-gradient launch."""
+    input-gradient launch.
+    Tapes with post-ops (all of one structure): a layer's grouped LayerNorm / second-Tanh backward launch runs first and
+    leaves the gradient at the layer's pre-activation, so its GEMMs run ungated; grads_list[g][k] is
+    (dW, db, dgamma, dbeta) for a normed layer, and a tape without weight gradients gets no dgamma / dbeta either.  The
+    two shortcuts that gate for the layer below through its activation outputs (head_dx, the one-output head) are not
+    taken when that layer has a post-op; input_sink then receives ys = None, gate_act = ACT_NONE for a first layer with
+    a post-op."""
     ds = list(d_outs)
     n = len(tapes[0].layers)
     want_in = list(need_input) if isinstance(need_input, (list, tuple)) else [bool(need_input)] * len(tapes)
     with_w = [] if grads_list is None else [g for g in range(len(tapes)) if grads_list[g] is not None]
+    posted = [getattr(t, "posts", None) is not None for t in tapes]
+    kinds = [None] * n
+    if any(posted):
+        if not all(posted):
+            raise _C.TrlError("mlp_backward_group: tapes with and without post-ops in one group")
+        kinds = _group_posts([t.layers for t in tapes], "mlp_backward_group")
+        seen = set()
+        for g in with_w:                                  # a view under two tapes would be written by two problems of a launch
+            for v in (v for views in grads_list[g] for v in views if v is not None):
+                if v.data_ptr() in seen:
+                    raise _C.TrlError("mlp_backward_group: one gradient view appears under two tapes of the call (tape %d)" % g)
+                seen.add(v.data_ptr())
     pregated = False                                  # ds already carries act' of layer k (see the one-output head below)
     for k in range(n - 1, -1, -1):
         last = k == n - 1
@@ -270,8 +361,23 @@ def mlp_backward_group(tapes, d_outs, grads_list=None, need_input=False, workspa
         gates = [None if (last and gate_act == _C.ACT_NONE) else t.outs[k] for t in tapes]
         if pregated:
             gates, gate_act, pregated = [None] * len(tapes), _C.ACT_NONE, False
+        if kinds[k] == "ln":
+            views = [grads_list[g][k] if g in with_w else (None,) * 4 for g in range(len(tapes))]
+            if any(len(v) < 4 for v in views):
+                raise _C.TrlError("mlp_backward_group: layer %d has a LayerNorm: its gradient views are (dW, db, dgamma, dbeta)" % k)
+            ds = _C.layernorm_bwd_group(ds, [t.outs[k] for t in tapes], [t.stats[k] for t in tapes],
+                                        [t.layers[k][2][1].detach() for t in tapes], gate_act, [v[2] for v in views],
+                                        [v[3] for v in views], workspace=workspace, plan=plan)
+            gates, gate_act = [None] * len(tapes), _C.ACT_NONE
+        elif kinds[k] == "act" and tapes[0].act == _C.ACT_TANH:
+            ds = _C.act2_bwd_group(ds, [t.outs[k] for t in tapes], [t.posts[k] for t in tapes], tapes[0].act)
+            gates, gate_act = [None] * len(tapes), _C.ACT_NONE
+        below_post = k > 0 and kinds[k - 1] is not None   # the layer below is not gated through its outs[k - 1] alone
+        if below_post:
+            head_dx = None
         if with_w:
-            inps = [(tapes[g].x if k == 0 else tapes[g].outs[k - 1]) for g in with_w]
+            inps = [(tapes[g].x if k == 0 else (tapes[g].outs[k - 1] if kinds[k - 1] is None else tapes[g].posts[k - 1]))
+                    for g in with_w]
             args = ([ds[g] for g in with_w], [gates[g] for g in with_w], gate_act, inps,
                     [grads_list[g][k][0] for g in with_w], [grads_list[g][k][1] for g in with_w])
             if plan is not None:
@@ -280,7 +386,7 @@ def mlp_backward_group(tapes, d_outs, grads_list=None, need_input=False, workspa
                 _C.linear_bwd_weight_group(*args, workspace=workspace)
         if k > 0 and last and head_dx is not None:
             ds, pregated = list(head_dx), True
-        elif k > 0 and last and gate_act == _C.ACT_NONE and int(tapes[0].layers[k][0].shape[0]) == 1 and \
+        elif k > 0 and last and not below_post and gate_act == _C.ACT_NONE and int(tapes[0].layers[k][0].shape[0]) == 1 and \
                 int(tapes[0].layers[k][0].shape[1]) % 4 == 0 and \
                 all(t.outs[k - 1].data_ptr() % 16 == 0 for t in tapes):
             # a head with ONE output: d(hidden) = dq w^T is rank 1 -- produced already gated for the layer below by one
