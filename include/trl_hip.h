@@ -1062,6 +1062,20 @@ int trl_boot_td_loss_f32(const float* q, const float* q_next, const int64_t* act
                          void* workspace, void* stream);
 /* The K heads' gradients at the trunk feature folded into one: src (K, n) -> dst (n), ascending k, fp32. */
 int trl_boot_fold_f32(const float* src, float* dst, int K, int64_t n, void* stream);
+/* The K heads' input gradient at a CONV feature, summed over the heads and gated for the top conv layer, as one launch:
+ *     out[b][p][c] = act'(y_top) * sum_k sum_j dZ_k[b][j] w[k][j][c P + p],   dZ_k = dz[k] * gate_act'(dz_gate[k])
+ * dz[k], dz_gate[k] (B, H1) (host arrays of K device pointers; dz_gate or any of its entries NULL: dz[k] is dZ_k as it
+ * stands), w[k] (H1, F = C P) the heads' first layers, y_top the top conv layer's (activation) output: (B, C, P), the
+ * feature's own order, when gate_like_in != 0, (B, P, C) otherwise; out (B, P, C), the order the conv backward reads --
+ * what trl_linear_bwd_input_group_f32 into a (K, B, F) stack, trl_boot_fold_f32 and trl_transpose_bpc_gate_f32 produce
+ * together, without the stack.  The reduction over K H1 is one chain per output element (fp32 MFMA, ascending k then j in
+ * panels of 32; no split over workgroups): the same inputs give the same bits, and rows whose dZ is zero in every head give
+ * exact zeros.  H1 is the heads' first width, or A for heads without a hidden layer (dz[k] = dq[k]).
+ * 1 <= K <= 64, B, H1, C, P >= 1, C P and K H1 below 2^30 (trl_boot_head_dx_supported); anything else: TRL_EINVAL. */
+int trl_boot_head_dx_supported(int K, int B, int H1, int C, int P);
+int trl_boot_head_dx_f32(int K, const float* const* dz, const float* const* dz_gate, int gate_act, const float* const* w,
+                         int B, int H1, int C, int P, const float* y_top, int top_act, int gate_like_in, float* out,
+                         void* stream);
 /* synthetic Atari-shaped env: (N, C, HW) uint8 frame stacks, Philox frames (see k_dqn.hip) */
 int trl_synth_frames_step_u8(uint8_t* frames, const int64_t* acts, int32_t* t_env, int64_t env_seed_base,
                              int horizon, int A, uint8_t* next_obs, float* rewards, float* dones,

@@ -338,6 +338,9 @@ SIGNATURES = {
     "trl_boot_td_loss_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trl_boot_fold_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "trl_boot_head_dx_supported": (C.c_int, [C.c_int] * 5),
+    "trl_boot_head_dx_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 +
+                             [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "trl_dqn_act_supported": (C.c_int, [C.c_int, C.c_int]),
     "trl_dqn_act_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -2329,6 +2332,36 @@ def boot_fold(src, out=None):
         raise TrlError("boot_fold: out holds one block of src")
     check(lib().trl_boot_fold_f32(dev_ptr(src, name="src"), dev_ptr(out, name="out"), K, int(out.numel()),
                                   stream_ptr(src.device)), "trl_boot_fold_f32")
+    return out
+
+
+def boot_head_dx_supported(K, B, H1, Cc, P):
+    return bool(lib().trl_boot_head_dx_supported(int(K), int(B), int(H1), int(Cc), int(P)))
+
+
+def boot_head_dx(dzs, gates, gate_act, ws, y_top, top_act, Cc, P, gate_like_in, out=None):
+    """The K heads' input gradient at a conv feature, summed over the heads, gated by act' of the top conv output `y_top`
+    and stored (B, P, Cc) as the conv backward reads it -- ONE launch for any K <= 64 (never cut at GROUP_MAX), no
+    (K, B, F) stack.  dzs[k] (B, H1): the gradient at head k's first layer, gated through gates[k] (its activation output)
+    with `gate_act` when `gates` is given; ws[k] (H1, Cc * P).  y_top: (B, Cc, P) when gate_like_in, else (B, P, Cc)."""
+    K = len(dzs)
+    B, H1 = (int(v) for v in dzs[0].shape)
+    F = int(Cc) * int(P)
+    if len(ws) != K or any(tuple(d.shape) != (B, H1) for d in dzs) or any(tuple(w.shape) != (H1, F) for w in ws) or \
+            int(y_top.numel()) != B * F:
+        raise TrlError("boot_head_dx: K gradients (B, H1), K weights (H1, C * P) and a top conv output of B * C * P values")
+    if gates is not None and (len(gates) != K or any(g is not None and tuple(g.shape) != (B, H1) for g in gates)):
+        raise TrlError("boot_head_dx: one gate (B, H1) or None per head")
+    if not boot_head_dx_supported(K, B, H1, Cc, P):
+        raise TrlError("boot_head_dx: unsupported shape K=%d B=%d H1=%d C=%d P=%d (1 <= K <= 64, sizes >= 1)" % (K, B, H1, Cc, P))
+    if out is None:
+        out = torch.empty((B, int(P), int(Cc)), dtype=torch.float32, device=dzs[0].device)
+    elif int(out.numel()) != B * F:
+        raise TrlError("boot_head_dx: out holds B * C * P values")
+    gp = None if gates is None else (C.c_void_p * K)(*[dev_ptr(g, name="gate", allow_none=True) for g in gates])
+    check(lib().trl_boot_head_dx_f32(K, _ptrs(dzs, "dz"), gp, int(gate_act), _ptrs(ws, "w"), B, H1, int(Cc), int(P),
+                                     dev_ptr(y_top, name="y_top"), int(top_act), int(bool(gate_like_in)),
+                                     dev_ptr(out, name="out"), stream_ptr(dzs[0].device)), "trl_boot_head_dx_f32")
     return out
 
 

@@ -39,7 +39,11 @@ class _CollectorBase:
             eval_env = bridge_host_env(copy.deepcopy(env.venv), device, like=env)
         if isinstance(eval_env, VecEnv):
             eval_env = bridge_host_env(eval_env, device, like=env)
-        if getattr(env, "kind", "vector") == "frames" and getattr(env, "is_host_env", False) and \
+        from .. import ops
+        # (TRL_BOOT_CONV=1: a Bootstrapped DQN policy over a conv trunk collects on them too, step by step)
+        boot_frames = ops.boot_conv() and not hasattr(self, "vf") and hasattr(pf, "head_num") and \
+            getattr(getattr(pf, "qf", None), "is_conv", False)
+        if getattr(env, "kind", "vector") == "frames" and getattr(env, "is_host_env", False) and not boot_frames and \
                 (hasattr(self, "vf") or not (hasattr(pf, "decay_frames") and hasattr(pf, "quantile_num"))):
             raise _C.TrlError("host envs with image observations (HostFrameBridge) are collected by VecCollector with an "
                               "epsilon-greedy DQN / QR-DQN policy over a conv Q network; %s with a %s is not built for them"
@@ -399,7 +403,9 @@ class VecCollector(_CollectorBase):
 
     def _step_frames(self, env, store, deterministic, max_frames):
         """Discrete-action step on the uint8 frame env: frames stay bytes in the replay rows; actions are
-        stored as (N, 1) so that DQN's gather works (the reference squeezes them, its Q16)."""
+        stored as (N, 1) so that DQN's gather works (the reference squeezes them, its Q16).  A Bootstrapped DQN policy
+        (TRL_BOOT_CONV=1) files its `masks` row and draws fresh heads after the reset exactly as `_step` does, keyed by
+        `global_step` and the env's `index_offset`; evaluation (store False) acts on the ensemble vote and draws nothing."""
         buf = self.replay_buffer
         n, shape = env.env_nums, env.frame_shape
         act = self._policy_action(env, deterministic)                       # (N,) int64
@@ -424,6 +430,10 @@ class VecCollector(_CollectorBase):
             nxt = None
             rew = torch.empty(n, 1, device=env.device)
             done = torch.empty(n, 1, device=env.device)
+        boot = not self.continuous and hasattr(self.pf, "head_num")         # Bootstrapped DQN: as on the vector path (`_step`)
+        if boot and store:
+            _C.boot_masks(buf._ensure_key("masks", (n, int(self.pf.head_num)))[row], self.pf.bernoulli_p, self.pf.seed,
+                          self.global_step, int(getattr(env, "index_offset", 0)))
         host = getattr(env, "is_host_env", False)                           # host pixel envs (HostFrameBridge)
         if host:
             # actions out; frames (pushed onto the device-resident stacks), rewards, dones and time limits in
@@ -443,6 +453,8 @@ class VecCollector(_CollectorBase):
             _C.synth_frames_reset(env.cur_obs, env.t_env, env.seed_base, self._mask)
         if dedup:
             buf.begin_episodes(env.cur_obs, self._mask)                     # fresh stacks of the envs just reset
+        if boot and store:
+            self.pf.sample_head(self._mask, counter=self.global_step, env_offset=int(getattr(env, "index_offset", 0)))
         if store:
             buf._advance()
         self.global_step += 1

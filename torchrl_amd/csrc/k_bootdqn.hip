@@ -257,3 +257,254 @@ extern "C" int trl_boot_fold_f32(const float* src, float* dst, int K, int64_t n,
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
+
+// ---------------------------------------------------------------- the heads' input gradient at a conv feature
+// Over a conv trunk the K heads' first layers all read one flattened feature (B, F = C P).  Its gradient, summed over the
+// heads and turned into the top conv layer's dZ, is ONE product with one long reduction:
+//     out[b][p][c] = act'(y_top) * sum_k sum_j dZ_k[b][j] W_k[j][c P + p],      dZ_k = dy_k * gate_act'(y_k)  (y_k nullable)
+// i.e. (B x K H1) . (K H1 x F) with the reduction index r = k H1 + j walking the heads back to back -- no (K, B, F) stack,
+// no fold, no transposing launch.  H1 is the heads' first width, or A itself for heads without a hidden layer (dZ_k is
+// then dq: one nonzero per row; nothing here depends on that).
+//
+// Exact fp32 on v_mfma_f32_32x32x2_f32, the tile code of k_gemm.hip in its plainest form: a workgroup of 4 waves owns a
+// 64 x 128 tile of (b, f) (a wave: 32 rows x 2 blocks of 32 columns, every A value read from LDS feeds two MFMAs), the
+// reduction walks panels of 32 through two LDS buffers with one barrier per panel: while the 32 MFMAs per wave of panel p
+// run, panel p + 1 goes from registers to the other buffer (gated there) and the loads of panel p + 2 are issued.
+// MFMA step (q, r) of lane half `hi` takes reduction index 8 q + 4 hi + r of the panel, as in k_gemm.hip.  No workgroup
+// shares an output element with another: every element is one chain in ascending panel order, so the same inputs give the
+// same bits.  All-zero rows of dZ give exact zeros (a sum of products with zero).  The epilogue applies act' of the top
+// conv output -- laid out like the feature (b, c, p) when `gate_like_in`, like `out` (b, p, c) otherwise -- and stores in
+// the (b, p, c) order the conv backward reads; those 4-byte stores are C floats apart, B F of them in all (the operand
+// traffic is K H1 F floats per row tile).  Any B, H1, C, P >= 1, 1 <= K <= 64; W rows are read with 16-byte loads when
+// F % 4 == 0 and every W_k is 16-byte aligned, else with predicated 4-byte loads.
+#define BH_TM 64
+#define BH_TN 128
+#define BH_KP 32
+#define BH_LDA (BH_KP + 4)
+#define BH_LDB (BH_TN + 8)
+struct BhPtrs { const float* dz[BT_MAX_K]; const float* gate[BT_MAX_K]; const float* w[BT_MAX_K]; };
+
+__device__ __forceinline__ float bh_dact(int act, float y) {
+  if (act == TRL_ACT_TANH) return 1.0f - y * y;
+  if (act == TRL_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
+  return 1.0f;
+}
+__device__ __forceinline__ f32x16 bh_mfma(float a, float b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// GATE_MODE: 0 no head's dz is gated, 1 every head's is (with gate_act != NONE), 2 some are (general loop only)
+template <int GATE_MODE>
+__global__ __launch_bounds__(256) void boot_head_dx_kernel(BhPtrs ptrs, int K, int B, int H1, int C, int P, int gate_act,
+                                                           const float* __restrict__ ytop, int top_act, int gate_like_in,
+                                                           int vec_ok, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float As[2 * BH_TM * BH_LDA];
+  __shared__ __attribute__((aligned(16))) float Bs[2 * BH_KP * BH_LDB];
+  __shared__ const float* tab[3 * BT_MAX_K];                           // dz | gate | w of head k (one dynamic read of the arguments)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int F = C * P, R = K * H1;
+  const int row_tiles = (B + BH_TM - 1) / BH_TM;
+  // workgroups are dealt round-robin to the 8 XCDs: renumber so that the row tiles that share W's columns share an L2
+  int bid = blockIdx.x;
+  const int nb = gridDim.x;
+  if ((nb & 7) == 0) bid = (bid & 7) * (nb >> 3) + (bid >> 3);
+  const int ct = bid / row_tiles, rt = bid - ct * row_tiles;
+  const int m0 = rt * BH_TM, n0 = ct * BH_TN;
+  if (tid < 3 * BT_MAX_K) {
+    const int which = tid / BT_MAX_K, k = tid - which * BT_MAX_K;
+    const float* p = nullptr;
+    if (k < K) p = which == 0 ? ptrs.dz[k] : (which == 1 ? ptrs.gate[k] : ptrs.w[k]);
+    tab[tid] = p;
+  }
+  __syncthreads();
+
+  // Registers of one panel in flight: the raw loads only -- the gate is applied when they are written to LDS, a whole
+  // panel of MFMAs later, so nothing waits for memory between the issue of the loads and the MFMAs that cover them.
+  float ra[8], rg[8];
+  f32x4 rb[4];
+  bool gated = false;
+  const int a_k = tid & 31, a_m = tid >> 5;                            // A slot: reduction index a_k, rows a_m + 8 t
+  const int b_n = n0 + 4 * (tid & 31), b_k = tid >> 5;                 // B slot: columns b_n .. + 3, reduction rows b_k + 8 t
+  auto fetch = [&](int r0) {
+    {
+      const int r = r0 + a_k;
+      const bool rok = r < R;
+      const int kk = rok ? r / H1 : 0, j = rok ? r - kk * H1 : 0;
+      const float* dzp = tab[kk];
+      const float* gp = tab[BT_MAX_K + kk];
+      gated = rok && gp != nullptr && gate_act != TRL_ACT_NONE;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const int m = m0 + a_m + 8 * t;
+        const bool ok = rok && m < B;
+        const size_t idx = ok ? (size_t)m * H1 + j : 0;
+        ra[t] = ok ? dzp[idx] : 0.0f;
+        rg[t] = (ok && gated) ? gp[idx] : 1.0f;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int r = r0 + b_k + 8 * t;
+      const bool rok = r < R;
+      const int kk = rok ? r / H1 : 0, j = rok ? r - kk * H1 : 0;
+      const float* wp = tab[2 * BT_MAX_K + kk] + (size_t)j * F;
+      if (rok && vec_ok && b_n + 3 < F) {
+        rb[t] = *reinterpret_cast<const f32x4*>(wp + b_n);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool ok = rok && b_n + e < F;
+          rb[t][e] = ok ? wp[ok ? b_n + e : 0] : 0.0f;
+        }
+      }
+    }
+  };
+  auto stash = [&](int buf) {
+    float* A_ = As + buf * (BH_TM * BH_LDA);
+    float* B_ = Bs + buf * (BH_KP * BH_LDB);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) A_[(a_m + 8 * t) * BH_LDA + a_k] = gated ? ra[t] * bh_dact(gate_act, rg[t]) : ra[t];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(B_ + (b_k + 8 * t) * BH_LDB + 4 * (tid & 31)) = rb[t];
+  };
+
+  const int i = lane & 31, hi = lane >> 5, wm = wave & 1, wn = wave >> 1;
+  f32x16 acc[2];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { acc[0][e] = 0.0f; acc[1][e] = 0.0f; }
+  auto group = [&](int buf, int q) {                                   // the 8 MFMAs of 8-k group q of the panel in `buf`
+    const f32x4 av = *reinterpret_cast<const f32x4*>(As + buf * (BH_TM * BH_LDA) + (32 * wm + i) * BH_LDA + 8 * q + 4 * hi);
+    const float* bp = Bs + buf * (BH_KP * BH_LDB) + (8 * q + 4 * hi) * BH_LDB + 64 * wn + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      acc[0] = bh_mfma(av[r], bp[r * BH_LDB], acc[0]);
+      acc[1] = bh_mfma(av[r], bp[r * BH_LDB + 32], acc[1]);
+    }
+  };
+  // two panel buffers, one barrier per panel: while the MFMAs of panel p run from buffer p & 1, the registers that hold
+  // panel p + 1 (fetched one panel earlier) go to the other buffer and the loads of panel p + 2 are issued
+  const int np = (R + BH_KP - 1) / BH_KP;
+  // Interior tiles (all 64 rows and 128 columns in range, 16-byte loads legal, every head gated or none) walk their WHOLE
+  // panels in a loop of their own that holds nothing but unconditional loads, LDS traffic and MFMAs: with the predicated
+  // loads of the general loop in the same body the compiler waits for all outstanding loads right where they are issued
+  // (k_gemm.hip has the same split).  Same panels, same k order: the same bits on either route.
+  const bool whole = m0 + BH_TM <= B && n0 + BH_TN <= F && vec_ok != 0 && GATE_MODE != 2;
+  const int nw = whole ? R / BH_KP : 0;
+  if (nw > 0) {
+    auto fetch_whole = [&](int r0) {
+      {
+        const int r = r0 + a_k;
+        const int kk = r / H1, j = r - kk * H1;
+        const size_t at = (size_t)(m0 + a_m) * H1 + j;
+        const float* dzp = tab[kk] + at;
+        const float* gp = GATE_MODE == 1 ? tab[BT_MAX_K + kk] + at : nullptr;     // (mode 0: the entries are NULL)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          ra[t] = dzp[(size_t)(8 * t) * H1];
+          if (GATE_MODE == 1) rg[t] = gp[(size_t)(8 * t) * H1];
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int r = r0 + b_k + 8 * t;
+        const int kk = r / H1, j = r - kk * H1;
+        rb[t] = *reinterpret_cast<const f32x4*>(tab[2 * BT_MAX_K + kk] + (size_t)j * F + b_n);
+      }
+    };
+    auto stash_whole = [&](int buf) {
+      float* A_ = As + buf * (BH_TM * BH_LDA);
+      float* B_ = Bs + buf * (BH_KP * BH_LDB);
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        A_[(a_m + 8 * t) * BH_LDA + a_k] = GATE_MODE == 1 ? ra[t] * bh_dact(gate_act, rg[t]) : ra[t];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(B_ + (b_k + 8 * t) * BH_LDB + 4 * (tid & 31)) = rb[t];
+    };
+    fetch_whole(0);
+    stash_whole(0);
+    if (nw > 1) fetch_whole(BH_KP);
+    __syncthreads();
+    for (int p = 0; p < nw; ++p) {
+      const int cur = p & 1;
+      group(cur, 0); group(cur, 1);
+      if (p + 1 < nw) stash_whole(cur ^ 1);
+      if (p + 2 < nw) fetch_whole((p + 2) * BH_KP);
+      group(cur, 2); group(cur, 3);
+      __syncthreads();
+    }
+  }
+  if (nw < np) {                                                       // general loop: panels [nw, np), edge-capable loads
+    fetch(nw * BH_KP);
+    stash(nw & 1);
+    if (nw + 1 < np) fetch((nw + 1) * BH_KP);
+    __syncthreads();
+    for (int p = nw; p < np; ++p) {
+      const int cur = p & 1;
+      group(cur, 0); group(cur, 1);
+      if (p + 1 < np) stash(cur ^ 1);
+      if (p + 2 < np) fetch((p + 2) * BH_KP);
+      group(cur, 2); group(cur, 3);
+      __syncthreads();
+    }
+  }
+  // epilogue: lane (i, hi) owns column f of rows 4 hi + (e & 3) + 8 (e >> 2) of each of the wave's two blocks
+#pragma unroll
+  for (int bb = 0; bb < 2; ++bb) {
+    const int f = n0 + 64 * wn + 32 * bb + i;
+    if (f >= F) continue;
+    const int c = f / P, pp = f - c * P;
+    const size_t o_col = (size_t)pp * C + c;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int m = m0 + 32 * wm + 4 * hi + (e & 3) + 8 * (e >> 2);
+      if (m < B) {
+        const size_t o = (size_t)m * F + o_col;
+        const float y = ytop[gate_like_in ? (size_t)m * F + f : o];
+        out[o] = acc[bb][e] * bh_dact(top_act, y);
+      }
+    }
+  }
+}
+
+extern "C" int trl_boot_head_dx_supported(int K, int B, int H1, int C, int P) {
+  if (K < 1 || K > BT_MAX_K || B < 1 || H1 < 1 || C < 1 || P < 1) return 0;
+  if ((int64_t)C * P > 0x3FFFFFFF || (int64_t)K * H1 > 0x3FFFFFFF) return 0;
+  const int64_t tiles = (((int64_t)C * P + BH_TN - 1) / BH_TN) * (((int64_t)B + BH_TM - 1) / BH_TM);
+  return tiles <= 0x7FFFFFFF ? 1 : 0;
+}
+extern "C" int trl_boot_head_dx_f32(int K, const float* const* dz, const float* const* dz_gate, int gate_act,
+                                    const float* const* w, int B, int H1, int C, int P, const float* y_top, int top_act,
+                                    int gate_like_in, float* out, void* stream) {
+  TRL_REQUIRE(trl_boot_head_dx_supported(K, B, H1, C, P),
+              "boot_head_dx: 1 <= K <= 64 heads, B, H1, C, P >= 1, C P and K H1 below 2^30");
+  TRL_REQUIRE(dz && w && y_top && out, "null pointer");
+  const auto known = [](int a) { return a == TRL_ACT_TANH || a == TRL_ACT_RELU || a == TRL_ACT_NONE; };
+  TRL_REQUIRE(known(gate_act) && known(top_act), "unknown activation");
+  BhPtrs ptrs;
+  const int F = C * P;
+  int vec_ok = (F % 4 == 0);
+  for (int k = 0; k < BT_MAX_K; ++k) {
+    ptrs.dz[k] = k < K ? dz[k] : nullptr;
+    ptrs.gate[k] = (k < K && dz_gate) ? dz_gate[k] : nullptr;
+    ptrs.w[k] = k < K ? w[k] : nullptr;
+    if (k < K) {
+      TRL_REQUIRE(dz[k] && w[k], "boot_head_dx: null head operand");
+      if (reinterpret_cast<uintptr_t>(w[k]) & 15) vec_ok = 0;
+    }
+  }
+  int n_gated = 0;
+  for (int k = 0; k < K; ++k) n_gated += (ptrs.gate[k] != nullptr && gate_act != TRL_ACT_NONE);
+  const int grid = trl_ceil_div(F, BH_TN) * trl_ceil_div(B, BH_TM);
+  const int like_in = gate_like_in ? 1 : 0;
+  if (n_gated == 0)
+    hipLaunchKernelGGL(boot_head_dx_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ptrs, K, B, H1, C, P, gate_act,
+                       y_top, top_act, like_in, vec_ok, out);
+  else if (n_gated == K)
+    hipLaunchKernelGGL(boot_head_dx_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ptrs, K, B, H1, C, P, gate_act,
+                       y_top, top_act, like_in, vec_ok, out);
+  else
+    hipLaunchKernelGGL(boot_head_dx_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ptrs, K, B, H1, C, P, gate_act,
+                       y_top, top_act, like_in, vec_ok, out);
+  TRL_LAUNCH_CHECK();
+  return TRL_OK;
+}

@@ -204,15 +204,24 @@ class BootstrappedNet(nn.Module):
     head-major (len(head_idxs), rows, A) stack (`forward_stack`) whose blocks are the returned tensors.
 
     Limits (each a loud _C.TrlError): MLP trunks only (a CNNBase trunk, the reference's Atari config, is not built), no
-    LayerNorm (`add_ln=True`), 1 <= head_num <= 64 and 1 <= output_shape <= 64 (the sizes k_bootdqn.hip carries)."""
+    LayerNorm (`add_ln=True`), 1 <= head_num <= 64 and 1 <= output_shape <= 64 (the sizes k_bootdqn.hip carries).
+
+    TRL_BOOT_CONV=1 (`ops.boot_conv`, read in the constructor): `base_type=CNNBase | partial(CNNBase, ...)` constructs too
+    (`is_conv`).  `trunk_layers()` / `param_list()` then give the conv W, b in `ops.cnn_param_list` order before the heads,
+    `forward_stack` takes (rows, C, H, W) uint8 frame stacks -- the conv trunk once, up to the flattened feature, the heads
+    as grouped launches -- and the eager `forward` stays what it is for CPU use.  Refused by name there as well: `add_ln`,
+    padding / dilation / groups the conv kernels refuse, a trunk whose activation differs from the heads'."""
 
     def __init__(self, output_shape, base_type, head_num=10, append_hidden_shapes=[],
                  append_hidden_init_func=init.basic_init, net_last_init_func=init.uniform_init,
                  activation_func=nn.ReLU, add_ln=False, **kwargs):
         super().__init__()
         import functools
+        from .base import CNNBase
+        from .. import ops
         trunk_cls = base_type.func if isinstance(base_type, functools.partial) else base_type
-        if not (isinstance(trunk_cls, type) and issubclass(trunk_cls, MLPBase)):
+        self.is_conv = isinstance(trunk_cls, type) and issubclass(trunk_cls, CNNBase) and ops.boot_conv()
+        if not self.is_conv and not (isinstance(trunk_cls, type) and issubclass(trunk_cls, MLPBase)):
             raise _C.TrlError("BootstrappedNet over a %s trunk is not built: the Bootstrapped DQN path runs MLP trunks "
                               "(networks.MLPBase) only, conv trunks are outside it" % getattr(trunk_cls, "__name__", trunk_cls))
         if add_ln:
@@ -225,6 +234,14 @@ class BootstrappedNet(nn.Module):
         self.base = base_type(activation_func=activation_func, add_ln=add_ln, **kwargs)
         self.add_ln = add_ln
         self.activation_func = activation_func
+        if self.is_conv:
+            ops.conv_layers(self)                                        # (padding / dilation / groups the conv kernels refuse)
+            if self.base.activation_func is not activation_func or self.base.last_activation_func is not activation_func:
+                raise _C.TrlError("BootstrappedNet: the conv trunk's activation (%s, last %s) differs from the heads' (%s): "
+                                  "trunk and heads run one activation"
+                                  % (getattr(self.base.activation_func, "__name__", self.base.activation_func),
+                                     getattr(self.base.last_activation_func, "__name__", self.base.last_activation_func),
+                                     getattr(activation_func, "__name__", activation_func)))
         self.head_num = int(head_num)
         self.out_dim = int(output_shape)
         self.bootstrapped_heads = []
@@ -244,6 +261,10 @@ class BootstrappedNet(nn.Module):
             self.bootstrapped_heads.append(head)
 
     def trunk_layers(self):
+        """(W, b) per trunk layer: the Linear layers of an MLP trunk, the Conv2d layers (W 4-D, `ops.cnn_param_list`'s
+        order) of a conv trunk."""
+        if self.is_conv:
+            return [(m.weight, m.bias) for m in self.base.seq_convs if isinstance(m, nn.Conv2d)]
         return [(m.weight, m.bias) for m in self.base.seq_fcs if isinstance(m, nn.Linear)]
 
     def head_layers(self, idx):
@@ -263,11 +284,16 @@ class BootstrappedNet(nn.Module):
         idxs = list(range(self.head_num)) if head_idxs is None else [int(i) for i in head_idxs]
         if not idxs or any(not 0 <= i < self.head_num for i in idxs):
             raise _C.TrlError("BootstrappedNet: head indices must lie in [0, %d), got %s" % (self.head_num, idxs))
-        act = ops.act_code(self)
-        trunk = [(w.detach(), b.detach()) for w, b in self.trunk_layers()]
-        x2 = x.reshape(-1, int(trunk[0][0].shape[1])).float().contiguous()
-        feat, _ = ops.mlp_forward(trunk, x2, act, last_act=act, keep=False)
-        stack = torch.empty((len(idxs), int(x2.shape[0]), self.out_dim), dtype=torch.float32, device=x.device)
+        if self.is_conv:
+            # (rows, C, H, W) uint8 frame stacks: the conv trunk once, up to the flattened feature
+            act = ops.cnn_act_code(self)
+            feat, _ = ops.cnn_forward(self, x.reshape((-1,) + tuple(x.shape[-3:])), feature=True)
+        else:
+            act = ops.act_code(self)
+            trunk = [(w.detach(), b.detach()) for w, b in self.trunk_layers()]
+            x2 = x.reshape(-1, int(trunk[0][0].shape[1])).float().contiguous()
+            feat, _ = ops.mlp_forward(trunk, x2, act, last_act=act, keep=False)
+        stack = torch.empty((len(idxs), int(feat.shape[0]), self.out_dim), dtype=torch.float32, device=x.device)
         heads = [[(w.detach(), b.detach()) for w, b in self.head_layers(i)] for i in idxs]
         ops.mlp_forward_group(heads, [feat] * len(idxs), act, keep=[False] * len(idxs), out=list(stack.unbind(0)))
         return stack
@@ -275,7 +301,7 @@ class BootstrappedNet(nn.Module):
     def forward(self, x, head_idxs):
         needs_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if x.is_cuda and not needs_graph:
-            lead = tuple(x.shape[:-1])
+            lead = tuple(x.shape[:-3]) if self.is_conv else tuple(x.shape[:-1])
             return [q.reshape(lead + (self.out_dim,)) for q in self.forward_stack(x, head_idxs).unbind(0)]
         if x.is_cuda:
             _C.note_eager(type(self).__name__ + ".forward", "autograd is on")

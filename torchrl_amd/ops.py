@@ -97,6 +97,13 @@ def offpolicy_layernorm():
     return os.environ.get("TRL_OFFPOLICY_LN") == "1"
 
 
+def boot_conv():
+    """TRL_BOOT_CONV=1: Bootstrapped DQN carries conv trunks (`networks.BootstrappedNet` over a CNNBase), pixel envs in the
+    collectors and RMSprop / SGD steps.  Unset, the constructors, the engine and the collectors refuse all three with the
+    messages they have always had (opt-in, like TRL_OFFPOLICY_LN)."""
+    return os.environ.get("TRL_BOOT_CONV") == "1"
+
+
 def offpolicy_layers(net):
     """`net_layers(net)` with the switch on; with it off the plain layer list, or `act_code`'s refusal."""
     if not offpolicy_layernorm():
@@ -485,13 +492,17 @@ def _dx_jobs(layers):
     return jobs
 
 
-def cnn_forward(net, frames_u8, scale=1.0 / 255.0, shift=-0.5, dx_prep=False, head=True):
+def cnn_forward(net, frames_u8, scale=1.0 / 255.0, shift=-0.5, dx_prep=False, head=True, feature=False):
     """frames_u8: (B, C, H, W) uint8.  Returns (out (B, O), tape).  dx_prep: a backward pass will follow -- the weight
     re-orderings of its input-gradient kernels ride on the first layer's launch (tape.dx_preps).  head=False: the pass
-    stops at the last HIDDEN activations (the caller runs the linear head itself, e.g. `_C.dqn_act`)."""
-    fcs = fc_layers(net)
+    stops at the last HIDDEN activations (the caller runs the linear head itself, e.g. `_C.dqn_act`).  feature=True: the
+    pass stops at the flattened conv feature (B, C * P) in nn.Flatten's order (tape.fc is None; `net` needs no FC layers:
+    a BootstrappedNet's heads are the caller's)."""
+    fcs = [] if feature else fc_layers(net)
     run_fc = (lambda feat: mlp_forward(fcs, feat, act)) if head else (lambda feat: mlp_forward(fcs[:-1], feat, act, last_act=act))
-    if not head and len(fcs) < 2:
+    if feature:
+        run_fc = lambda feat: (feat.view(int(frames_u8.shape[0]), -1), None)
+    if not feature and not head and len(fcs) < 2:
         raise _C.TrlError("cnn_forward(head=False) needs a hidden FC layer in front of the head")
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
         raise _C.TrlError("cnn_forward expects (B, C, H, W) uint8 frame stacks")
@@ -547,28 +558,35 @@ def cnn_forward(net, frames_u8, scale=1.0 / 255.0, shift=-0.5, dx_prep=False, he
     return out, t
 
 
-def cnn_forward_pair(net_a, net_b, frames_a, frames_b, scale=1.0 / 255.0, shift=-0.5, head=True, dx_prep=False):
+def cnn_forward_pair(net_a, net_b, frames_a, frames_b, scale=1.0 / 255.0, shift=-0.5, head=True, dx_prep=False,
+                     feature=False):
     """`cnn_forward` of two same-architecture networks on two frame batches -- DQN's online net on obs and target net on
     next_obs -- with every layer after the first as ONE grouped launch (conv 2 / 3 as grouped implicit GEMMs, the FC head
     as grouped (split-K) layers).  Returns ((out_a, tape_a), (out_b, tape_b)); falls back to two separate passes for
     geometries outside the grouped paths.  Same kernels and arithmetic as `cnn_forward`.
     head=False: the pass stops at the last HIDDEN activations (the caller runs the linear head itself, `_C.dqn_head`);
     the tapes then end at that layer and `cnn_backward` takes the gradient w.r.t. those activations.  Returns None when
-    the grouped path does not apply (the caller then runs the full pass)."""
+    the grouped path does not apply (the caller then runs the full pass).
+    feature=True: both passes stop at the flattened conv features (`cnn_forward(feature=True)`; always a result: outside the
+    grouped path two separate passes)."""
     convs_a, convs_b = conv_layers(net_a), conv_layers(net_b)
+    fc_layers_ = (lambda net: []) if feature else fc_layers
     act = cnn_act_code(net_a)
     same = (len(convs_a) == len(convs_b) and cnn_act_code(net_b) == act and tuple(frames_a.shape) == tuple(frames_b.shape)
             and all(ma.weight.shape == mb.weight.shape and ma.kernel_size == mb.kernel_size and ma.stride == mb.stride
                     for ma, mb in zip(convs_a, convs_b))
-            and [tuple(w.shape) for w, _ in fc_layers(net_a)] == [tuple(w.shape) for w, _ in fc_layers(net_b)])
+            and [tuple(w.shape) for w, _ in fc_layers_(net_a)] == [tuple(w.shape) for w, _ in fc_layers_(net_b)])
     first = convs_a[0] if convs_a else None
     if not same or first is None or frames_a.dtype != torch.uint8 or \
             not _C.conv_u8_implicit_ok(frames_a, *first.kernel_size, *first.stride) or \
             any(int(m.in_channels) % 4 for m in convs_a[1:]):
+        if feature:
+            return (cnn_forward(net_a, frames_a, scale, shift, dx_prep=dx_prep, feature=True),
+                    cnn_forward(net_b, frames_b, scale, shift, feature=True))
         if not head:
             return None
         return cnn_forward(net_a, frames_a, scale, shift, dx_prep=dx_prep), cnn_forward(net_b, frames_b, scale, shift)
-    if not head and len(fc_layers(net_a)) < 2:
+    if not feature and not head and len(fc_layers(net_a)) < 2:
         return None
     tapes, xs, shadows = [], [], []
     m = convs_a[0]
@@ -627,6 +645,10 @@ def cnn_forward_pair(net_a, net_b, frames_a, frames_b, scale=1.0 / 255.0, shift=
         for t, x in zip(tapes, xs):
             t.feat_shape = (Ho * Wo, Cc)
             feats.append(_C.transpose_bpc(x, B, Ho * Wo, Cc).view(B, Cc * Ho * Wo))   # PyTorch's NCHW flatten order
+    if feature:
+        for t in tapes:
+            t.fc = None
+        return (feats[0].view(tapes[0].B, -1), tapes[0]), (feats[1].view(tapes[1].B, -1), tapes[1])
     if head:
         outs, fcs = mlp_forward_group([fc_layers(net_a), fc_layers(net_b)], feats, act)
     else:
@@ -672,6 +694,16 @@ def cnn_backward(net, tape, d_out, grads, workspace=None):
     top_y = tape.convs[-1][2]
     d = _C.transpose_bpc(d_feat.view(tape.B, Cc, P), tape.B, Cc, P, y_gate=top_y, gate_act=tape.act,
                          gate_like_in=tape.feat_chw).view(tape.B * P, Cc)   # back to (B, P, C)
+    cnn_backward_from_dz(tape, d, grads, workspace=workspace)
+
+
+def cnn_backward_from_dz(tape, d, grads, workspace=None):
+    """The conv half of `cnn_backward`, entered with the top conv layer's dZ: d (B * P, C), the gradient at the feature
+    ALREADY un-flattened to (b, p, c) order and gated by act' of the top conv output (what the gated transpose of
+    `cnn_backward` leaves; Bootstrapped DQN makes it with that transpose behind its fold by default, or directly with
+    `_C.boot_head_dx` when opted in).  grads: the conv layers' (dW, db)
+    views, in order."""
+    n_conv = len(tape.convs)
     gated = True                                                         # d is dZ of layer k (else dY)
     needs = _conv_ws_needs(tape)
     if workspace is None or workspace.numel() < sum(needs) or workspace.data_ptr() % 16:

@@ -148,6 +148,11 @@ class BootstrappedDQNDiscretePolicy:
             self.idx.fill_(int(idx))
 
     def _rows(self, x):
+        if getattr(self.qf, "is_conv", False):                       # frame batches (..., C, H, W): one row per stack
+            if x.dim() < 3:
+                raise _C.TrlError("BootstrappedDQNDiscretePolicy over a conv trunk takes (N, C, H, W) frame stacks, got a "
+                                  "tensor of shape %s" % (tuple(x.shape),))
+            return x.reshape((-1,) + tuple(x.shape[-3:]))
         if x.dim() == 3 and x.shape[0] == 1:                         # the collector's unsqueeze(0)
             x = x.squeeze(0)
         return x.reshape(-1, x.shape[-1])
