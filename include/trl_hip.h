@@ -733,6 +733,25 @@ int trl_mlp3_forward_group_f32(int G, const float* const* x, const float* const*
                                const float* const* w2, const float* const* b2, const float* const* w3,
                                const float* const* b3, float* const* h1, float* const* h2, float* const* y, int M,
                                int D, int O, int act, int last_act, void* stream);
+/* The same launch for `add_ln=True` networks: each hidden layer may carry a post-op behind its activation, applied to
+ * the layer's tile in LDS -- TRL_POST_LN: an affine LayerNorm over the 256 outputs (biased variance, eps 1e-5; the
+ * arithmetic of trl_layernorm_fwd_f32's 16-byte form), TRL_POST_ACT: the activation once more (Tanh; a second ReLU
+ * changes nothing).  gamma1 / beta1 (gamma2 / beta2): per-network tables of the first (second) hidden layer's norm,
+ * 4-byte aligned, required where that layer's kind is TRL_POST_LN.  Per hidden layer k a network that keeps its tape
+ * gets h<k> (M, 256), the activation output; p<k> (M, 256), the post-op's output (the next layer's input); st<k>
+ * (M, 2) = [mean, rstd] per row for a norm.  Each of these tables, and each entry, may be NULL: a network with no
+ * entries writes nothing but y.  Without post-ops the hidden activations and y are those of trl_mlp3_forward_group_f32. */
+#define TRL_POST_NONE 0
+#define TRL_POST_LN   1
+#define TRL_POST_ACT  2
+int trl_mlp3_forward_post_ok(int D, int H1, int H2, int O, int post1, int post2);
+int trl_mlp3_forward_post_group_f32(int G, const float* const* x, const float* const* w1, const float* const* b1,
+                                    const float* const* w2, const float* const* b2, const float* const* w3,
+                                    const float* const* b3, int post1, int post2, const float* const* gamma1,
+                                    const float* const* beta1, const float* const* gamma2, const float* const* beta2,
+                                    float* const* h1, float* const* p1, float* const* st1, float* const* h2,
+                                    float* const* p2, float* const* st2, float* const* y, int M, int D, int O, int act,
+                                    int last_act, void* stream);
 
 /* --- K12 / K13: twin-Q SAC update pieces (torchrl/algo/off_policy/twin_sac_q.py:84-220) ---- */
 /* torch.cat([obs, act], -1) of QNet.forward (torchrl/networks/nets.py:61-68) */

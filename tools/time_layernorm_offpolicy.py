@@ -2,7 +2,7 @@
 """Time the grouped LayerNorm launches against back-to-back single-problem launches, and one TwinSACQ update at the
 cfg-3 shape with and without `add_ln`, with device events (200 calls after 10 warm-up calls); one JSON line per figure.
 
-    python tools/time_layernorm_offpolicy.py [--groups 6x4096x256,4x4096x256] [--iters 200] [--no-update]
+    python tools/time_layernorm_offpolicy.py [--groups 6x4096x256,4x4096x256] [--iters 200] [--no-update] [--mlp3]
 
 Kernels.  G problems of (M, H): trl_layernorm_fwd_group_f32 / trl_layernorm_bwd_group_f32 (rows + one fold) against G
 calls of trl_layernorm_fwd_f32 / trl_layernorm_bwd_f32 (G x (rows + fold)) -- the single-problem entry points are the
@@ -12,7 +12,12 @@ reaches on an MI355X.
 
 Update.  TwinSACQ, B = 4096, D 17, A 6, 256 x 256 ReLU nets, device noise, soft target updates: `engine.enqueue` on a
 fixed batch -- after the second call a replayed graph -- with add_ln on policy and critics, and without it (the launch
-sequence of a tree without the feature)."""
+sequence of a tree without the feature).
+
+--mlp3.  The fused 256-wide forward with post-ops (TRL_MLP3_LN=1) against the per-layer post route, in one session: the
+6-network and the 2-network forward of that update alone (`ops.mlp_forward_group`, Python wrappers included on both
+sides), the collector's policy pass (`ops.mlp_forward(keep=False)`, N = 1024 rows), and the `add_ln` update with the
+switch unset and set, each with the number of entry-point calls one eager update makes."""
 import argparse
 import json
 import os
@@ -73,7 +78,46 @@ def kernels(G, M, H, iters, dev):
     print(json.dumps(res))
 
 
-def update(add_ln, iters, dev):
+def forwards(iters, dev):
+    """(ln, act) ReLU nets, the structure `hidden_shapes=[256, 256]` builds: the forward passes of the cfg-3 update alone."""
+    from torchrl_amd import ops
+    D, A, H = 17, 6, 256
+    r = lambda *s: torch.randn(*s, device=dev) * 0.1
+    net = lambda d, o: [(r(H, d), r(H), ("ln", 1 + r(H), r(H))), (r(H, H), r(H), ("act",)), (r(o, H), r(o), None)]
+    cases = (("critics_x6", [net(D + A, 1) for _ in range(6)], 4096, [True] * 4 + [False] * 2),
+             ("policy_x2", [net(D, 2 * A)] * 2, 4096, [True, False]), ("collector_policy", [net(D, 2 * A)], 1024, [False]))
+    for name, nets, M, keep in cases:
+        xs = [torch.randn(M, nets[0][0][0].shape[1], device=dev) for _ in nets]
+        res = {"forward": name, "G": len(nets), "M": M, "keep": keep, "iters": iters}
+        for switch in ("0", "1"):
+            os.environ["TRL_MLP3_LN"] = switch
+            if len(nets) == 1:
+                fn = lambda: ops.mlp_forward(nets[0], xs[0], _C.ACT_RELU, keep=False)
+            else:
+                fn = lambda: ops.mlp_forward_group(nets, xs, _C.ACT_RELU, keep=keep)
+            res["fused_us" if switch == "1" else "per_layer_us"] = round(timed(fn, iters), 2)
+        res["note"] = "device events around back-to-back calls: launch gaps, output allocation and the Python wrappers included"
+        print(json.dumps(res))
+
+
+def entry_calls(fn):
+    """The number of libtrl_hip entry-point calls `fn` makes (every one goes through `_C.check`)."""
+    n, check = [0], _C.check
+
+    def counting(*a, **k):
+        n[0] += 1
+        return check(*a, **k)
+    _C.check = counting
+    try:
+        fn()
+    finally:
+        _C.check = check
+    return n[0]
+
+
+def update(add_ln, iters, dev, mlp3=None):
+    if mlp3 is not None:
+        os.environ["TRL_MLP3_LN"] = "1" if mlp3 else "0"
     from torchrl_amd import networks, policies
     from torchrl_amd.algo import TwinSACQ
     from torchrl_amd.env.synth import SynthVecEnv
@@ -98,6 +142,13 @@ def update(add_ln, iters, dev):
                      replay_buffer=None, collector=Stub(), logger=Log(), discount=0.99, num_epochs=1, batch_size=B, device=dev,
                      save_dir=None, tau=0.005, use_soft_update=True, opt_times=64)
     eng = agent.engine()
+    calls = None
+    if mlp3 is not None:                                                    # one eager update, before anything is captured
+        os.environ["TRL_NO_GRAPH"] = "1"
+        batch = {"obs": torch.randn(B, D, device=dev), "next_obs": torch.randn(B, D, device=dev), "rewards": torch.randn(B, 1, device=dev),
+                 "acts": torch.rand(B, A, device=dev) * 2 - 1, "terminals": torch.zeros(B, 1, device=dev)}
+        calls = entry_calls(lambda: agent.update(batch))
+        os.environ.pop("TRL_NO_GRAPH")
     st = eng.static_batch(B)
     st["obs"].normal_(), st["next_obs"].normal_(), st["rewards"].normal_()
     st["acts"].uniform_(-1, 1)
@@ -112,7 +163,7 @@ def update(add_ln, iters, dev):
     us = timed(one, iters)
     infos = eng.resolve(handles) if handles else []
     print(json.dumps({"update": "TwinSACQ", "B": B, "D": D, "A": A, "H": H, "add_ln": bool(add_ln), "iters": iters,
-                      "us_per_update": round(us, 2), "graphs": len(eng._graphs),
+                      "us_per_update": round(us, 2), "graphs": len(eng._graphs), "mlp3_ln": mlp3, "entry_calls_eager": calls,
                       "finite": all(all(v == v for v in i.values()) for i in infos),
                       "note": "engine.enqueue on a fixed batch, one read-back of the statistics per 32 updates included"}))
 
@@ -122,8 +173,14 @@ def main():
     ap.add_argument("--groups", default="6x4096x256,4x4096x256")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--no-update", action="store_true")
+    ap.add_argument("--mlp3", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.mlp3:
+        forwards(args.iters, dev)
+        for mlp3 in (False, True, False, True):                             # interleaved: both routes see the same clocks
+            update(True, args.iters, dev, mlp3=mlp3)
+        return
     for spec in args.groups.split(","):
         G, M, H = (int(v) for v in spec.split("x"))
         kernels(G, M, H, args.iters, dev)

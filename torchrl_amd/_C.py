@@ -413,6 +413,9 @@ SIGNATURES = {
     "trl_outer_gate_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "trl_mlp3_forward_ok": (C.c_int, [C.c_int] * 4),
     "trl_mlp3_forward_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
+    "trl_mlp3_forward_post_ok": (C.c_int, [C.c_int] * 6),
+    "trl_mlp3_forward_post_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_void_p] * 11 + [C.c_int] * 5 +
+                                        [C.c_void_p]),
     "trl_linear_fwd_splitk_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "trl_conv_fwd_nhwc_group_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 12 + [C.c_void_p]),
     "trl_linear_fwd_splitk_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
@@ -1364,6 +1367,46 @@ def mlp3_forward_group(layers_list, xs, act, last_act, keep):
                                            opt_ptrs(h1s), opt_ptrs(h2s), _ptrs(ys, "y"), M, D, O, act, last_act,
                                            stream_ptr(dev)), "trl_mlp3_forward_group_f32")
     return list(zip(h1s, h2s, ys))
+
+
+POST_CODE = {None: 0, "ln": 1, "act": 2}     # TRL_POST_*: the post-op kinds of `ops.net_plan`
+
+
+def mlp3_forward_post_ok(D, H1, H2, O, post1, post2):
+    """post1 / post2: TRL_POST_* codes, or the kinds None / "ln" / "act" (anything else is an unknown kind: False)."""
+    codes = [POST_CODE.get(p, -1) if (p is None or isinstance(p, str)) else int(p) for p in (post1, post2)]
+    return bool(lib().trl_mlp3_forward_post_ok(int(D), int(H1), int(H2), int(O), codes[0], codes[1]))
+
+
+def mlp3_forward_post_group(layers_list, xs, act, last_act, keep, kinds):
+    """`mlp3_forward_group` for layer lists [(W, b, post)] * 3 with post-ops of the kinds (kind1, kind2) behind the hidden
+    layers, still ONE launch.  Returns per network (outs, posts, stats), the lists a `ops.Tape` carries: outs = [h1, h2, y]
+    (the activation outputs), posts[k] the post-op's output (outs[k] itself behind a second ReLU, None without a post-op),
+    stats[k] the (M, 2) [mean, rstd] of a norm; keep[g] False: network g leaves only y (every other entry None)."""
+    G = len(xs)
+    M, D = int(xs[0].shape[0]), int(xs[0].shape[1])
+    O = int(layers_list[0][2][0].shape[0])
+    dev = xs[0].device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    if any(int(ls[k][2][j].numel()) != 256 for k in range(2) if kinds[k] == "ln" for ls in layers_list for j in (1, 2)):
+        raise TrlError("mlp3_forward_post_group: gamma / beta of a norm hold 256 values")
+    own = [k is not None and not (k == "act" and act != ACT_TANH) for k in kinds]      # the post-op has an output of its own
+    hs = [[f(M, 256) if keep[g] else None for g in range(G)] for _ in range(2)]
+    ps = [[f(M, 256) if keep[g] and own[k] else None for g in range(G)] for k in range(2)]
+    sts = [[f(M, 2) if keep[g] and kinds[k] == "ln" else None for g in range(G)] for k in range(2)]
+    ys = [f(M, O) for _ in range(G)]
+    col = lambda k, j: _ptrs([ls[k][j] for ls in layers_list], "param", True)
+    norm = lambda k, j: _ptrs([ls[k][2][j].detach() for ls in layers_list], "gamma / beta") if kinds[k] == "ln" else None
+    check(lib().trl_mlp3_forward_post_group_f32(
+        G, _ptrs(xs, "x"), col(0, 0), col(0, 1), col(1, 0), col(1, 1), col(2, 0), col(2, 1), POST_CODE[kinds[0]],
+        POST_CODE[kinds[1]], norm(0, 1), norm(0, 2), norm(1, 1), norm(1, 2), _opt_ptrs(hs[0], "h1"), _opt_ptrs(ps[0], "p1"),
+        _opt_ptrs(sts[0], "st1"), _opt_ptrs(hs[1], "h2"), _opt_ptrs(ps[1], "p2"), _opt_ptrs(sts[1], "st2"), _ptrs(ys, "y"),
+        M, D, O, act, last_act, stream_ptr(dev)), "trl_mlp3_forward_post_group_f32")
+    res = []
+    for g in range(G):
+        posts = [(ps[k][g] if own[k] else hs[k][g]) if kinds[k] is not None else None for k in range(2)]
+        res.append(([hs[0][g], hs[1][g], ys[g]], posts + [None], [sts[0][g], sts[1][g], None]))
+    return res
 
 
 def linear_bwd_input_group(dys, y_gates, gate_act, ws, dxs=None):

@@ -13,6 +13,8 @@ NOISE_SRC = "trl_noise_ext.cpp"
 SOURCES = ["trl_host.cpp", "trl_mtjump.cpp", "k_gae.hip", "k_gather.hip", "k_ppo.hip", "k_optim.hip", "k_ppo_generic.hip", "k_categorical.hip", "k_gauss_sd.hip", "k_layernorm.hip", "k_vmpo.hip", "k_trpo.hip", "k_rollout.hip", "k_gemm.hip", "k_mlp3.hip", "k_conv1.hip", "k_conv_dx.hip", "k_sac.hip", "k_conv.hip", "k_dqn.hip", "k_bootdqn.hip", "k_norm.hip", "k_frames.hip", "k_comm.hip", "k_peaks.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
+# per-source flags.  k_mlp3.hip: no packed-fp32 VALU forms in its LayerNorm pass (its plain kernels emit none either way)
+SOURCE_FLAGS = {"k_mlp3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _stale():
@@ -90,7 +92,7 @@ def build(force=False, verbose=True, extra_flags=(), lib=None):
     procs = []
     for src in SOURCES:
         obj = os.path.join(LIB_DIR, os.path.splitext(src)[0] + (".exp.o" if lib else ".o"))
-        cmd = [hipcc] + FLAGS + (["-x", "hip"] if src.endswith(".cpp") else []) + \
+        cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(src, []) + (["-x", "hip"] if src.endswith(".cpp") else []) + \
               ["-c", os.path.join(CSRC, src), "-o", obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
         objs.append(obj)

@@ -29,24 +29,14 @@
 // second launch, or left to a fold the caller runs anyway (trl_layernorm_bwd_group_partials_f32).
 #include "trl_common.h"
 #include "trl_mlp.h"
+#include "trl_layernorm.h"
 
 #define LN_THREADS 256
 #define LN_WAVES (LN_THREADS / 64)
 #define LN_MAX_H 1024
 #define LN_MAX_WG_FWD 2048     // workgroups of the forward pass at most (eight waves per SIMD)
 #define LN_MAX_WG_BWD 1024     // workgroups = slabs of the backward pass at most
-#define LN_EPS 1e-5f
-
-template <int G> __device__ __forceinline__ float ln_group_sum(float v) {      // every lane of a sub-group gets its sum
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// column of register r of sub-group lane sl
-template <bool VEC, int G> __device__ __forceinline__ int ln_col(int sl, int r) {
-  return VEC ? 4 * (sl + G * (r >> 2)) + (r & 3) : sl + G * r;
-}
+// (LN_EPS, ln_group_sum, ln_col and ln_load_cols: trl_layernorm.h, shared with k_mlp3.hip)
 
 // a row into registers; columns past H (and every column of a row that does not exist) read as 0
 template <bool VEC, int G, int CH>
@@ -86,15 +76,6 @@ __device__ __forceinline__ void ln_store_row(float* row, int H, int sl, bool val
       const int c = sl + G * r;
       if (valid && c < H) row[c] = v[r];
     }
-  }
-}
-
-// a per-column vector (gamma, beta) into the registers of its columns, 4-byte loads
-template <bool VEC, int G, int CH> __device__ __forceinline__ void ln_load_cols(const float* p, int H, int sl, float (&v)[4 * CH]) {
-#pragma unroll
-  for (int r = 0; r < 4 * CH; ++r) {
-    const int c = ln_col<VEC, G>(sl, r);
-    v[r] = c < H ? p[c] : 0.0f;
   }
 }
 

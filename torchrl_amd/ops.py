@@ -11,7 +11,9 @@ stored layer OUTPUTS, so no pre-activation tensors are kept.
 replaces the trunk's last LayerNorm.  They run on k_layernorm.hip: one launch per post-op on the ungrouped `mlp_forward` /
 `mlp_backward`, one GROUPED launch per post-op (for all G networks of the call) on `mlp_forward_group` /
 `mlp_backward_group`; under a `_C.FoldPlan` the sums of the norms' gradient slabs are entries of the plan's one fold.  The
-fused three-layer forward does not know post-ops: layer lists that carry them never take it.
+fused three-layer forward carries post-ops only when opted in (TRL_MLP3_LN=1, `mlp3_layernorm`): D -> 256 -> 256 -> O layer
+lists then take ONE launch that applies the post-ops to the hidden tiles in LDS and leaves the same tapes; unset, layer
+lists with post-ops never take the fused launch.
 """
 
 import os
@@ -97,6 +99,13 @@ def offpolicy_layernorm():
     return os.environ.get("TRL_OFFPOLICY_LN") == "1"
 
 
+def mlp3_layernorm():
+    """TRL_MLP3_LN=1: D -> 256 -> 256 -> O layer lists with post-ops take the fused forward's post-op variant (one launch,
+    the normed hidden layers stay on chip).  Unset, they run one launch per layer and per post-op, as they always have
+    (opt-in, like TRL_OFFPOLICY_LN)."""
+    return os.environ.get("TRL_MLP3_LN") == "1"
+
+
 def boot_conv():
     """TRL_BOOT_CONV=1: Bootstrapped DQN carries conv trunks (`networks.BootstrappedNet` over a CNNBase), pixel envs in the
     collectors and RMSprop / SGD steps.  Unset, the constructors, the engine and the collectors refuse all three with the
@@ -132,6 +141,9 @@ def mlp_forward(layers, x, act, last_act=None, keep=True):
     the head output inside the last layer's epilogue (deterministic policies: tanh(mlp(x))).  keep=False: no backward pass
     will follow (acting): the fused three-layer launch then leaves its hidden activations on chip."""
     if has_post(layers):
+        if _mlp3_post_kinds([layers], None) is not None:
+            outs, tapes = mlp_forward_group([layers], [x], act, last_act=last_act, keep=[bool(keep)])   # one fused launch
+            return outs[0], tapes[0]
         return _mlp_forward_post(layers, x, act, last_act)
     if any(len(l) > 2 for l in layers):                               # (a plan without post-ops)
         layers = [(l[0], l[1]) for l in layers]
@@ -246,7 +258,17 @@ def mlp_forward_group(layers_list, xs, act, last_act=None, keep=None, out=None):
     G = len(layers_list)
     code_last = _C.ACT_NONE if last_act is None else last_act
     if any(has_post(ls) for ls in layers_list):
-        return _mlp_forward_group_post(layers_list, xs, act, code_last, out)
+        kinds = _mlp3_post_kinds(layers_list, out)
+        if kinds is None:
+            return _mlp_forward_group_post(layers_list, xs, act, code_last, out)
+        keep = [True] * G if keep is None else list(keep)
+        tapes = []
+        for g, (outs, posts, stats) in enumerate(_C.mlp3_forward_post_group(layers_list, xs, act, code_last, keep, kinds)):
+            t = Tape()
+            t.x, t.act, t.last_act, t.outs, t.posts, t.stats = xs[g], act, code_last, outs, posts, stats
+            t.layers = [(l[0], l[1], _post_of(l)) for l in layers_list[g]]
+            tapes.append(t)
+        return [t.outs[2] for t in tapes], tapes
     if any(len(l) > 2 for ls in layers_list for l in ls):             # (plans without post-ops)
         layers_list = [[(l[0], l[1]) for l in ls] for ls in layers_list]
     ls0 = layers_list[0]
@@ -298,6 +320,21 @@ def _group_posts(layers_list, what):
     if kinds[-1] is not None:
         raise _C.TrlError("%s: the head (layer %d) carries no post-op" % (what, n - 1))
     return kinds
+
+
+def _mlp3_post_kinds(layers_list, out):
+    """The post-op kinds (kind1, kind2) of layer lists that take the fused forward's post-op variant, else None: the
+    switch is set, three layers of a covered shape, one structure for all networks of a group of at most `_C.GROUP_MAX`,
+    hidden biases present, no `out=`."""
+    ls0 = layers_list[0]
+    if not mlp3_layernorm() or out is not None or len(layers_list) > _C.GROUP_MAX or any(len(ls) != 3 for ls in layers_list):
+        return None
+    kinds = [[None if _post_of(l) is None else _post_of(l)[0] for l in ls] for ls in layers_list]
+    if any(k != kinds[0] for k in kinds) or kinds[0][2] is not None or \
+            any(l[1] is None for ls in layers_list for l in ls[:2]) or \
+            not _C.mlp3_forward_post_ok(ls0[0][0].shape[1], ls0[0][0].shape[0], ls0[1][0].shape[0], ls0[2][0].shape[0], *kinds[0][:2]):
+        return None
+    return kinds[0][:2]
 
 
 def _mlp_forward_group_post(layers_list, xs, act, code_last, out):
