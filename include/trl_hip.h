@@ -226,6 +226,20 @@ int trl_rollout_cat_supported(int D, int H, int A, int act);
  * trl_rollout_sd_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32, 1 <= A <= 8, Tanh or ReLU. */
 int trl_rollout_synth_sd_f32(const trl_rollout_t* args, void* stream);
 int trl_rollout_sd_supported(int D, int H, int A, int act);
+/* The same rollout for `add_ln=True` networks (torchrl/networks/base.py, nets.py: Linear(D, 64), act, LayerNorm(64),
+ * Linear(64, 64), act, act, Linear(64, O)) with any of the three heads: head = 0 Gaussian with a logstd tail (args as for
+ * trl_rollout_synth_f32), 1 categorical (args as for trl_rollout_synth_cat_f32; noise_seed / env_offset key its draw and
+ * are ignored otherwise), 2 state-dependent std (args as for trl_rollout_synth_sd_f32).  pf_ln / vf_ln: which of the two
+ * networks carries the LayerNorm -- they are independent, and a network without one keeps its MLP2 block.  A normed
+ * network's block is ONE contiguous vector in module order,
+ *     W1 (64, D) | b1 | gamma1 (64) | beta1 (64) | W2 (64, 64) | b2 | W3 (O, 64) | b3 (| logstd (A), Gaussian policy),
+ * read in place.  The norm is two-pass (mean, then squared deviations about it), eps = 1e-5, biased variance; layer 2
+ * applies the activation twice, as the reference's construction leaves it.  vf_params NULL: no critic, as above.
+ * args->norm_state / noise_flag / stage_n must be unset (TRL_EINVAL); shapes: trl_rollout_ln_supported (TRL_EUNSUPPORTED
+ * otherwise) -- the head's own range, H == 64, 2 <= D <= 32, Tanh or ReLU. */
+int trl_rollout_synth_ln_f32(const trl_rollout_t* args, int head, int pf_ln, int vf_ln, int64_t noise_seed,
+                             int64_t env_offset, void* stream);
+int trl_rollout_ln_supported(int head, int D, int H, int A, int act);
 /* Page-locked host block -> device buffer by a KERNEL (the device reads host memory in place), meant for a stream of
  * its own next to the one that computes: n floats (n % 4 == 0, 16-byte aligned pointers); when every workgroup's part is
  * in device memory, state[0] = stamp is stored with device scope -- what a consumer launched on another stream polls

@@ -188,6 +188,8 @@ SIGNATURES = {
     "trl_rollout_cat_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_rollout_synth_sd_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_void_p]),
     "trl_rollout_sd_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_rollout_synth_ln_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_rollout_ln_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_stage_h2d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trl_ppo_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_mlp2_forward_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -693,6 +695,14 @@ def rollout_sd(args, device):
     """The persistent rollout with a state-dependent-std Gaussian head [mean | log_std]: args.A is the number of action
     dimensions (half the head's width), args.acts rows are (N, A)."""
     check(lib().trl_rollout_synth_sd_f32(C.byref(args), stream_ptr(device)), "trl_rollout_synth_sd_f32")
+
+
+def rollout_ln(args, head, pf_ln, vf_ln, noise_seed, env_offset, device):
+    """The persistent rollout for `add_ln` networks: head 0 / 1 / 2 = shared-std Gaussian / categorical / state-dependent
+    std (args as for `rollout` / `rollout_cat` / `rollout_sd`), pf_ln / vf_ln which of the two nets carries the LayerNorm; a
+    normed net's block is in `ops.plan_params` order."""
+    check(lib().trl_rollout_synth_ln_f32(C.byref(args), int(head), int(bool(pf_ln)), int(bool(vf_ln)), int(noise_seed),
+                                         int(env_offset), stream_ptr(device)), "trl_rollout_synth_ln_f32")
 
 
 def _partial_stride(name, D, H, A):

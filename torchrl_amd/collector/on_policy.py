@@ -370,6 +370,35 @@ class VecOnPolicyCollector(VecCollector):
                 all(getattr(e, "discrete", False) and hasattr(e, "env_B") and not getattr(e, "is_host_env", False)
                     and not hasattr(e, "_obs_normalizer") for e in (self.env, self.eval_env) if e is not None)
             self._spec = ps if fused else None
+        self._ln = None
+        if os.environ.get("TRL_LN_FUSED_ROLLOUT") == "1":
+            self._ln_fused_route(kind)
+
+    def _ln_fused_route(self, kind):
+        """`add_ln` nets (`mlp2_spec()` is None for them, so everything above chose the per-step route): the persistent
+        rollout's LayerNorm variant (trl_rollout_synth_ln_f32) carries a pair of which at least one net is the two-layer
+        `add_ln` block (`Net.mlp2_ln_spec`) and the other that or a plain MLP2 block, 64 wide, same input and activation,
+        a head shape of the head's range, on a device synthetic env of the head's kind, one rank, no observation normaliser,
+        no noise prefetch.  Opt-in, TRL_LN_FUSED_ROLLOUT=1 (profiles/NOTES_layernorm_rollout.md); TRL_NO_RT_ROLLOUT=1
+        switches it off like the other runtime-dims instantiations.  `_ln` = (policy normed, critic normed)."""
+        def spec_of(net):
+            if not hasattr(net, "mlp2_ln_spec"):
+                return None
+            return net.mlp2_ln_spec() if net.add_ln else net.mlp2_spec()
+        pf_ln = bool(getattr(self.pf, "add_ln", False))
+        vf_ln = not self._no_critic and bool(getattr(self.vf, "add_ln", False))
+        ps, vs = spec_of(self.pf), None if self._no_critic else spec_of(self.vf)
+        if not (pf_ln or vf_ln) or ps is None or ps[2] != self._head_w:
+            return
+        if not self._no_critic and (vs is None or vs[:2] != ps[:2] or vs[2] != 1 or vs[3] != ps[3]):
+            return
+        A = self._dims[1]
+        envs = [e for e in (self.env, self.eval_env) if e is not None]
+        if bool(_C.lib().trl_rollout_ln_supported(kind, ps[0], ps[1], A, ps[3])) and \
+                os.environ.get("TRL_NO_RT_ROLLOUT") != "1" and dist.world_size() == 1 and not self.prefetch_noise and \
+                all(bool(getattr(e, "discrete", False)) == self._cat and hasattr(e, "env_B")
+                    and not getattr(e, "is_host_env", False) and not hasattr(e, "_obs_normalizer") for e in envs):
+            self._spec, self._mlp2, self._ln, self._head = (ps[0], ps[1], A, ps[3]), None, (pf_ln, vf_ln), kind
 
     def _forward(self, net, x, out_dim, out=None):
         """mean / value of an MLP on the device: the fused 2-layer kernel when instantiated, the dense-layer family
@@ -417,8 +446,11 @@ class VecOnPolicyCollector(VecCollector):
             a.norm_workspace, a.norm_clip = self._norm_ws.data_ptr(), float(nz.clip)
             a.norm_update = int(update)
             a.normalize_partial_reset = int(bool(getattr(env, "normalize_partial_reset", False)))
-        a.pf_params = self.pf.flat_params().data_ptr()
-        a.vf_params = None if self._no_critic else self.vf.flat_params().data_ptr()   # (NULL: the zero-storing value pass)
+        # (a normed net: its block in ops.plan_params order, where the update engine homed it -- nothing is copied or moved)
+        ln = self._ln or (False, False)
+        block = lambda net, normed: net.flat_plan_params() if normed else net.flat_params()
+        a.pf_params = block(self.pf, ln[0]).data_ptr()
+        a.vf_params = None if self._no_critic else block(self.vf, ln[1]).data_ptr()   # (NULL: the zero-storing value pass)
         # The rollout reads the policy only; the value function may still be in the hands of the previous epoch's critic
         # updates on another stream (algo/on_policy/ppo.py: two update chains): the value pass behind the rollout waits
         # for their end, the rollout itself does not.
@@ -481,7 +513,9 @@ class VecOnPolicyCollector(VecCollector):
             words = 8 + 3 * self.SPECULATIVE_ROWS
             a.publish_dst, a.publish_src, a.publish_words = self._blob_host.data_ptr(), self._blob.data_ptr(), words
             self._published = True
-        if self._cat:                                                   # the draw trl_cat_act_f32 makes at these steps
+        if self._ln:                                                    # (either net normed; the head's own arguments)
+            _C.rollout_ln(a, self._head, ln[0], ln[1], self._noise_seed, self._noise_layout(env)[1] if self._cat else 0, env.device)
+        elif self._cat:                                                 # the draw trl_cat_act_f32 makes at these steps
             _C.rollout_cat(a, self._noise_seed, self._noise_layout(env)[1], env.device)
         elif self._sd:                                                  # a.A = action dims, pf_params has a 2A-row head
             _C.rollout_sd(a, env.device)

@@ -121,6 +121,44 @@ class Net(nn.Module):
     def _extra_flat_params(self):
         return []
 
+    # ---- the `add_ln` two-layer block of the persistent rollout's LayerNorm variant ----
+    def mlp2_ln_spec(self):
+        """(D, H, O, act_code) if this net is exactly Linear(D, H), act, LayerNorm(H), Linear(H, H), act, act, Linear(H, O)
+        -- an `add_ln` MLPBase of two equal widths with one appended head, what the reference's construction makes of it
+        (base.py::_trunk) -- else None.  `mlp2_spec()` stays None for such a net."""
+        b = self.base
+        if not isinstance(b, MLPBase) or not self.add_ln or not b.add_ln or len(self.append_fcs) != 1:
+            return None
+        if len(b.hidden_shapes) != 2 or b.hidden_shapes[0] != b.hidden_shapes[1]:
+            return None
+        a = b.activation_func
+        if a not in _ACT_CODE or b.last_activation_func is not a:
+            return None
+        H = b.hidden_shapes[0]
+        kinds = [type(m) for m in b.seq_fcs]
+        if kinds != [nn.Linear, a, nn.LayerNorm, nn.Linear, a, a]:
+            return None
+        norm = b.seq_fcs[2]
+        if tuple(norm.normalized_shape) != (H,) or not norm.elementwise_affine or norm.bias is None or float(norm.eps) != 1e-5:
+            return None
+        return (b.input_dim, H, self.out_dim, _ACT_CODE[a])
+
+    def flat_plan_params(self):
+        """The parameters in `ops.plan_params` order -- W1 b1 gamma1 beta1 W2 b2 W3 b3 [logstd] for an `mlp2_ln_spec` net --
+        as ONE contiguous fp32 vector that aliases them.  Where they already lie back to back in that order (the update
+        engine homes them so, `_GenericPPO._home`) the vector is a view of that very storage and nothing moves; otherwise
+        they are re-homed once, like `flat_params`."""
+        from .. import ops
+        plist = ops.plan_params(ops.net_plan(self)) + self._extra_flat_params()
+        first, off = plist[0], 0
+        for p in plist:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != first.device or \
+                    p.untyped_storage().data_ptr() != first.untyped_storage().data_ptr() or \
+                    p.storage_offset() != first.storage_offset() + off:
+                return flatten_into(plist)                              # (the parameters keep it alive; the next call finds them in place)
+            off += p.numel()
+        return first.detach().new_empty(0).set_(first.untyped_storage(), first.storage_offset(), (off,), (1,))
+
     # (whoever saves or loads the parameters reads / writes them on the current stream: settle first, like `forward`)
     def _settle_params(self):
         if _PENDING and self in _PENDING:
