@@ -737,6 +737,22 @@ int trl_linear_bwd_weight_multi_splits(int M, int K, int N);
 int trl_linear_bwd_weight_partials_multi_f32(int G, const float* const* dy, const float* const* y_gate, int gate_act,
                                              const float* const* x, const int* K, const int* N, int want_db,
                                              float* const* workspace, int M, void* stream);
+/* Host-only route query of the dense-layer family: which kernel instantiation, reduction split and fold the entry point
+ * `op` takes for G problems of a batch of M rows, K inputs and N outputs.  Launches nothing and touches no device; it
+ * asks the selector functions the launchers ask.  K / N have length 1, for TRL_ROUTE_BWD_WEIGHT_MULTI length G.  Per
+ * problem (one, for the multi launch G) `out` receives TRL_ROUTE_FIELDS ints: tile M, tile N (of the GEMM as launched: the
+ * weight gradient's C is (N x K)), panel depth, splits, split length, skinny flag, fold waves (0: no fold).  A layer of
+ * an all-skinny multi launch runs in the skinny kernel and reports tile 0 x 0, panel 0.  FWD_SPLITK / BWD_INPUT_SPLITK /
+ * BWD_WEIGHT describe trl_linear_fwd_splitk[_group]_f32, trl_linear_bwd_input_splitk_f32 (G = 1) and
+ * trl_linear_bwd_weight[_group]_f32 (fold waves as when db is asked for); one split means the plain launch. */
+#define TRL_ROUTE_FWD              0
+#define TRL_ROUTE_FWD_SPLITK       1
+#define TRL_ROUTE_BWD_INPUT        2
+#define TRL_ROUTE_BWD_INPUT_SPLITK 3
+#define TRL_ROUTE_BWD_WEIGHT       4
+#define TRL_ROUTE_BWD_WEIGHT_MULTI 5
+#define TRL_ROUTE_FIELDS           7
+int trl_linear_route_i32(int op, int G, int M, const int* K, const int* N, int32_t* out);
 
 /* Forward of G MLPs D -> 256 -> 256 -> O (D <= 32, O <= 16: the policy / Q networks of SAC, DDPG, TD3;
  * networks/base.py:30-44, nets.py:34-68) in ONE launch: hidden activations stay in LDS, W2 is walked in double-buffered

@@ -434,6 +434,7 @@ SIGNATURES = {
     "trl_linear_bwd_weight_multi_splits": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_linear_bwd_weight_partials_multi_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "trl_linear_route_i32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "trl_linear_bwd_weight_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
@@ -1756,6 +1757,23 @@ def linear_bwd_weight(dy, y_gate, gate_act, x, dw=None, db=None, need_bias=True,
                                           dev_ptr(db, name="db", allow_none=True), dev_ptr(workspace, name="workspace"),
                                           M, K, N, stream_ptr(dy.device)), "trl_linear_bwd_weight_f32")
     return dw, db
+
+
+ROUTE_OPS = {"fwd": 0, "fwd_splitk": 1, "bwd_input": 2, "bwd_input_splitk": 3, "bwd_weight": 4, "bwd_weight_multi": 5}
+ROUTE_FIELDS = ("tile_m", "tile_n", "panel", "splits", "split_len", "skinny", "fold_waves")
+
+
+def linear_route(op, M, K, N, G=1):
+    """The route a dense-layer entry point takes (include/trl_hip.h trl_linear_route_i32; host only, nothing is launched):
+    a dict of ROUTE_FIELDS, or for op "bwd_weight_multi" (K, N: sequences of the G layers' widths) a list of one per layer."""
+    multi = op == "bwd_weight_multi"
+    Ks, Ns = (list(K), list(N)) if multi else ([int(K)], [int(N)])
+    G = len(Ks) if multi else int(G)
+    out = (C.c_int32 * (len(ROUTE_FIELDS) * len(Ks)))()
+    check(lib().trl_linear_route_i32(ROUTE_OPS[op], G, int(M), (C.c_int * len(Ks))(*Ks), (C.c_int * len(Ns))(*Ns), out),
+          "trl_linear_route_i32")
+    rows = [dict(zip(ROUTE_FIELDS, out[i * len(ROUTE_FIELDS):(i + 1) * len(ROUTE_FIELDS)])) for i in range(len(Ks))]
+    return rows if multi else rows[0]
 
 
 def concat2(a, b):

@@ -35,7 +35,7 @@ __device__ __forceinline__ float dact_from_out(int act, float y) {
   return 1.0f;
 }
 
-// Up to 8 independent problems of identical shape in one launch (blockIdx.y): the twin critics and their targets,
+// Up to 12 independent problems of identical shape in one launch (blockIdx.y): the twin critics and their targets,
 // one network on several inputs.  A 4096 x 256 x 256 layer is 256 workgroups and ~4 us of MFMA behind ~4 us of
 // launch + prologue + epilogue; grouped, the problems' workgroups overlap each other's fixed costs.
 #define GEMM_MAX_GROUPS 12
@@ -610,10 +610,13 @@ extern "C" int trl_fold_scope_end(void* stream) {
   return TRL_OK;
 }
 
+// many splits behind few workgroups: 16 waves share them (latency-bound walk); otherwise 4
+static int fold_waves(int splits, int blocks, int groups) {
+  return (splits >= 32 && (int64_t)blocks * groups < 2048) ? FOLD_MAX_WAVES : 4;
+}
 static int launch_fold(FoldDev f, int groups, hipStream_t s, bool immediate = false) {
   const int blocks = trl_ceil_div((int64_t)f.n + f.n2, FOLD_OUT);
-  // many splits behind few workgroups: 16 waves share them (latency-bound walk); otherwise 4
-  const int waves = (f.splits >= 32 && (int64_t)blocks * groups < 2048) ? FOLD_MAX_WAVES : 4;
+  const int waves = fold_waves(f.splits, blocks, groups);
   if (g_fold_scope.on && !immediate && groups == 1 && f.n_cols == 0 && g_fold_scope.d.count < FOLD_SCOPE_MAX) {
     const FoldGroup& q = f.grp[0];
     g_fold_scope.d.e[g_fold_scope.d.count++] = FoldScopeEntry{f.n, f.n2, f.splits, f.perm_c, f.perm_khw, waves, g_fold_scope.blocks,
@@ -735,19 +738,32 @@ static bool short_reduction(const GemmDev& g, int splits, int gm, int gn, int co
   return wgs >= 768 && red <= 512;
 }
 
+// The instantiation a launch takes: waves along M, accumulator blocks per wave and side, panel depth.  The one place that
+// decides it, for launch_gemm_gate and for the host-only route query (trl_linear_route_i32).
+struct TileRoute { int wm, tmb, kp; };
+static TileRoute tile_route(const GemmDev& g, int splits, int conv) {
+  const int wm = tile_wm(g.M, g.N);
+  if (wm == 4) return TileRoute{4, 1, (conv == 3 && short_reduction(g, splits, 128, 32, conv)) ? 32 : 64};
+  if (wm == 1) return TileRoute{1, 1, 64};
+  if (conv == 0 && tile_128(g, splits)) return TileRoute{2, 2, 32};
+  // (the implicit forward on 64 x 64 tiles decodes its taps once per panel and, without pre-ordered weights, gathers B
+  // with strided 4-byte loads: with twice the panels that lost, 56.6 vs 42 us)
+  if ((conv == 0 || conv == 3) && short_reduction(g, splits, 64, 64, conv)) return TileRoute{2, 1, 32};
+  return TileRoute{2, 1, 64};
+}
+
 template <bool TA, bool TB, int GATE, int CONV>
 static int launch_gemm_gate(const GemmDev& g, int splits, hipStream_t s) {
-  switch (tile_wm(g.M, g.N)) {
+  const TileRoute r = tile_route(g, splits, CONV);
+  switch (r.wm) {
     case 4:
-      if constexpr (CONV == 3) { if (short_reduction(g, splits, 128, 32, CONV)) return launch_gemm_tile<TA, TB, GATE, CONV, 4, 1, 32>(g, splits, s); }
+      if constexpr (CONV == 3) { if (r.kp == 32) return launch_gemm_tile<TA, TB, GATE, CONV, 4, 1, 32>(g, splits, s); }
       return launch_gemm_tile<TA, TB, GATE, CONV, 4>(g, splits, s);
     case 1:  return launch_gemm_tile<TA, TB, GATE, CONV, 1>(g, splits, s);
     default:
-      if constexpr (CONV == 0) { if (tile_128(g, splits)) return launch_gemm_tile<TA, TB, GATE, CONV, 2, 2>(g, splits, s); }
-      // (the implicit forward on 64 x 64 tiles decodes its taps once per panel and, without pre-ordered weights, gathers B
-      // with strided 4-byte loads: with twice the panels that lost, 56.6 vs 42 us)
+      if constexpr (CONV == 0) { if (r.tmb == 2) return launch_gemm_tile<TA, TB, GATE, CONV, 2, 2>(g, splits, s); }
       if constexpr (CONV == 0 || CONV == 3) {
-        if (short_reduction(g, splits, 64, 64, CONV)) return launch_gemm_tile<TA, TB, GATE, CONV, 2, 1, 32>(g, splits, s);
+        if (r.kp == 32) return launch_gemm_tile<TA, TB, GATE, CONV, 2, 1, 32>(g, splits, s);
       }
       return launch_gemm_tile<TA, TB, GATE, CONV, 2>(g, splits, s);
   }
@@ -1131,16 +1147,33 @@ static int launch_bwd_weight_multi_kp(GemmDev& g, int max_tiles, int max_splits,
   TRL_LAUNCH_CHECK();
   return TRL_OK;
 }
-template <int GATE>
-static int launch_bwd_weight_multi(GemmDev& g, int max_tiles, int max_splits, hipStream_t s) {
-  // slices of <= 512 batch rows on >= 768 workgroups: the 32-wide panel, four workgroups per CU (see gemm_f32_kernel)
+// panel depth of the mixed-shape launch: slices of <= 512 batch rows on >= 768 workgroups take the 32-wide panel, four
+// workgroups per CU (see gemm_f32_kernel)
+static int multi_panel(const GemmShape* shp, int G) {
   static const int pin = [] { const char* e = getenv("TRL_GEMM_KP"); return e ? atoi(e) : 0; }();
   int64_t wgs = 0;
   int longest = 0;
-  for (int i = 0; i < g.groups; ++i) { wgs += (int64_t)g.shp[i].tiles * g.shp[i].splits; longest = std::max(longest, g.shp[i].split_len); }
-  if (pin != 64 && (pin == 32 || (wgs >= 768 && longest <= 512)))
-    return launch_bwd_weight_multi_kp<GATE, 32>(g, max_tiles, max_splits, s);
+  for (int i = 0; i < G; ++i) { wgs += (int64_t)shp[i].tiles * shp[i].splits; longest = std::max(longest, shp[i].split_len); }
+  return (pin != 64 && (pin == 32 || (wgs >= 768 && longest <= 512))) ? 32 : 64;
+}
+template <int GATE>
+static int launch_bwd_weight_multi(GemmDev& g, int max_tiles, int max_splits, hipStream_t s) {
+  if (multi_panel(g.shp, g.groups) == 32) return launch_bwd_weight_multi_kp<GATE, 32>(g, max_tiles, max_splits, s);
   return launch_bwd_weight_multi_kp<GATE, 0>(g, max_tiles, max_splits, s);
+}
+// every layer of a mixed-shape launch is skinny: the launch is skinny_bwdw_kernel's, else the hetero GEMM's
+static bool multi_all_skinny(int G, const int* K, const int* N) {
+  bool all_skinny = true;
+  for (int i = 0; i < G; ++i) all_skinny = all_skinny && K[i] > 0 && N[i] > 0 && skinny_layer(K[i], N[i]);
+  return all_skinny;
+}
+// the shape of one layer's weight gradient (N x K, reduction M) in the hetero launch: 64 x 64 tiles, its own split
+static void multi_shape(int M, int K, int N, GemmShape& h) {
+  const int split_len = multi_split_len(M, K, N);
+  const int splits = trl_ceil_div(M, split_len);
+  h.M = N; h.N = K; h.K = M; h.lda = N; h.ldb = K; h.ldc = K;
+  h.split_len = splits > 1 ? split_len : M; h.splits = splits;
+  h.tiles_n = trl_ceil_div(K, 64); h.tiles = h.tiles_n * trl_ceil_div(N, 64);
 }
 extern "C" int trl_linear_bwd_weight_partials_multi_f32(int G, const float* const* dy, const float* const* y_gate,
                                                         int gate_act, const float* const* x, const int* K, const int* N,
@@ -1148,9 +1181,7 @@ extern "C" int trl_linear_bwd_weight_partials_multi_f32(int G, const float* cons
   TRL_REQUIRE(G >= 1 && G <= GEMM_MAX_GROUPS, "1..12 problems per launch");
   TRL_REQUIRE(dy && x && K && N && workspace && M > 0, "null pointer array / empty batch");
   TRL_REQUIRE(gate_act == TRL_ACT_TANH || gate_act == TRL_ACT_RELU || gate_act == TRL_ACT_NONE, "unknown activation");
-  bool all_skinny = true;
-  for (int i = 0; i < G; ++i) all_skinny = all_skinny && K[i] > 0 && N[i] > 0 && skinny_layer(K[i], N[i]);
-  if (all_skinny) {
+  if (multi_all_skinny(G, K, N)) {
     SkinnyDev sk{};
     sk.M = M; sk.gate_act = gate_act;
     int max_splits = 0, max_wide = 0;
@@ -1180,12 +1211,9 @@ extern "C" int trl_linear_bwd_weight_partials_multi_f32(int G, const float* cons
   bool any_gate = false;
   for (int i = 0; i < G; ++i) {
     TRL_REQUIRE(dy[i] && x[i] && workspace[i] && K[i] > 0 && N[i] > 0, "null pointer / bad layer size");
-    const int split_len = multi_split_len(M, K[i], N[i]);
-    const int splits = trl_ceil_div(M, split_len);
     GemmShape& h = g.shp[i];
-    h.M = N[i]; h.N = K[i]; h.K = M; h.lda = N[i]; h.ldb = K[i]; h.ldc = K[i];
-    h.split_len = splits > 1 ? split_len : M; h.splits = splits;
-    h.tiles_n = trl_ceil_div(K[i], 64); h.tiles = h.tiles_n * trl_ceil_div(N[i], 64);
+    multi_shape(M, K[i], N[i], h);
+    const int splits = h.splits;
     float* part = workspace[i];
     float* cpart = want_db ? part + (size_t)splits * N[i] * K[i] : nullptr;
     const float* gate = (y_gate && gate_act != TRL_ACT_NONE) ? y_gate[i] : nullptr;
@@ -1202,6 +1230,74 @@ extern "C" int trl_linear_bwd_weight_partials_multi_f32(int G, const float* cons
   if (gate_act == TRL_ACT_TANH) return launch_bwd_weight_multi<TRL_ACT_TANH>(g, max_tiles, max_splits, s);
   return launch_bwd_weight_multi<TRL_ACT_RELU>(g, max_tiles, max_splits, s);
 }
+
+// ---- host-only route query: which instantiation, split and fold a dense entry point would take ----
+// Launches nothing and touches no device: it asks the selectors above, the ones the launchers ask.  Per problem, out holds
+// TRL_ROUTE_FIELDS ints: tile M, tile N, panel depth, splits, split length, skinny flag, fold waves (0: nothing is folded).
+// The tile is that of the GEMM as launched (the weight gradient's is over (N x K)); a problem of an all-skinny mixed launch
+// runs in skinny_bwdw_kernel and reports tile 0 x 0 and panel 0.  The weight-gradient folds are those of a call that asks for db.
+static void route_fill(int32_t* o, const GemmDev& g, int splits, int fold_n, int fold_groups) {
+  const TileRoute r = tile_route(g, splits, 0);
+  o[0] = 32 * r.wm * r.tmb; o[1] = 32 * (4 / r.wm) * r.tmb; o[2] = r.kp;
+  o[3] = splits; o[4] = g.split_len; o[5] = 0;
+  o[6] = splits > 1 ? fold_waves(splits, trl_ceil_div(fold_n, FOLD_OUT), fold_groups) : 0;
+}
+extern "C" int trl_linear_route_i32(int op, int G, int M, const int* K, const int* N, int32_t* out) {
+  TRL_REQUIRE(K && N && out, "null pointer");
+  TRL_REQUIRE(G >= 1 && G <= GEMM_MAX_GROUPS, "1..12 problems per grouped launch");
+  TRL_REQUIRE(M > 0, "bad sizes");
+  const int count = op == TRL_ROUTE_BWD_WEIGHT_MULTI ? G : 1;
+  for (int i = 0; i < count; ++i) TRL_REQUIRE(K[i] > 0 && N[i] > 0, "bad sizes");
+  const int k = K[0], n = N[0];
+  GemmDev g{};
+  g.groups = G;
+  switch (op) {
+    case TRL_ROUTE_FWD:
+      g.M = M; g.N = n; g.K = k; g.split_len = k;
+      route_fill(out, g, 1, 0, 1);
+      return TRL_OK;
+    case TRL_ROUTE_FWD_SPLITK: {
+      const int split_len = fwd_split_len(M, k, n, G), splits = trl_ceil_div(k, split_len);
+      g.M = M; g.N = n; g.K = k; g.split_len = splits > 1 ? split_len : k;
+      g.prefer128 = (splits > 1 && fwd_use_128(M, k, n, G)) ? 1 : 0;
+      route_fill(out, g, splits, M * n, G);
+      return TRL_OK;
+    }
+    case TRL_ROUTE_BWD_INPUT:
+      g.M = M; g.N = k; g.K = n; g.split_len = n;
+      route_fill(out, g, 1, 0, 1);
+      return TRL_OK;
+    case TRL_ROUTE_BWD_INPUT_SPLITK: {
+      TRL_REQUIRE(G == 1, "the split input gradient is a single problem");
+      const int split_len = bwdin_split_len(M, k, n), splits = trl_ceil_div(n, split_len);
+      g.M = M; g.N = k; g.K = n; g.split_len = splits > 1 ? split_len : n;
+      route_fill(out, g, splits, M * k, 1);
+      return TRL_OK;
+    }
+    case TRL_ROUTE_BWD_WEIGHT: {
+      const int split_len = bw_split_len(M, k, n), splits = trl_ceil_div(M, split_len);
+      g.M = n; g.N = k; g.K = M; g.split_len = split_len;
+      route_fill(out, g, splits, n * k + n, G);
+      return TRL_OK;
+    }
+    case TRL_ROUTE_BWD_WEIGHT_MULTI: {
+      const bool skinny = multi_all_skinny(G, K, N);
+      GemmShape shp[GEMM_MAX_GROUPS];
+      for (int i = 0; i < G; ++i) multi_shape(M, K[i], N[i], shp[i]);
+      const int kp = skinny ? 0 : multi_panel(shp, G);
+      for (int i = 0; i < G; ++i) {
+        int32_t* o = out + TRL_ROUTE_FIELDS * i;
+        o[0] = skinny ? 0 : 64; o[1] = skinny ? 0 : 64; o[2] = kp;
+        o[3] = shp[i].splits; o[4] = multi_split_len(M, K[i], N[i]); o[5] = skinny ? 1 : 0;
+        o[6] = 4;                                    // fold_multi_kernel: always four waves
+      }
+      return TRL_OK;
+    }
+  }
+  trl_set_error("trl_linear_route_i32: unknown op %d", op);
+  return TRL_EINVAL;
+}
+
 // ---- first conv layer on uint8 frames as an implicit GEMM ----
 static int fill_conv(const char* who, const uint8_t* frames, int B, int C, int H, int W, int kh, int kw, int sh, int sw,
                      float scale, float shift, ConvSrc& cv, int& M, int& K) {
