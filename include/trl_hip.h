@@ -597,6 +597,32 @@ int trl_ppo_sd_reduce_adam_net_f32(const float* partial, const double* scal_part
                                    int D, int H, int A, float* grads, double* info,
                                    const trl_adam_t* adam, float* workspace, void* stream);
 
+/* --- the fused minibatch update for LAYERNORM nets (`add_ln`, 64 wide) ------------------------------------------------
+ * The entry points above for a pair of which the policy (ln_mask bit 0) and / or the critic (bit 1) is
+ *   Linear(D, 64), act, LayerNorm(64, eps 1e-5, affine), Linear(64, 64), act, act, Linear(64, O)
+ * -- the gradient kernel's LN passes.  A normed net's flat block is [W1 b1 gamma beta W2 b2 W3 b3 (logstd)], 128 floats more
+ * than a plain one's; its gradients leave in that order, gamma / beta are ordinary elements of the fold, the clip norm and
+ * Adam.  `head`: 0 Gaussian with a shared logstd, 1 categorical, 2 state-dependent-std; args, rows, scalar rows and info are
+ * that head's (above), the loss arithmetic too.  The norm: mean and variance of act(z1) over the 64 features in two passes,
+ * y = gamma xhat + beta; backward da1 = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)), dxhat = dy gamma.
+ * Shapes: trl_ppo_ln_supported (TRL_EUNSUPPORTED otherwise): H == 64, 2 <= D <= 32, A in the head's range, Tanh / ReLU,
+ * ln_mask in 1..3.  partial rows are trl_ppo_ln_partial_stride floats.  The folds are the kernels of the plain entry points
+ * launched with this pair's block lengths, stride and logstd offset; optimiser groups [policy | value] of those lengths.
+ * A single-network launch folded by trl_ppo_ln_reduce_adam_net_f32 gives the bits of the joint launch +
+ * trl_ppo_ln_reduce_adam_f32.  There is no cross-rank variant. */
+int trl_ppo_ln_supported(int D, int H, int A, int act, int head, int ln_mask);
+int trl_ppo_ln_partial_stride(int D, int H, int A, int head, int ln_mask);
+int trl_ppo_ln_minibatch_grad_f32(const trl_ppo_batch_t* args, int head, int ln_mask, void* stream);
+int trl_ppo_ln_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                          int head, int ln_mask, const float* pf_params, float* grads, double* info, void* stream);
+int trl_ppo_ln_reduce_adam_workspace(int D, int H, int A, int head, int ln_mask);
+int trl_ppo_ln_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                               int head, int ln_mask, float* grads, double* info, const trl_adam_t* adam,
+                               float* workspace, void* stream);
+int trl_ppo_ln_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net, int D, int H, int A,
+                                   int head, int ln_mask, float* grads, double* info, const trl_adam_t* adam,
+                                   float* workspace, void* stream);
+
 typedef struct trl_comm trl_comm_t;   /* opaque communicator, see the collectives section below */
 /* --- C1 / C2 / C3: collectives of the multi-GPU path ---------------
  * The reference has no distributed backend; with envs sharded by index over one process per GPU

@@ -265,6 +265,16 @@ SIGNATURES = {
                                               C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
     "trl_ppo_sd_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]),
+    # LayerNorm pairs (k_ppo_ln.hip): (..., head, ln_mask) behind the shape; ln_mask bit 0 = policy, bit 1 = critic
+    "trl_ppo_ln_supported": (C.c_int, [C.c_int] * 6),
+    "trl_ppo_ln_partial_stride": (C.c_int, [C.c_int] * 5),
+    "trl_ppo_ln_minibatch_grad_f32": (C.c_int, [C.POINTER(PpoBatchArgs), C.c_int, C.c_int, C.c_void_p]),
+    "trl_ppo_ln_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4),
+    "trl_ppo_ln_reduce_adam_workspace": (C.c_int, [C.c_int] * 5),
+    "trl_ppo_ln_reduce_adam_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(AdamArgs),
+                                                                                       C.c_void_p, C.c_void_p]),
+    "trl_ppo_ln_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(AdamArgs),
+                                                                                           C.c_void_p, C.c_void_p]),
     "trl_synth_reset_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "trl_gauss_logp_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_concat2_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
@@ -753,6 +763,27 @@ def ppo_sd_reduce(partial, scal_partial, n_wg, D, H, A, grads, info, n_wg_pf=0):
                                       dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A,
                                       None, dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
                                       stream_ptr(partial.device)), "trl_ppo_sd_reduce_f32")
+
+
+def ppo_ln_partial_stride(D, H, A, head, ln_mask):
+    """Floats of a partial row for a pair of which the policy (ln_mask bit 0) and / or the critic (bit 1) is normed."""
+    ps = lib().trl_ppo_ln_partial_stride(D, H, A, head, ln_mask)
+    if ps < 0:
+        check(ps, "trl_ppo_ln_partial_stride")
+    return ps
+
+
+def ppo_ln_minibatch_grad(args, head, ln_mask, device):
+    """The fused minibatch gradient for `add_ln` nets: a normed net's block is [W1 b1 gamma beta W2 b2 W3 b3 (logstd)]."""
+    check(lib().trl_ppo_ln_minibatch_grad_f32(C.byref(args), head, ln_mask, stream_ptr(device)), "trl_ppo_ln_minibatch_grad_f32")
+
+
+def ppo_ln_reduce(partial, scal_partial, n_wg, D, H, A, head, ln_mask, grads, info, pf_params=None, n_wg_pf=0):
+    check(lib().trl_ppo_ln_reduce_f32(dev_ptr(partial, name="partial"),
+                                      dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A, head, ln_mask,
+                                      dev_ptr(pf_params, name="pf_params", allow_none=True),
+                                      dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
+                                      stream_ptr(partial.device)), "trl_ppo_ln_reduce_f32")
 
 
 def ppo_minibatch_grad(args, device):

@@ -150,7 +150,15 @@ class _FusedPPO:
     def __init__(self, algo):
         self.algo = algo
         pf, vf = algo.pf, _critic(algo)
-        ps, vs = pf.mlp2_spec(), None if vf is None else vf.mlp2_spec()
+        # TRL_LN_FUSED_UPDATE=1 (`make_engine`): `add_ln` two-layer blocks (`Net.mlp2_ln_spec`) are carried by the gradient
+        # kernel's LN passes (trl_ppo_ln_*); `ln_mask` bit 0: the policy is normed, bit 1: the critic.  The parameters are
+        # homed in `ops.plan_params` order -- gamma / beta behind their layer -- which is where `Net.flat_plan_params` and
+        # with it the LayerNorm rollout find them.
+        ln_on = _ln_fused_update()
+        normed = lambda net: bool(ln_on and net is not None and getattr(net, "add_ln", False))
+        spec_of = lambda net: net.mlp2_ln_spec() if normed(net) else net.mlp2_spec()
+        self.ln_mask = int(normed(pf)) | (int(normed(vf)) << 1)
+        ps, vs = spec_of(pf), None if vf is None else spec_of(vf)
         # a vacant critic (vf None): the policy alone in the flat buffers, every gradient workgroup the policy's
         # a categorical head (policies.CategoricalDisPolicy): the gradient kernel's HEAD_CAT instantiations and their folds
         # (trl_ppo_cat_*); no logstd in the flat vector, the entropy arrives through info slot 20
@@ -174,12 +182,17 @@ class _FusedPPO:
         if self.dev.type != "cuda":
             raise _C.TrlError("PPO networks live on %s: the fused path needs a GPU (no CPU path exists)" % self.dev)
         tail = (lambda net: []) if (self.categorical or self.state_std) else (lambda net: [net.logstd])
-        pf_list = pf._mlp2_param_list() + tail(pf)
-        vf_list = [] if vf is None else vf._mlp2_param_list()
+        if self.ln_mask:
+            from ... import ops
+            plist = lambda net: ops.plan_params(ops.net_plan(net))     # W, b (, gamma, beta) per layer: a plain net's MLP2 order
+        else:
+            plist = lambda net: net._mlp2_param_list()
+        pf_list = plist(pf) + tail(pf)
+        vf_list = [] if vf is None else plist(vf)
         tgt = getattr(algo, "target_pf", None)
-        self._home(pf_list, vf_list, None if tgt is None else tgt._mlp2_param_list() + tail(tgt))
-        if tgt is not None and (self.categorical or self.state_std):   # (its forward must find THIS storage, see _GenericPPO)
-            tgt._flat = self.target_flat
+        self._home(pf_list, vf_list, None if tgt is None else plist(tgt) + tail(tgt))
+        if tgt is not None and (self.categorical or self.state_std) and tgt.mlp2_spec() is not None:
+            tgt._flat = self.target_flat                               # (its forward must find THIS storage, see _GenericPPO)
         lib = _C.lib()
         sfx = HEAD_TAG[self.head]
         kernel = lambda name: (getattr(lib, name), name)
@@ -187,14 +200,25 @@ class _FusedPPO:
         self._k_fold, self._k_fold_net = kernel("trl_ppo_%sreduce_adam_f32" % sfx), kernel("trl_ppo_%sreduce_adam_net_f32" % sfx)
         # (the folds that carry the gradient SUM over ranks exist for the shared-std Gaussian head only)
         self._k_fold_x, self._k_fold_net_x = kernel("trl_ppo_reduce_adam_xrank_f32"), kernel("trl_ppo_reduce_adam_xrank_net_f32")
-        self.p_stride = getattr(_C, "ppo_%spartial_stride" % sfx)(self.D, self.H, self.A)
+        if self.ln_mask:
+            # the LN entry points take (head, ln_mask) behind the shape: the same call sites, the pair bound here
+            hd, mask = self.head, self.ln_mask
+            bound = lambda name: ((lambda *a: getattr(lib, name)(*a[:7], hd, mask, *a[7:])), name)
+            self._k_grad = ((lambda g, stream: lib.trl_ppo_ln_minibatch_grad_f32(g, hd, mask, stream)), "trl_ppo_ln_minibatch_grad_f32")
+            self._k_fold, self._k_fold_net = bound("trl_ppo_ln_reduce_adam_f32"), bound("trl_ppo_ln_reduce_adam_net_f32")
+            self._k_fold_x = self._k_fold_net_x = None
+            self.one_rank = "the fused LayerNorm update runs on one rank (no cross-rank fold exists for it)"
+            self.p_stride = _C.ppo_ln_partial_stride(self.D, self.H, self.A, hd, mask)
+        else:
+            self.p_stride = getattr(_C, "ppo_%spartial_stride" % sfx)(self.D, self.H, self.A)
         # doubles of scalar statistics per workgroup (SD: a second block of rows behind the n_wg x 8 of every head)
         self.scal_w = _C.ppo_sd_scalar_stride() if self.state_std else 8
         self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         self.max_wg = 2 * max(1, self.n_cu // 2)
         self.partial = torch.zeros(self.max_wg, self.p_stride, device=self.dev)
         self.scal = torch.zeros(self.max_wg, self.scal_w, dtype=torch.float64, device=self.dev)
-        n_ws = getattr(lib, "trl_ppo_%sreduce_adam_workspace" % sfx)(self.D, self.H, self.A)
+        n_ws = lib.trl_ppo_ln_reduce_adam_workspace(self.D, self.H, self.A, self.head, self.ln_mask) if self.ln_mask else \
+            getattr(lib, "trl_ppo_%sreduce_adam_workspace" % sfx)(self.D, self.H, self.A)
         self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + norm granules of the fold / clip / Adam launch
         # One process: the critic's and the actor's updates of an epoch (ppo.py:93-122 / 41-91: separate networks, optimisers,
         # clips and statistics) run as TWO launch sequences on two streams (`_run_chains`); TRL_PPO_CHAINS=joint keeps the
@@ -771,6 +795,33 @@ class _PendingInfos:
 _HEAD_OPT_IN = {HEAD_CAT: "TRL_CAT_FUSED_UPDATE", HEAD_SD: "TRL_SD_FUSED_UPDATE"}
 
 
+def _ln_fused_update():
+    """TRL_LN_FUSED_UPDATE=1: 64-wide `add_ln` pairs take the two-launch update (the gradient kernel's LN passes).  Unset,
+    they run on the generic engine, as they always have (opt-in, like TRL_LN_FUSED_ROLLOUT)."""
+    return os.environ.get("TRL_LN_FUSED_UPDATE") == "1"
+
+
+def _ln_fused_pair(algo, pf, vf, kind):
+    """Does the fused engine carry this pair under TRL_LN_FUSED_UPDATE=1?  Every network is an `mlp2_spec` or an
+    `mlp2_ln_spec` block and at least one the latter; input, width (64) and activation match; the head's shape is in its
+    range; both optimisers are Adam; one rank.  (The two non-default heads need no switch of their own on this route.)"""
+    nets = [pf] + ([] if vf is None else [vf])
+    if not all(hasattr(n, "mlp2_ln_spec") for n in nets) or not any(getattr(n, "add_ln", False) for n in nets):
+        return False
+    specs = [n.mlp2_ln_spec() if n.add_ln else n.mlp2_spec() for n in nets]
+    if any(s is None for s in specs):
+        return False
+    ps = _head_spec(kind, specs[0])
+    if vf is not None and tuple(specs[1]) != (ps[0], ps[1], 1, ps[3]):
+        return False
+    if kind == HEAD_GAUSS and not hasattr(pf, "logstd"):
+        return False
+    mask = int(bool(pf.add_ln)) | (int(vf is not None and bool(vf.add_ln)) << 1)
+    opts = [getattr(algo, name, None) for name in ("pf_optimizer",) + (() if vf is None else ("vf_optimizer",))]
+    return bool(_C.lib().trl_ppo_ln_supported(ps[0], ps[1], ps[2], ps[3], kind, mask)) and \
+        all(type(o) is optim.Adam for o in opts) and not dist.collectives_active()
+
+
 def _head_spec(kind, ps):
     """(D, H, A, act) as the head's kernels count A: a [mean | log_std] head of width 2A has A action dimensions."""
     return (ps[0], ps[1], ps[2] // 2, ps[3]) if kind == HEAD_SD else tuple(ps)
@@ -973,6 +1024,8 @@ def make_engine(algo, fused=_FusedPPO, generic=_GenericPPO):
     forced = os.environ.get("TRL_GENERIC_PPO") == "1"
     kind = head_kind(pf)
     opt = getattr(algo, "pf_optimizer", None)
+    if _ln_fused_update() and not forced and kind in (HEAD_GAUSS, HEAD_CAT, HEAD_SD) and _ln_fused_pair(algo, pf, vf, kind):
+        return fused(algo)                                             # `add_ln` pairs, 64 wide (opt-in)
     if opt is not None and type(opt) is not optim.Adam:
         return generic(algo)                                           # RMSprop / SGD: the fused fold / clip / Adam launches are Adam's
     if kind in _HEAD_OPT_IN:
