@@ -240,6 +240,14 @@ int trl_rollout_sd_supported(int D, int H, int A, int act);
 int trl_rollout_synth_ln_f32(const trl_rollout_t* args, int head, int pf_ln, int vf_ln, int64_t noise_seed,
                              int64_t env_offset, void* stream);
 int trl_rollout_ln_supported(int head, int D, int H, int A, int act);
+/* The same rollout for plain two-layer networks of width H = 128 or 256 (k_rollout_wide.hip), with any of the three heads:
+ * head = 0 Gaussian with a logstd tail, 1 categorical (noise_seed / env_offset key its draw and are ignored otherwise),
+ * 2 state-dependent std; args, parameter blocks [W1 b1 W2 b2 W3 b3 (logstd)], stored formats, value pass, header and episode
+ * log as for trl_rollout_synth_f32 / _cat_f32 / _sd_f32.  vf_params NULL: no critic.  args->norm_state / noise_flag /
+ * stage_n must be unset (TRL_EINVAL); shapes: trl_rollout_wide_supported (TRL_EUNSUPPORTED otherwise) -- H == 128 or 256,
+ * 2 <= D <= 32, the head's own range of A, Tanh or ReLU.  n_steps == 0: nothing is launched. */
+int trl_rollout_synth_wide_f32(const trl_rollout_t* args, int head, int64_t noise_seed, int64_t env_offset, void* stream);
+int trl_rollout_wide_supported(int head, int D, int H, int A, int act);
 /* Page-locked host block -> device buffer by a KERNEL (the device reads host memory in place), meant for a stream of
  * its own next to the one that computes: n floats (n % 4 == 0, 16-byte aligned pointers); when every workgroup's part is
  * in device memory, state[0] = stamp is stored with device scope -- what a consumer launched on another stream polls

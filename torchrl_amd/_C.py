@@ -190,6 +190,8 @@ SIGNATURES = {
     "trl_rollout_sd_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_rollout_synth_ln_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "trl_rollout_ln_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_rollout_synth_wide_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_rollout_wide_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_stage_h2d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trl_ppo_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_mlp2_forward_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -714,6 +716,13 @@ def rollout_ln(args, head, pf_ln, vf_ln, noise_seed, env_offset, device):
     normed net's block is in `ops.plan_params` order."""
     check(lib().trl_rollout_synth_ln_f32(C.byref(args), int(head), int(bool(pf_ln)), int(bool(vf_ln)), int(noise_seed),
                                          int(env_offset), stream_ptr(device)), "trl_rollout_synth_ln_f32")
+
+
+def rollout_wide(args, head, noise_seed, env_offset, device):
+    """The persistent rollout for plain 128- / 256-wide two-layer networks (args.H): head 0 / 1 / 2 = shared-std Gaussian /
+    categorical / state-dependent std, args as for `rollout` / `rollout_cat` / `rollout_sd`."""
+    check(lib().trl_rollout_synth_wide_f32(C.byref(args), int(head), int(noise_seed), int(env_offset), stream_ptr(device)),
+          "trl_rollout_synth_wide_f32")
 
 
 def _partial_stride(name, D, H, A):

@@ -373,6 +373,9 @@ class VecOnPolicyCollector(VecCollector):
         self._ln = None
         if os.environ.get("TRL_LN_FUSED_ROLLOUT") == "1":
             self._ln_fused_route(kind)
+        self._wide = False
+        if os.environ.get("TRL_WIDE_FUSED_ROLLOUT") == "1":
+            self._wide_fused_route(kind, ps, vs)
 
     def _ln_fused_route(self, kind):
         """`add_ln` nets (`mlp2_spec()` is None for them, so everything above chose the per-step route): the persistent
@@ -399,6 +402,26 @@ class VecOnPolicyCollector(VecCollector):
                 all(bool(getattr(e, "discrete", False)) == self._cat and hasattr(e, "env_B")
                     and not getattr(e, "is_host_env", False) and not hasattr(e, "_obs_normalizer") for e in envs):
             self._spec, self._mlp2, self._ln, self._head = (ps[0], ps[1], A, ps[3]), None, (pf_ln, vf_ln), kind
+
+    def _wide_fused_route(self, kind, ps, vs):
+        """128- and 256-wide plain pairs (everything above chose the per-step route for them): the persistent rollout's wide
+        variant (trl_rollout_synth_wide_f32, k_rollout_wide.hip) carries a policy and a critic that are MLP2 blocks of the same
+        input, width and activation (or a ZeroNet critic), a head shape of the head's range, on a device synthetic env of the
+        head's kind, one rank, no observation normaliser, no noise prefetch.  Opt-in, TRL_WIDE_FUSED_ROLLOUT=1
+        (profiles/NOTES_wide_rollout.md); TRL_NO_RT_ROLLOUT=1 switches it off like the other runtime-dims instantiations.
+        The update of such nets stays on the generic engine, which homes them in the MlpFlat order the kernel reads
+        (`flat_params()` is a view of that storage)."""
+        if ps is None or ps[2] != self._head_w:
+            return
+        if not self._no_critic and (vs is None or vs[:2] != ps[:2] or vs[2] != 1 or vs[3] != ps[3]):
+            return
+        A = self._dims[1]
+        envs = [e for e in (self.env, self.eval_env) if e is not None]
+        if bool(_C.lib().trl_rollout_wide_supported(kind, ps[0], ps[1], A, ps[3])) and \
+                os.environ.get("TRL_NO_RT_ROLLOUT") != "1" and dist.world_size() == 1 and not self.prefetch_noise and \
+                all(bool(getattr(e, "discrete", False)) == self._cat and hasattr(e, "env_B")
+                    and not getattr(e, "is_host_env", False) and not hasattr(e, "_obs_normalizer") for e in envs):
+            self._spec, self._wide, self._head = (ps[0], ps[1], A, ps[3]), True, kind
 
     def _forward(self, net, x, out_dim, out=None):
         """mean / value of an MLP on the device: the fused 2-layer kernel when instantiated, the dense-layer family
@@ -513,7 +536,9 @@ class VecOnPolicyCollector(VecCollector):
             words = 8 + 3 * self.SPECULATIVE_ROWS
             a.publish_dst, a.publish_src, a.publish_words = self._blob_host.data_ptr(), self._blob.data_ptr(), words
             self._published = True
-        if self._ln:                                                    # (either net normed; the head's own arguments)
+        if self._wide:                                                  # 128 / 256 wide: the head's own arguments
+            _C.rollout_wide(a, self._head, self._noise_seed, self._noise_layout(env)[1] if self._cat else 0, env.device)
+        elif self._ln:                                                  # (either net normed; the head's own arguments)
             _C.rollout_ln(a, self._head, ln[0], ln[1], self._noise_seed, self._noise_layout(env)[1] if self._cat else 0, env.device)
         elif self._cat:                                                 # the draw trl_cat_act_f32 makes at these steps
             _C.rollout_cat(a, self._noise_seed, self._noise_layout(env)[1], env.device)

@@ -139,7 +139,7 @@ extern "C" int trl_rollout_sd_supported(int D, int H, int A, int act) { return h
 // head: which entry point (trl_rollout_synth_f32 / _cat_f32 / _sd_f32); cat_seed, cat_env0: the categorical draw's key and
 // first global env index; p->A is the number of actions (HEAD_CAT) or of action dims.  Checks *p and fills the launch
 // descriptor `d` (nothing is launched; with p->n_steps == 0 the caller has nothing to launch either).
-int rollout_synth(const trl_rollout_t* p, int head, int64_t cat_seed, int64_t cat_env0, RolloutDev& d) {
+int rollout_synth(const trl_rollout_t* p, int head, int64_t cat_seed, int64_t cat_env0, RolloutDev& d, bool shape_checked) {
   if (!p) { trl_set_error("rollout: null descriptor"); return TRL_EINVAL; }
   TRL_REQUIRE(p->pf_params && p->env_A && p->env_B, "null network / env pointer");   // (vf_params NULL: no critic)
   TRL_REQUIRE(p->cur_obs && p->t_env && p->cur_step && p->episode_idx && p->ep_return, "null env state pointer");
@@ -162,7 +162,7 @@ int rollout_synth(const trl_rollout_t* p, int head, int64_t cat_seed, int64_t ca
     TRL_REQUIRE(!p->noise_flag && !p->stage_n,
                 "state-dependent std: the noise block is stream-ordered in front of the launch (no noise gate, nothing staged)");
   }
-  if (head != HEAD_GAUSS && !head_supported(head, p->D, p->H, p->A, p->act)) {
+  if (head != HEAD_GAUSS && !shape_checked && !head_supported(head, p->D, p->H, p->A, p->act)) {
     trl_set_error("rollout: %s shape D=%d H=%d A=%d act=%d not instantiated", HEADS[head].name, p->D, p->H, p->A, p->act);
     return TRL_EUNSUPPORTED;
   }

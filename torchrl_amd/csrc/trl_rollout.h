@@ -892,7 +892,8 @@ static inline int value_pass_grid(const RolloutDev& d) {
   return (int)(n_tiles / 4 + 1 < 512 ? n_tiles / 4 + 1 : 512);
 }
 // defined in k_rollout.hip
-int rollout_synth(const trl_rollout_t* p, int head, int64_t cat_seed, int64_t cat_env0, RolloutDev& d);
+// (shape_checked: the caller carries other widths than head_supported's and has checked the shape itself -- k_rollout_wide.hip)
+int rollout_synth(const trl_rollout_t* p, int head, int64_t cat_seed, int64_t cat_env0, RolloutDev& d, bool shape_checked = false);
 int rollout_zero_value(const RolloutDev& d, hipStream_t s);
 int rollout_value_wait(hipStream_t s, hipEvent_t value_wait);
 int rollout_policy_rt(const RolloutDev& d, int head, int act, hipStream_t s);
