@@ -631,6 +631,34 @@ int trl_ppo_ln_reduce_adam_net_f32(const float* partial, const double* scal_part
                                    int head, int ln_mask, float* grads, double* info, const trl_adam_t* adam,
                                    float* workspace, void* stream);
 
+/* --- the fused minibatch update for plain nets of WIDTH 128 (k_ppo_wide.hip) -------------------------------------------
+ * The entry points above for a policy / critic pair of Linear(D, 128), act, Linear(128, 128), act, Linear(128, O) blocks:
+ * a weight-stationary gradient kernel (four waves, wave w keeps hidden rows [32 w, 32 w + 32) of both layers, of W2^T and of
+ * the dW2 / dW1 accumulators in registers; a workgroup walks trl_ppo_wide_tile()-sample tiles whose activations cross the
+ * waves through LDS).  `head`: 0 Gaussian with a shared logstd, 1 categorical, 2 state-dependent-std; args (every n_wg_pf and
+ * loss mode), flat blocks [W1 b1 W2 b2 W3 b3 (logstd)], rows, scalar rows, info and the per-sample loss arithmetic are that
+ * head's (above).  Shapes: trl_ppo_wide_supported (TRL_EUNSUPPORTED otherwise): H == 128, 2 <= D <= 32, A in the head's
+ * range, Tanh / ReLU.  partial rows are trl_ppo_wide_partial_stride floats.  The folds are the kernels of the plain entry
+ * points launched with this pair's block lengths and stride, the fold / clip / Adam launch as a job loop on a bounded,
+ * always co-resident grid (workspace: trl_ppo_wide_reduce_adam_workspace floats, zeroed once); optimiser groups
+ * [policy | value] of those lengths.  A single-network launch folded by trl_ppo_wide_reduce_adam_net_f32 gives the bits of
+ * the joint launch + trl_ppo_wide_reduce_adam_f32.  trl_ppo_wide_wg_split: how many of n_wg >= 2 workgroups run the policy
+ * when each network has n_tiles tiles of trl_ppo_wide_tile() samples.  There is no cross-rank variant. */
+int trl_ppo_wide_supported(int D, int H, int A, int act, int head);
+int trl_ppo_wide_tile(void);
+int trl_ppo_wide_partial_stride(int D, int H, int A, int head);
+int trl_ppo_wide_wg_split(int n_tiles, int n_wg);
+int trl_ppo_wide_minibatch_grad_f32(const trl_ppo_batch_t* args, int head, void* stream);
+int trl_ppo_wide_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                            int head, const float* pf_params, float* grads, double* info, void* stream);
+int trl_ppo_wide_reduce_adam_workspace(int D, int H, int A, int head);
+int trl_ppo_wide_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                                 int head, float* grads, double* info, const trl_adam_t* adam, float* workspace,
+                                 void* stream);
+int trl_ppo_wide_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net, int D, int H, int A,
+                                     int head, float* grads, double* info, const trl_adam_t* adam, float* workspace,
+                                     void* stream);
+
 typedef struct trl_comm trl_comm_t;   /* opaque communicator, see the collectives section below */
 /* --- C1 / C2 / C3: collectives of the multi-GPU path ---------------
  * The reference has no distributed backend; with envs sharded by index over one process per GPU

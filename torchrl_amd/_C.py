@@ -277,6 +277,18 @@ SIGNATURES = {
                                                                                        C.c_void_p, C.c_void_p]),
     "trl_ppo_ln_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(AdamArgs),
                                                                                            C.c_void_p, C.c_void_p]),
+    # 128-wide plain pairs (k_ppo_wide.hip): (..., head) behind the shape
+    "trl_ppo_wide_supported": (C.c_int, [C.c_int] * 5),
+    "trl_ppo_wide_tile": (C.c_int, []),
+    "trl_ppo_wide_partial_stride": (C.c_int, [C.c_int] * 4),
+    "trl_ppo_wide_wg_split": (C.c_int, [C.c_int] * 2),
+    "trl_ppo_wide_minibatch_grad_f32": (C.c_int, [C.POINTER(PpoBatchArgs), C.c_int, C.c_void_p]),
+    "trl_ppo_wide_reduce_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4),
+    "trl_ppo_wide_reduce_adam_workspace": (C.c_int, [C.c_int] * 4),
+    "trl_ppo_wide_reduce_adam_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.POINTER(AdamArgs),
+                                                                                         C.c_void_p, C.c_void_p]),
+    "trl_ppo_wide_reduce_adam_net_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.POINTER(AdamArgs),
+                                                                                             C.c_void_p, C.c_void_p]),
     "trl_synth_reset_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "trl_gauss_logp_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "trl_concat2_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
@@ -793,6 +805,27 @@ def ppo_ln_reduce(partial, scal_partial, n_wg, D, H, A, head, ln_mask, grads, in
                                       dev_ptr(pf_params, name="pf_params", allow_none=True),
                                       dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
                                       stream_ptr(partial.device)), "trl_ppo_ln_reduce_f32")
+
+
+def ppo_wide_partial_stride(D, H, A, head):
+    """Floats of a partial row for a plain 128-wide pair (k_ppo_wide.hip)."""
+    ps = lib().trl_ppo_wide_partial_stride(D, H, A, head)
+    if ps < 0:
+        check(ps, "trl_ppo_wide_partial_stride")
+    return ps
+
+
+def ppo_wide_minibatch_grad(args, head, device):
+    """The fused minibatch gradient for a plain 128-wide pair: blocks [W1 b1 W2 b2 W3 b3 (logstd)]."""
+    check(lib().trl_ppo_wide_minibatch_grad_f32(C.byref(args), head, stream_ptr(device)), "trl_ppo_wide_minibatch_grad_f32")
+
+
+def ppo_wide_reduce(partial, scal_partial, n_wg, D, H, A, head, grads, info, pf_params=None, n_wg_pf=0):
+    check(lib().trl_ppo_wide_reduce_f32(dev_ptr(partial, name="partial"),
+                                        dev_ptr(scal_partial, torch.float64, "scal_partial"), n_wg, n_wg_pf, D, H, A, head,
+                                        dev_ptr(pf_params, name="pf_params", allow_none=True),
+                                        dev_ptr(grads, name="grads"), dev_ptr(info, torch.float64, "info"),
+                                        stream_ptr(partial.device)), "trl_ppo_wide_reduce_f32")
 
 
 def ppo_minibatch_grad(args, device):

@@ -170,9 +170,12 @@ class _FusedPPO:
             raise _C.TrlError(needs)
         self.head = head_kind(pf, refuse=needs)
         self.categorical, self.state_std = self.head == HEAD_CAT, self.head == HEAD_SD
+        # TRL_WIDE_FUSED_UPDATE=1 (`make_engine`): a plain pair of width 128 is carried by the weight-stationary gradient
+        # kernel (trl_ppo_wide_*), whatever the head; every other width keeps the 64-wide kernels' checks
+        self.wide = bool(_wide_fused_update() and not self.ln_mask and ps[1] == _WIDE_H)
         if self.head != HEAD_GAUSS:
             ps = _head_spec(self.head, ps)
-            why = _fused_head_refusal(self.head, ps)
+            why = None if self.wide else _fused_head_refusal(self.head, ps)
             if why:
                 raise _C.TrlError(why)
         if vf is not None and (vs[0] != ps[0] or vs[1] != ps[1] or vs[2] != 1 or vs[3] != ps[3]):
@@ -209,6 +212,15 @@ class _FusedPPO:
             self._k_fold_x = self._k_fold_net_x = None
             self.one_rank = "the fused LayerNorm update runs on one rank (no cross-rank fold exists for it)"
             self.p_stride = _C.ppo_ln_partial_stride(self.D, self.H, self.A, hd, mask)
+        elif self.wide:
+            # the wide entry points take `head` behind the shape: the same call sites, the head bound here
+            hd = self.head
+            bound = lambda name: ((lambda *a: getattr(lib, name)(*a[:7], hd, *a[7:])), name)
+            self._k_grad = ((lambda g, stream: lib.trl_ppo_wide_minibatch_grad_f32(g, hd, stream)), "trl_ppo_wide_minibatch_grad_f32")
+            self._k_fold, self._k_fold_net = bound("trl_ppo_wide_reduce_adam_f32"), bound("trl_ppo_wide_reduce_adam_net_f32")
+            self._k_fold_x = self._k_fold_net_x = None
+            self.one_rank = "the fused 128-wide update runs on one rank (no cross-rank fold exists for it)"
+            self.p_stride = _C.ppo_wide_partial_stride(self.D, self.H, self.A, hd)
         else:
             self.p_stride = getattr(_C, "ppo_%spartial_stride" % sfx)(self.D, self.H, self.A)
         # doubles of scalar statistics per workgroup (SD: a second block of rows behind the n_wg x 8 of every head)
@@ -218,6 +230,7 @@ class _FusedPPO:
         self.partial = torch.zeros(self.max_wg, self.p_stride, device=self.dev)
         self.scal = torch.zeros(self.max_wg, self.scal_w, dtype=torch.float64, device=self.dev)
         n_ws = lib.trl_ppo_ln_reduce_adam_workspace(self.D, self.H, self.A, self.head, self.ln_mask) if self.ln_mask else \
+            lib.trl_ppo_wide_reduce_adam_workspace(self.D, self.H, self.A, self.head) if self.wide else \
             getattr(lib, "trl_ppo_%sreduce_adam_workspace" % sfx)(self.D, self.H, self.A)
         self.red_ws = torch.zeros(n_ws, device=self.dev)              # Adam header + norm granules of the fold / clip / Adam launch
         # One process: the critic's and the actor's updates of an epoch (ppo.py:93-122 / 41-91: separate networks, optimisers,
@@ -284,6 +297,8 @@ class _FusedPPO:
 
     def _n_wg(self, n_samples):
         """(workgroups to launch, how many of them run the policy) for one minibatch."""
+        if self.wide:
+            return self._n_wg_wide(n_samples)
         tiles = (n_samples + 15) // 16
         n_wg = 2 * max(1, min(self.max_wg // 2, (tiles + 3) // 4))
         n_pf = _C.lib().trl_ppo_wg_split(self.D, self.H, self.A, tiles, n_wg)
@@ -300,6 +315,20 @@ class _FusedPPO:
             cands = [x for x in (n_pf // 8 * 8, -(-n_pf // 8) * 8) if 0 < x < n_wg]
             if cands:
                 n_pf = min(cands, key=lambda x: (cost(x), abs(x - n_pf)))
+        return n_wg, n_pf
+
+    def _n_wg_wide(self, n_samples, policy_only=False):
+        """`_n_wg` of the 128-wide route: a workgroup walks whole tiles of trl_ppo_wide_tile() samples, one at a time, so a
+        network gets up to one workgroup per tile while the chip has room; the split is trl_ppo_wide_wg_split's."""
+        lib = _C.lib()
+        tiles = -(-n_samples // lib.trl_ppo_wide_tile())
+        if policy_only:
+            n_wg = max(1, min(self.max_wg, tiles))
+            return n_wg, n_wg
+        n_wg = 2 * max(1, min(self.max_wg // 2, tiles))
+        n_pf = lib.trl_ppo_wide_wg_split(tiles, n_wg)
+        if not 0 < n_pf < n_wg:
+            raise _C.TrlError("trl_ppo_wide_wg_split(%d tiles, %d workgroups) returned %d" % (tiles, n_wg, n_pf))
         return n_wg, n_pf
 
     def _buffers(self, K, rows_mb):
@@ -416,6 +445,7 @@ class _FusedPPO:
 
     defers = True                                                    # run(..., defer=True) is implemented
     one_rank = None                                                  # (the refusal's text, where an engine runs on one rank only)
+    wide = False                                                     # the 128-wide route (set by `_FusedPPO.__init__`)
 
     def run(self, t, row_idx, N, pre=None, pre_key=None, defer=False):
         """t: dict of (rows, N, feat) device tensors; row_idx: (K, rows_mb) host int64.
@@ -801,6 +831,34 @@ def _ln_fused_update():
     return os.environ.get("TRL_LN_FUSED_UPDATE") == "1"
 
 
+_WIDE_H = 128                                                         # the width of k_ppo_wide.hip (trl_ppo_wide_supported)
+
+
+def _wide_fused_update():
+    """TRL_WIDE_FUSED_UPDATE=1: plain pairs of width 128 take the two-launch update (k_ppo_wide.hip).  Unset, they run on the
+    generic engine, as they always have (opt-in, like TRL_WIDE_FUSED_ROLLOUT)."""
+    return os.environ.get("TRL_WIDE_FUSED_UPDATE") == "1"
+
+
+def _wide_fused_pair(algo, pf, vf, kind):
+    """Does the fused engine carry this pair under TRL_WIDE_FUSED_UPDATE=1?  Every network is a plain `mlp2_spec` block of
+    width 128; input and activation match; the head's shape is in its range; both optimisers are Adam; one rank."""
+    nets = [pf] + ([] if vf is None else [vf])
+    if any(getattr(n, "add_ln", False) or not hasattr(n, "mlp2_spec") for n in nets):
+        return False
+    specs = [n.mlp2_spec() for n in nets]
+    if any(s is None for s in specs):
+        return False
+    ps = _head_spec(kind, specs[0])
+    if vf is not None and tuple(specs[1]) != (ps[0], ps[1], 1, ps[3]):
+        return False
+    if kind == HEAD_GAUSS and not hasattr(pf, "logstd"):
+        return False
+    opts = [getattr(algo, name, None) for name in ("pf_optimizer",) + (() if vf is None else ("vf_optimizer",))]
+    return bool(_C.lib().trl_ppo_wide_supported(ps[0], ps[1], ps[2], ps[3], kind)) and \
+        all(type(o) is optim.Adam for o in opts) and not dist.collectives_active()
+
+
 def _ln_fused_pair(algo, pf, vf, kind):
     """Does the fused engine carry this pair under TRL_LN_FUSED_UPDATE=1?  Every network is an `mlp2_spec` or an
     `mlp2_ln_spec` block and at least one the latter; input, width (64) and activation match; the head's shape is in its
@@ -1026,6 +1084,8 @@ def make_engine(algo, fused=_FusedPPO, generic=_GenericPPO):
     opt = getattr(algo, "pf_optimizer", None)
     if _ln_fused_update() and not forced and kind in (HEAD_GAUSS, HEAD_CAT, HEAD_SD) and _ln_fused_pair(algo, pf, vf, kind):
         return fused(algo)                                             # `add_ln` pairs, 64 wide (opt-in)
+    if _wide_fused_update() and not forced and kind in (HEAD_GAUSS, HEAD_CAT, HEAD_SD) and _wide_fused_pair(algo, pf, vf, kind):
+        return fused(algo)                                             # plain pairs, 128 wide (opt-in)
     if opt is not None and type(opt) is not optim.Adam:
         return generic(algo)                                           # RMSprop / SGD: the fused fold / clip / Adam launches are Adam's
     if kind in _HEAD_OPT_IN:

@@ -87,6 +87,8 @@ class _PolicyOnly:
     def _n_wg(self, n_samples):
         """Workgroups of one minibatch's gradient launch, all of them the policy's: one 16-sample tile per wave while the
         chip has room."""
+        if self.wide:
+            return self._n_wg_wide(n_samples, policy_only=True)
         tiles = (n_samples + 15) // 16
         n_wg = max(1, min(self.max_wg, (tiles + 3) // 4))
         return n_wg, n_wg

@@ -24,6 +24,7 @@
 #include "trl_head.h"
 #include "trl_comm.h"
 #include "trl_ppo_wave.h"
+#include "trl_ppo_wide.h"
 
 // ---------------------------------------------------------------- partial reduce
 // grads[p] = sum_w partial[w][p] in fixed order; info[] from the scalar partials:
@@ -518,7 +519,14 @@ __global__ __launch_bounds__(256) void mlp2_forward_kernel(const float* __restri
 // (ppo_wave_pass<..., RT = true, HEAD>: the 17- and the 32-wide tile).  The flat policy block is [W1 b1 W2 b2 W3 b3] with
 // the head's rows, and the Gaussian's logstd tail: up to 1040 head floats (SD, 2A rows) against the Gaussian's 528.
 // ln_mask (trl_ppo_ln_*): bit 0 the policy, bit 1 the critic carries a LayerNorm -- 128 more floats in that net's block
+// ln_mask == PPO_WIDE_MASK (trl_ppo_wide_*): a plain pair of width 128, the rows of k_ppo_wide.hip
 static int ppo_stride_for(int D, int H, int A, int head, int ln_mask = 0) {
+  if (ln_mask == PPO_WIDE_MASK) {
+    if (ppo_wide_ok(head, D, H, A, TRL_ACT_TANH)) return ppo_ln_stride(D, H, A, head, 0);
+    trl_set_error("trl_ppo_wide: head %d, shape D=%d H=%d A=%d outside what the wide instantiations carry (H == 128, 2 <= D <= 32, "
+                  "A in the head's range)", head, D, H, A);
+    return TRL_EUNSUPPORTED;
+  }
   if (head == HEAD_GAUSS && SHAPE_IS(17, 64, 6) && !ln_mask) return PpoShape<17, 64, 6>::P_STRIDE;
   if (head_shape_ok(head, D, H, A)) return ppo_ln_stride(D, H, A, head, ln_mask);
   trl_set_error("trl_ppo_%spartial_stride: shape D=%d H=%d A=%d not instantiated (H == 64, 2 <= D <= 32, %d <= A <= %d)",
@@ -769,6 +777,37 @@ extern "C" int trl_ppo_ln_reduce_adam_net_f32(const float* partial, const double
   TRL_REQUIRE(ln_args_ok(head, ln_mask), "head must be 0..2 and ln_mask 1..3");
   TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
   return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr, 0, stream, net, head, ln_mask);
+}
+
+// The folds behind trl_ppo_wide_minibatch_grad_f32 (k_ppo_wide.hip): the same kernels again, launched with the block lengths
+// and the stride of a plain 128-wide pair.  A policy block is up to 22.8 k floats -- ~360 jobs of 64 parameters per network,
+// against the 64-wide pair's ~100 -- so the fold / clip / Adam launch takes the job-loop form (LOOP = true) on a grid of
+// PPO_WIDE_FOLD_BLOCKS blocks (half of it for one network's `_net` fold, two of which may wait beside each other): every
+// block is resident while it polls, whatever the job count.  The kernel is untouched: its slot poll already strides over any
+// number of slots, and the workspace query sizes the slots from the job count.  One rank: there is no cross-rank variant.
+extern "C" int trl_ppo_wide_reduce_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H, int A,
+                                       int head, const float* pf_params, float* grads, double* info, void* stream) {
+  TRL_REQUIRE(head >= HEAD_GAUSS && head <= HEAD_SD, "head must be 0..2");
+  return launch_reduce(partial, scal_partial, n_wg, n_wg_pf, D, H, A, pf_params, grads, info, stream, head, PPO_WIDE_MASK);
+}
+extern "C" int trl_ppo_wide_reduce_adam_workspace(int D, int H, int A, int head) {
+  TRL_REQUIRE(head >= HEAD_GAUSS && head <= HEAD_SD, "head must be 0..2");
+  return reduce_adam_workspace(D, H, A, head, PPO_WIDE_MASK);
+}
+extern "C" int trl_ppo_wide_reduce_adam_f32(const float* partial, const double* scal_partial, int n_wg, int n_wg_pf, int D, int H,
+                                            int A, int head, float* grads, double* info, const trl_adam_t* adam,
+                                            float* workspace, void* stream) {
+  TRL_REQUIRE(head >= HEAD_GAUSS && head <= HEAD_SD, "head must be 0..2");
+  return launch_reduce_adam(partial, scal_partial, n_wg, n_wg_pf, D, H, A, grads, info, adam, workspace, nullptr,
+                            PPO_WIDE_FOLD_BLOCKS, stream, -1, head, PPO_WIDE_MASK);
+}
+extern "C" int trl_ppo_wide_reduce_adam_net_f32(const float* partial, const double* scal_partial, int n_wg, int net, int D, int H,
+                                                int A, int head, float* grads, double* info, const trl_adam_t* adam,
+                                                float* workspace, void* stream) {
+  TRL_REQUIRE(head >= HEAD_GAUSS && head <= HEAD_SD, "head must be 0..2");
+  TRL_REQUIRE(net == 0 || net == 1, "net: 0 = policy, 1 = value function");
+  return launch_reduce_adam(partial, scal_partial, n_wg, 0, D, H, A, grads, info, adam, workspace, nullptr,
+                            PPO_WIDE_FOLD_BLOCKS / 2, stream, net, head, PPO_WIDE_MASK);
 }
 
 // Env shards on several ranks: the same launch with the gradient SUM over ranks between the fold and the clip
