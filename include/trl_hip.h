@@ -248,6 +248,19 @@ int trl_rollout_ln_supported(int head, int D, int H, int A, int act);
  * 2 <= D <= 32, the head's own range of A, Tanh or ReLU.  n_steps == 0: nothing is launched. */
 int trl_rollout_synth_wide_f32(const trl_rollout_t* args, int head, int64_t noise_seed, int64_t env_offset, void* stream);
 int trl_rollout_wide_supported(int head, int D, int H, int A, int act);
+/* The wide rollout for `add_ln=True` networks of width H = 128 or 256 (k_rollout_wide_ln.hip): Linear(D, H), act, LayerNorm(H),
+ * Linear(H, H), act, act, Linear(H, O).  head, noise_seed, env_offset as for trl_rollout_synth_wide_f32; pf_ln / vf_ln: which
+ * of the two networks carries the LayerNorm, independently, as for trl_rollout_synth_ln_f32 -- at least one of them must (a
+ * plain pair is trl_rollout_synth_wide_f32's: TRL_EINVAL), a network without one keeps its [W1 b1 W2 b2 W3 b3 (logstd)] block
+ * and runs the plain wide kernel, a normed one's block is
+ *     W1 (H, D) | b1 | gamma1 (H) | beta1 (H) | W2 (H, H) | b2 | W3 (O, H) | b3 (| logstd (A), Gaussian policy),
+ * read in place.  The row statistics are the exact combination of per-wave means and squared deviations about them
+ * (no E[x^2] - E[x]^2), eps = 1e-5, biased variance; gamma and beta are folded into W2 and b2 once per launch.  vf_params
+ * NULL: no critic.  args->norm_state / noise_flag / stage_n must be unset (TRL_EINVAL); shapes:
+ * trl_rollout_wide_ln_supported (TRL_EUNSUPPORTED otherwise) -- those of trl_rollout_wide_supported. */
+int trl_rollout_synth_wide_ln_f32(const trl_rollout_t* args, int head, int pf_ln, int vf_ln, int64_t noise_seed,
+                                  int64_t env_offset, void* stream);
+int trl_rollout_wide_ln_supported(int head, int D, int H, int A, int act);
 /* Page-locked host block -> device buffer by a KERNEL (the device reads host memory in place), meant for a stream of
  * its own next to the one that computes: n floats (n % 4 == 0, 16-byte aligned pointers); when every workgroup's part is
  * in device memory, state[0] = stamp is stored with device scope -- what a consumer launched on another stream polls

@@ -192,6 +192,8 @@ SIGNATURES = {
     "trl_rollout_ln_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_rollout_synth_wide_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "trl_rollout_wide_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "trl_rollout_synth_wide_ln_f32": (C.c_int, [C.POINTER(RolloutArgs), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "trl_rollout_wide_ln_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "trl_stage_h2d_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "trl_ppo_partial_stride": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "trl_mlp2_forward_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
@@ -735,6 +737,13 @@ def rollout_wide(args, head, noise_seed, env_offset, device):
     categorical / state-dependent std, args as for `rollout` / `rollout_cat` / `rollout_sd`."""
     check(lib().trl_rollout_synth_wide_f32(C.byref(args), int(head), int(noise_seed), int(env_offset), stream_ptr(device)),
           "trl_rollout_synth_wide_f32")
+
+
+def rollout_wide_ln(args, head, pf_ln, vf_ln, noise_seed, env_offset, device):
+    """The persistent rollout for 128- / 256-wide `add_ln` networks (args.H): head as for `rollout_wide`, pf_ln / vf_ln which of
+    the two nets carries the LayerNorm (at least one); a normed net's block is in `ops.plan_params` order."""
+    check(lib().trl_rollout_synth_wide_ln_f32(C.byref(args), int(head), int(bool(pf_ln)), int(bool(vf_ln)), int(noise_seed),
+                                              int(env_offset), stream_ptr(device)), "trl_rollout_synth_wide_ln_f32")
 
 
 def _partial_stride(name, D, H, A):

@@ -10,14 +10,14 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libtrl_hip.so")
 NOISE_LIB = os.path.join(LIB_DIR, "libtrl_noise.so")     # host helper of the reference noise stream; links libtorch (optional)
 NOISE_SRC = "trl_noise_ext.cpp"
-SOURCES = ["trl_host.cpp", "trl_mtjump.cpp", "k_gae.hip", "k_gather.hip", "k_ppo.hip", "k_ppo_ln.hip", "k_ppo_wide.hip", "k_optim.hip", "k_ppo_generic.hip", "k_categorical.hip", "k_gauss_sd.hip", "k_layernorm.hip", "k_vmpo.hip", "k_trpo.hip", "k_rollout.hip", "k_rollout_ln.hip", "k_rollout_wide.hip", "k_gemm.hip", "k_mlp3.hip", "k_conv1.hip", "k_conv_dx.hip", "k_sac.hip", "k_conv.hip", "k_dqn.hip", "k_bootdqn.hip", "k_norm.hip", "k_frames.hip", "k_comm.hip", "k_peaks.hip"]
+SOURCES = ["trl_host.cpp", "trl_mtjump.cpp", "k_gae.hip", "k_gather.hip", "k_ppo.hip", "k_ppo_ln.hip", "k_ppo_wide.hip", "k_optim.hip", "k_ppo_generic.hip", "k_categorical.hip", "k_gauss_sd.hip", "k_layernorm.hip", "k_vmpo.hip", "k_trpo.hip", "k_rollout.hip", "k_rollout_ln.hip", "k_rollout_wide.hip", "k_rollout_wide_ln.hip", "k_gemm.hip", "k_mlp3.hip", "k_conv1.hip", "k_conv_dx.hip", "k_sac.hip", "k_conv.hip", "k_dqn.hip", "k_bootdqn.hip", "k_norm.hip", "k_frames.hip", "k_comm.hip", "k_peaks.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]
 # per-source flags.  k_mlp3.hip: no packed-fp32 VALU forms in its LayerNorm pass (its plain kernels emit none either way);
-# k_rollout_ln.hip / k_ppo_ln.hip: the same for the LayerNorm rollout / gradient instantiations, which is why they have files
-# of their own
+# k_rollout_ln.hip / k_rollout_wide_ln.hip / k_ppo_ln.hip: the same for the LayerNorm rollout / gradient instantiations, which is
+# why they have files of their own
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"k_mlp3.hip": _NO_PK, "k_rollout_ln.hip": _NO_PK, "k_ppo_ln.hip": _NO_PK}
+SOURCE_FLAGS = {"k_mlp3.hip": _NO_PK, "k_rollout_ln.hip": _NO_PK, "k_rollout_wide_ln.hip": _NO_PK, "k_ppo_ln.hip": _NO_PK}
 
 
 def _stale():

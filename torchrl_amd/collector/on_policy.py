@@ -376,14 +376,14 @@ class VecOnPolicyCollector(VecCollector):
         self._wide = False
         if os.environ.get("TRL_WIDE_FUSED_ROLLOUT") == "1":
             self._wide_fused_route(kind, ps, vs)
+        self._wide_ln = False
+        if os.environ.get("TRL_WIDE_LN_FUSED_ROLLOUT") == "1":
+            self._wide_ln_fused_route(kind)
 
-    def _ln_fused_route(self, kind):
-        """`add_ln` nets (`mlp2_spec()` is None for them, so everything above chose the per-step route): the persistent
-        rollout's LayerNorm variant (trl_rollout_synth_ln_f32) carries a pair of which at least one net is the two-layer
-        `add_ln` block (`Net.mlp2_ln_spec`) and the other that or a plain MLP2 block, 64 wide, same input and activation,
-        a head shape of the head's range, on a device synthetic env of the head's kind, one rank, no observation normaliser,
-        no noise prefetch.  Opt-in, TRL_LN_FUSED_ROLLOUT=1 (profiles/NOTES_layernorm_rollout.md); TRL_NO_RT_ROLLOUT=1
-        switches it off like the other runtime-dims instantiations.  `_ln` = (policy normed, critic normed)."""
+    def _ln_pair_specs(self):
+        """((D, H, head width, act) of the policy, (policy normed, critic normed)) of a two-layer pair of which at least one net
+        is the `add_ln` block (`Net.mlp2_ln_spec`) and the other that or a plain MLP2 block of the same input, width and
+        activation (or a ZeroNet critic); None for every other pair."""
         def spec_of(net):
             if not hasattr(net, "mlp2_ln_spec"):
                 return None
@@ -392,9 +392,40 @@ class VecOnPolicyCollector(VecCollector):
         vf_ln = not self._no_critic and bool(getattr(self.vf, "add_ln", False))
         ps, vs = spec_of(self.pf), None if self._no_critic else spec_of(self.vf)
         if not (pf_ln or vf_ln) or ps is None or ps[2] != self._head_w:
-            return
+            return None
         if not self._no_critic and (vs is None or vs[:2] != ps[:2] or vs[2] != 1 or vs[3] != ps[3]):
+            return None
+        return ps, (pf_ln, vf_ln)
+
+    def _wide_ln_fused_route(self, kind):
+        """128- and 256-wide `add_ln` pairs (everything above chose the per-step route for them): the wide rollout's LayerNorm
+        variant (trl_rollout_synth_wide_ln_f32, k_rollout_wide_ln.hip) under `_ln_fused_route`'s conditions with the width test
+        replaced by trl_rollout_wide_ln_supported.  Opt-in, TRL_WIDE_LN_FUSED_ROLLOUT=1
+        (profiles/NOTES_wide_layernorm_rollout.md); TRL_NO_RT_ROLLOUT=1 switches it off like the other runtime-dims
+        instantiations.  The update of such nets stays on the generic engine, which homes them in plan order."""
+        pair = self._ln_pair_specs()
+        if pair is None:
             return
+        ps, ln = pair
+        A = self._dims[1]
+        envs = [e for e in (self.env, self.eval_env) if e is not None]
+        if bool(_C.lib().trl_rollout_wide_ln_supported(kind, ps[0], ps[1], A, ps[3])) and \
+                os.environ.get("TRL_NO_RT_ROLLOUT") != "1" and dist.world_size() == 1 and not self.prefetch_noise and \
+                all(bool(getattr(e, "discrete", False)) == self._cat and hasattr(e, "env_B")
+                    and not getattr(e, "is_host_env", False) and not hasattr(e, "_obs_normalizer") for e in envs):
+            self._spec, self._mlp2, self._ln, self._head, self._wide_ln = (ps[0], ps[1], A, ps[3]), None, ln, kind, True
+
+    def _ln_fused_route(self, kind):
+        """`add_ln` nets (`mlp2_spec()` is None for them, so everything above chose the per-step route): the persistent
+        rollout's LayerNorm variant (trl_rollout_synth_ln_f32) carries a pair of which at least one net is the two-layer
+        `add_ln` block (`Net.mlp2_ln_spec`) and the other that or a plain MLP2 block, 64 wide, same input and activation,
+        a head shape of the head's range, on a device synthetic env of the head's kind, one rank, no observation normaliser,
+        no noise prefetch.  Opt-in, TRL_LN_FUSED_ROLLOUT=1 (profiles/NOTES_layernorm_rollout.md); TRL_NO_RT_ROLLOUT=1
+        switches it off like the other runtime-dims instantiations.  `_ln` = (policy normed, critic normed)."""
+        pair = self._ln_pair_specs()
+        if pair is None:
+            return
+        ps, (pf_ln, vf_ln) = pair
         A = self._dims[1]
         envs = [e for e in (self.env, self.eval_env) if e is not None]
         if bool(_C.lib().trl_rollout_ln_supported(kind, ps[0], ps[1], A, ps[3])) and \
@@ -538,6 +569,9 @@ class VecOnPolicyCollector(VecCollector):
             self._published = True
         if self._wide:                                                  # 128 / 256 wide: the head's own arguments
             _C.rollout_wide(a, self._head, self._noise_seed, self._noise_layout(env)[1] if self._cat else 0, env.device)
+        elif self._wide_ln:                                             # ... with either net normed
+            _C.rollout_wide_ln(a, self._head, ln[0], ln[1], self._noise_seed, self._noise_layout(env)[1] if self._cat else 0,
+                               env.device)
         elif self._ln:                                                  # (either net normed; the head's own arguments)
             _C.rollout_ln(a, self._head, ln[0], ln[1], self._noise_seed, self._noise_layout(env)[1] if self._cat else 0, env.device)
         elif self._cat:                                                 # the draw trl_cat_act_f32 makes at these steps
